@@ -10,10 +10,16 @@ barrier + device synchronisation on both sides; the maximum over ranks is report
 nGlobal * K / seconds.  Atoms are resident in HBM when the timed region starts (they are generated on the host once,
 uploaded by CopyDataToGpu, and never leave the device).
 
+A plain run does only what the headline needs: set up, W warm-up steps, the K timed steps, the result line.
+--dump-outputs DIR writes what the timed path computed in its last step (a fixed, seeded sample of the atoms' positions, momenta,
+forces and energies, plus the global energies) as DIR/<name>.npy, float64.  --full adds everything below that is not `roofline`
+(and, for N > 1, the sized-vs-handshake self-check).
+
 Extra objects on the JSON line:
   roofline     : the dominant kernel (the LJ or EAM force kernel) against the 8 TB/s HBM roof, from HIP events recorded
                  on the launch stream around every force launch of the timed region (comdForceTiming*).
                  Algorithmic bytes per atom: LJ force 56 B, EAM force (3 passes) 176 B.
+  --full only:
   cpu_baseline : the CPU restatement (oracle/, kind "port") timed on this host's cores on a bounded sample of the same
                  workload (same potential, same density, fewer atoms and steps), rank 0 at N = 1 only.
   variants     : N = 1 only: the same K timed steps with the other force methods (cta_cell, the Verlet-list method
@@ -66,15 +72,37 @@ def parse():
     ap.add_argument("--nx", type=int, default=80, help="unit cells per GPU along each axis")
     ap.add_argument("--async-halo", type=int, default=None, help="-a flag: overlap interior force with the halo exchange")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the other force methods (reported as `variants` at N = 1)")
+    ap.add_argument("--no-variants", action="store_true", help="skip the other force methods (reported as `variants` by a --full run at N = 1)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    ap.add_argument("--no-target-line", action="store_true", help="skip the LJ 256^3 leg (N = 1 default run)")
+    ap.add_argument("--no-target-line", action="store_true", help="skip the LJ 256^3 leg (N = 1 --full run)")
     ap.add_argument("--precision", choices=["double", "single"], default="double",
-                    help="single: the PRECISION=single build (real_t = float); never the headline -- the default run reports it as a variant")
+                    help="single: the PRECISION=single build (real_t = float); never the headline -- a --full run reports it as a variant")
     ap.add_argument("--allow-host-staged", action="store_true",
                     help="N > 1 only: if the RCCL communicator cannot be formed, run over host-staged gloo messages instead of failing "
                          "(the line then carries \"measured\": false -- it is a functional rehearsal, not an xGMI number)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: cpu_baseline, variants (other methods, potential, precision), "
+                         "target_line, and for N > 1 the sized-vs-handshake self-check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="one rank only: after the timed steps write what their last step computed to DIR/<name>.npy (float64)")
     return ap.parse_args()
+
+
+DUMP_SEED = 20261016
+DUMP_SAMPLE = 1 << 18                              # atoms kept when the system is larger: 11 float64 per atom, 23 MB in all
+
+
+def dump_outputs(sim, directory):
+    """The state a caller of timestep() receives after the last timed step: positions, momenta, forces and per-atom energies of a
+    fixed, seeded sample of the atoms (by gid), and the global (ePotential, eKinetic, nGlobal)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    n = sim.n_global
+    gids = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+    np.save(os.path.join(directory, "gid.npy"), gids.astype(np.float64))
+    for which, name in ((0, "positions"), (1, "momenta"), (2, "forces"), (3, "atom_energy")):
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(sim.gather(which)[gids], dtype=np.float64))
+    np.save(os.path.join(directory, "energy.npy"), np.array(sim.energy(), dtype=np.float64))
 
 
 class stdout_to_stderr:
@@ -196,6 +224,8 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if a.dump_outputs and world > 1:
+        sys.exit("bench.py: --dump-outputs needs a one-rank run (a rank holds only its own atoms)")
     if world != a.gpus:
         if world == 1 and a.gpus > 1:
             sys.exit("bench.py --gpus N>1 must be launched with torch.distributed.run --nproc-per-node N")
@@ -288,9 +318,10 @@ def main():
             return float(t[0])
         return seconds
 
-    def measure(pot, meth, steps, warmup, nx=None, mem=False, handshake=False):
+    def measure(pot, meth, steps, warmup, nx=None, mem=False, handshake=False, dump=None):
         """One Simulation of `pot`/`meth`: W untimed steps, then exactly K steps between barrier + device syncs.
-        handshake: exact message sizes are swapped before every exchange (COMD_HALO_HANDSHAKE=1) -- the cross-check of the sized protocol."""
+        handshake: exact message sizes are swapped before every exchange (COMD_HALO_HANDSHAKE=1) -- the cross-check of the sized protocol.
+        dump: a directory that receives what the last timed step computed (dump_outputs), written after the timed region."""
         nx = nx or a.nx
         pairlist = meth == "cta_cell_pairlist"                # the reference's -L: pairlist bits for the CTA-per-cell LJ kernel
         args = ["-x", nx * px, "-y", nx * py, "-z", nx * pz, "-i", px, "-j", py, "-k", pz,
@@ -321,13 +352,15 @@ def main():
         ep, ek, n_global = sim.energy()
         sim.sum_atoms()
         assert sim.energy()[2] == n_global, "atoms were lost"
+        if dump:
+            dump_outputs(sim, dump)
         res = {"elapsed": elapsed, "force_ms": force_ms, "aux_ms": aux_ms, "launches": n_launch, "ep": ep, "ek": ek, "n_global": n_global,
                "cap": sim.max_atoms, "nl_builds": sim.nl_builds - builds0, "e_initial": e0[0] + e0[1], "path": sim.force_path_info(),
                "mem_GB": {"simulation": (free0 - free1) / 1e9, "allocated_by_the_first_steps": (free1 - free2) / 1e9} if mem else None}
         sim.close()
         return res
 
-    m = measure(a.pot, method, a.steps, a.warmup)
+    m = measure(a.pot, method, a.steps, a.warmup, dump=a.dump_outputs)
     elapsed, force_ms, n_global, ep, ek = m["elapsed"], m["force_ms"], m["n_global"], m["ep"], m["ek"]
 
     if rank == 0:
@@ -362,7 +395,7 @@ def main():
     # bit-reproducible, so the two must agree to the last bit -- a mis-paired same-peer message (decomposition.c:57-66: two ranks on an axis make both
     # neighbours of a phase ONE peer) or a truncated one cannot.
     mismatch = False
-    if (a.gpus > 1 or loopback) and (transport is not None or dist is not None):
+    if a.full and (a.gpus > 1 or loopback) and (transport is not None or dist is not None):
         # (COMD_BENCH_SELFTEST_PERTURB=1, tests only: the second run takes one step more, so that the comparison can be seen to fail)
         c = measure(a.pot, method, a.steps + (1 if os.environ.get("COMD_BENCH_SELFTEST_PERTURB") == "1" else 0), a.warmup, handshake=True)
         pkg.lib_host().comdSetHaloHandshake(-1)
@@ -382,7 +415,7 @@ def main():
                                     "dE_pot_eV": c["ep"] - ep, "dE_kin_eV": c["ek"] - ek, "d_atoms": c["n_global"] - n_global}
     # the other force methods on the same workload (one GPU only): not the headline, reported beside it
     variants = []
-    if a.gpus == 1 and not a.no_variants:
+    if a.full and a.gpus == 1 and not a.no_variants:
         for pot, meth in (("lj", "thread_atom"), ("lj", "thread_atom_nl"), ("lj", "cta_cell"), ("lj", "cta_cell_pairlist"), ("eam", "cta_cell"), ("eam", "thread_atom_nl"), ("eam", "thread_atom")):
             if (pot, meth) == (a.pot, method):
                 continue
@@ -399,7 +432,7 @@ def main():
                 entry["roofline"] = roofline_object(pot, meth, a.nx, v["n_global"], v["force_ms"] / a.steps, v["aux_ms"] / a.steps, a.precision)
             variants.append(entry)
     # the single-precision build on the two BASELINE workloads: a child process each (the two builds export the same symbols)
-    if a.gpus == 1 and not a.no_variants and a.precision == "double":
+    if a.full and a.gpus == 1 and not a.no_variants and a.precision == "double":
         import subprocess
         for pot in ("lj", "eam"):
             cmd = [sys.executable, os.path.abspath(__file__), "--precision", "single", "--pot", pot, "--steps", str(a.steps), "--warmup", str(a.warmup),
@@ -414,7 +447,7 @@ def main():
                 variants.append({"workload": f"{pot.upper()} Cu FCC {a.nx}^3, PRECISION=single build", "dtype": "f32", "error": repr(exc)[:200]})
     # BASELINE.json's target line: LJ 256^3 on one GPU (north_star: ">= 50 % of the HBM roofline on LJ force at 256^3")
     target = None
-    if a.gpus == 1 and not a.no_variants and not a.no_target_line and a.precision == "double" and not loopback:
+    if a.full and a.gpus == 1 and not a.no_variants and not a.no_target_line and a.precision == "double" and not loopback:
         free, total = pkg.device_mem_info()
         if free < 60e9:
             target = {"workload": "LJ Cu FCC 256^3, thread_atom", "skipped": f"{free / 1e9:.0f} GB of device memory free, the leg needs ~45 GB (atoms 16 GB, candidate lists 17 GB, packed positions 6 GB) and asks for 60"}
@@ -436,7 +469,7 @@ def main():
             out["variants"] = variants
         if target:
             out["target_line"] = target
-        if a.gpus == 1 and not a.no_cpu_baseline:
+        if a.full and a.gpus == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.pot, a.cpu_seconds)
         print(json.dumps(out))
     if transport is not None:

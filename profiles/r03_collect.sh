@@ -15,7 +15,7 @@ tail -2 $O/gpu_tests.log
 fi
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-T0=$SECONDS; python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "default bench: $((SECONDS - T0)) s wall" | tee $O/bench_default.time
+T0=$SECONDS; python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "default bench: $((SECONDS - T0)) s wall" | tee $O/bench_default.time
 echo "default bench done"
 C=./comd-cuda-async_amd/csrc
 $C/comd-hip -x 20 -y 20 -z 20 -m thread_atom > $O/comd_hip_lj20_stdout.txt 2>&1

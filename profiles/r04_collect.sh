@@ -15,7 +15,7 @@ tail -2 $O/gpu_tests.log
 fi
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-T0=$SECONDS; python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "default bench: $((SECONDS - T0)) s wall" | tee $O/bench_default.time
+T0=$SECONDS; python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "default bench: $((SECONDS - T0)) s wall" | tee $O/bench_default.time
 echo "default bench done"
 C=./comd-cuda-async_amd/csrc
 $C/comd-hip -x 20 -y 20 -z 20 -m thread_atom > $O/comd_hip_lj20_stdout.txt 2>&1
@@ -32,12 +32,12 @@ $C/comd-hip-sp -x 20 -y 20 -z 20 -m thread_atom > $O/comd_hip_sp_lj20_stdout.txt
 $C/comd-hip-sp -e -x 20 -y 20 -z 20 -m cta_cell > $O/comd_hip_sp_eam20_stdout.txt 2>&1
 rm -f CoMD-hip*.yaml
 echo "comd-hip runs done"
-COMD_LOOPBACK_TRANSPORT=1 python bench.py --no-variants --no-cpu-baseline > $O/loopback_lj.json 2>/dev/null
-COMD_LOOPBACK_TRANSPORT=1 COMD_HALO_HANDSHAKE=1 python bench.py --no-target-line --no-variants --no-cpu-baseline > $O/loopback_lj_handshake.json 2>/dev/null
-COMD_LOOPBACK_TRANSPORT=1 python bench.py --pot eam --no-variants --no-cpu-baseline > $O/loopback_eam.json 2>/dev/null
-COMD_LOOPBACK_TRANSPORT=1 COMD_HALO_HANDSHAKE=1 python bench.py --pot eam --no-variants --no-cpu-baseline > $O/loopback_eam_handshake.json 2>/dev/null
-COMD_LOOPBACK_TRANSPORT=1 python bench.py --async-halo 1 --no-variants --no-cpu-baseline --no-target-line > $O/loopback_lj_overlap.json 2>/dev/null
-COMD_LOOPBACK_TRANSPORT=1 python bench.py --pot eam --async-halo 1 --no-variants --no-cpu-baseline > $O/loopback_eam_overlap.json 2>/dev/null
+COMD_LOOPBACK_TRANSPORT=1 python bench.py --full --no-variants --no-cpu-baseline > $O/loopback_lj.json 2>/dev/null
+COMD_LOOPBACK_TRANSPORT=1 COMD_HALO_HANDSHAKE=1 python bench.py --full --no-target-line --no-variants --no-cpu-baseline > $O/loopback_lj_handshake.json 2>/dev/null
+COMD_LOOPBACK_TRANSPORT=1 python bench.py --full --pot eam --no-variants --no-cpu-baseline > $O/loopback_eam.json 2>/dev/null
+COMD_LOOPBACK_TRANSPORT=1 COMD_HALO_HANDSHAKE=1 python bench.py --full --pot eam --no-variants --no-cpu-baseline > $O/loopback_eam_handshake.json 2>/dev/null
+COMD_LOOPBACK_TRANSPORT=1 python bench.py --full --async-halo 1 --no-variants --no-cpu-baseline --no-target-line > $O/loopback_lj_overlap.json 2>/dev/null
+COMD_LOOPBACK_TRANSPORT=1 python bench.py --full --pot eam --async-halo 1 --no-variants --no-cpu-baseline > $O/loopback_eam_overlap.json 2>/dev/null
 python bench.py --no-variants --no-cpu-baseline --no-target-line > $O/plain_lj.json 2>/dev/null
 python bench.py --pot eam --no-variants --no-cpu-baseline > $O/plain_eam.json 2>/dev/null
 COMD_HALO_MIRROR=0 python bench.py --no-variants --no-cpu-baseline --no-target-line > $O/plain_lj_messages.json 2>/dev/null
@@ -48,8 +48,8 @@ COMD_EAM_NL=lds python bench.py --pot eam --method thread_atom_nl --no-variants 
 python bench.py --pot eam --method thread_atom --no-variants --no-cpu-baseline > $O/plain_eam_thread_atom.json 2>/dev/null
 COMD_EAM_THREAD_ATOM=cell python bench.py --pot eam --method thread_atom --no-variants --no-cpu-baseline > $O/plain_eam_thread_atom_round2_kernel.json 2>/dev/null
 COMD_EAM_ATOM_HANDOVER=0 python bench.py --pot eam --method thread_atom --no-variants --no-cpu-baseline > $O/plain_eam_thread_atom_no_handover.json 2>/dev/null
-COMD_LOOPBACK_TRANSPORT=1 python bench.py --pot eam --method thread_atom --async-halo 1 --no-variants --no-cpu-baseline > $O/loopback_eam_thread_atom_overlap.json 2>/dev/null
-COMD_LOOPBACK_TRANSPORT=1 python bench.py --pot eam --method thread_atom_nl --async-halo 1 --no-variants --no-cpu-baseline > $O/loopback_eam_nl_overlap.json 2>/dev/null
+COMD_LOOPBACK_TRANSPORT=1 python bench.py --full --pot eam --method thread_atom --async-halo 1 --no-variants --no-cpu-baseline > $O/loopback_eam_thread_atom_overlap.json 2>/dev/null
+COMD_LOOPBACK_TRANSPORT=1 python bench.py --full --pot eam --method thread_atom_nl --async-halo 1 --no-variants --no-cpu-baseline > $O/loopback_eam_nl_overlap.json 2>/dev/null
 echo "loopback benches done"
 exit 0
 fi

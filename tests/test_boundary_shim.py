@@ -7,6 +7,7 @@
    comm.cc, + the gpu_utility.c entry points) is defined by libcomd_hip.so; the table below records what each one is.
 """
 import ctypes
+import json
 import os
 import shutil
 import subprocess
@@ -92,16 +93,26 @@ def test_reference_call_expressions_compile_and_link(tmp_path):
 REFERENCE = "/root/reference/src-mpi"
 HOT_PATH_FILES = ("ljForce", "timestep", "eam", "haloExchange")                   # the four host files of the hot path
 OTHER_HOST_FILES = ("neighborList", "hashTable", "linkCells", "initAtoms", "mytype")   # reference host code the four call into (its CPU list path); no device-library call in them
+# the device-library symbols those four files leave undefined, as their compile step below records them (symbol names only)
+STORED_DEVICE_CALLS = set(json.load(open(os.path.join(ROOT, "tests", "golden", "reference_host_device_calls.json")))["device_calls"])
+EXPECTED_DEVICE_CALLS = {"ljForceGpu", "eamForce1Gpu", "eamForce3GpuAsync", "advanceVelocityGpu", "advancePositionGpu", "computeEnergy", "updateLinkCellsGpu", "sortAtomsGpu",
+                         "compactCellsGpu", "unloadAtomsBufferToGpu", "loadForceBufferFromGpu", "unloadForceBufferToGpu", "emptyHaloCellsGpu", "pairlistUpdateRequiredGpu"}
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE) or shutil.which("gcc") is None, reason="needs the reference checkout (build container) and gcc")
 def test_reference_host_files_compile_and_link_against_the_shim(tmp_path):
     """COMPILE AND LINK ONLY -- nothing built here is ever run, and it is no oracle.  The reference's ljForce.c, timestep.c, eam.c and haloExchange.c, as
     they lie (symlinked into a scratch directory so that `#include "gpu_types.h"` etc. resolve to five one-line headers that include
     include/comd_hip_shim.h in the place of cuda_runtime.h / nvToolsExt.h / gpu_kernels.h / gpu_utility.h / gpu_types.h), must compile without an error,
     every device-library symbol they leave undefined must be one libcomd_hip.so defines, and together with the reference's own host files they call into
     they must link against libcomd_hip.so + libcomd_host.so with --no-undefined (libcomd_host.so stands in for the reference's parallel.c /
-    performanceTimers.c / decomposition.c, same names and signatures)."""
+    performanceTimers.c / decomposition.c, same names and signatures).
+    Where the reference checkout is absent, the device-library symbols its compile step recorded (tests/golden/reference_host_device_calls.json)
+    must still all be defined by libcomd_hip.so; where it is present, the recording is checked against the live compile."""
+    hip_defined = {l.split()[-1] for l in subprocess.run(["nm", "-D", "--defined-only", os.path.join(CSRC, "libcomd_hip.so")], capture_output=True, text=True).stdout.splitlines() if l.strip()}
+    assert STORED_DEVICE_CALLS <= hip_defined, sorted(STORED_DEVICE_CALLS - hip_defined)
+    assert EXPECTED_DEVICE_CALLS | {"neighborListForceRebuildGpu"} <= STORED_DEVICE_CALLS
+    if not os.path.isdir(REFERENCE) or shutil.which("gcc") is None:
+        return                                                                     # the compile-and-link leg needs the reference checkout and gcc
     src = tmp_path / "src"
     inc = tmp_path / "inc"
     src.mkdir(); inc.mkdir()
@@ -123,14 +134,13 @@ def test_reference_host_files_compile_and_link_against_the_shim(tmp_path):
         cc = subprocess.run(flags + ["-c", str(src / (f + ".c")), "-o", obj], capture_output=True, text=True)
         assert cc.returncode == 0, f"{f}.c: " + cc.stderr[-3000:]
         objs.append(obj)
-    hip_defined = {l.split()[-1] for l in subprocess.run(["nm", "-D", "--defined-only", os.path.join(CSRC, "libcomd_hip.so")], capture_output=True, text=True).stdout.splitlines() if l.strip()}
     wanted = set()
     for obj in objs[:len(HOT_PATH_FILES)]:
         wanted |= {l.split()[-1] for l in subprocess.run(["nm", "-u", obj], capture_output=True, text=True).stdout.splitlines() if l.strip()}
     device_calls = wanted & (set(SURFACE) | {n for n in hip_defined if n.startswith("comd")})
     assert device_calls <= hip_defined, sorted(device_calls - hip_defined)
-    assert {"ljForceGpu", "eamForce1Gpu", "eamForce3GpuAsync", "advanceVelocityGpu", "advancePositionGpu", "computeEnergy", "updateLinkCellsGpu", "sortAtomsGpu",
-            "compactCellsGpu", "unloadAtomsBufferToGpu", "loadForceBufferFromGpu", "unloadForceBufferToGpu", "emptyHaloCellsGpu", "pairlistUpdateRequiredGpu"} <= device_calls
+    assert EXPECTED_DEVICE_CALLS <= device_calls
+    assert device_calls | {"neighborListForceRebuildGpu"} == STORED_DEVICE_CALLS, sorted((device_calls | {"neighborListForceRebuildGpu"}) ^ STORED_DEVICE_CALLS)
     assert "neighborListForceRebuildGpu" in wanted and "neighborListForceRebuildGpu" in hip_defined          # (gpu_neighborList.h:55: host code in the reference, same signature here)
     ld = subprocess.run(["gcc", "-shared", "-o", str(tmp_path / "libreference_host.so")] + objs + ["-L" + CSRC, "-lcomd_host", "-lcomd_hip", "-Wl,--no-undefined", "-Wl,-rpath," + CSRC, "-lm"],
                         capture_output=True, text=True)

@@ -114,7 +114,7 @@ def test_bench_reports_what_rccl_saw_and_maps_one_copy_of_it():
     import json
     env = dict(os.environ, COMD_LOOPBACK_TRANSPORT="1", MASTER_PORT=str(_free_port()))
     proc = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--nx", "20", "--steps", "3", "--warmup", "1",
-                           "--no-variants", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
+                           "--full", "--no-variants", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
     assert proc.returncode == 0, proc.stderr[-2000:]
     line = json.loads(proc.stdout.strip().splitlines()[-1])
     cfg = line["config"]
@@ -135,7 +135,7 @@ def test_bench_self_check_catches_a_run_that_differs(tmp_path):
     import json
     env = dict(os.environ, COMD_LOOPBACK_TRANSPORT="1", MASTER_PORT=str(_free_port()), COMD_BENCH_SELFTEST_PERTURB="1")
     proc = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--nx", "20", "--steps", "3", "--warmup", "1",
-                           "--no-variants", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
+                           "--full", "--no-variants", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
     assert proc.returncode == 4, (proc.returncode, proc.stderr[-2000:])
     line = json.loads(proc.stdout.strip().splitlines()[-1])
     assert line["sized_matches_handshake"] is False
@@ -151,7 +151,7 @@ def test_bench_through_the_launcher_with_several_ranks(pot, ranks):
     import json
     env = dict(os.environ, COMD_FORCE_DEVICE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", str(ranks), "--pot", pot, "--nx", "16", "--steps", "4", "--warmup", "2", "--allow-host-staged"]
+           os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", str(ranks), "--pot", pot, "--nx", "16", "--steps", "4", "--warmup", "2", "--allow-host-staged", "--full"]
     proc = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [l for l in proc.stdout.splitlines() if l.startswith("{")]
