@@ -125,6 +125,8 @@ def lib_host():
         lib.comdHostAtoms.restype = ctypes.POINTER(HostAtoms)
         lib.comdGridInfo.argtypes = [vp, c_int_p]
         lib.comdEamTable.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]
+        lib.comdLjTable.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]
+        lib.comdLjTable.restype = ctypes.c_int
         lib.comdEamTable.restype = ctypes.c_int
         lib.comdNeighborListBuilds.argtypes = [vp]
         lib.comdNeighborListBuilds.restype = ctypes.c_int
@@ -259,6 +261,18 @@ class Simulation:
         n = self.lib.comdEamTable(self.ptr, which, ctypes.byref(x0), ctypes.byref(inv), None)
         v = np.empty(n + 3)
         self.lib.comdEamTable(self.ptr, which, ctypes.byref(x0), ctypes.byref(inv), v.ctypes.data_as(ctypes.c_void_p))
+        return x0.value, inv.value, v
+
+    def lj_table(self):
+        """(x0, invDx, padded samples) of the -I table as the host hands it to AllocateGpu: n + 4 entries (leading pad, n + 1 samples from x0 to
+        the cutoff, one more past it, trailing pad).  None without -I."""
+        import numpy as np
+        x0, inv = ctypes.c_double(), ctypes.c_double()
+        n = self.lib.comdLjTable(self.ptr, ctypes.byref(x0), ctypes.byref(inv), None)
+        if n == 0:
+            return None
+        v = np.empty(n + 4)
+        self.lib.comdLjTable(self.ptr, ctypes.byref(x0), ctypes.byref(inv), v.ctypes.data_as(ctypes.c_void_p))
         return x0.value, inv.value, v
 
     @property

@@ -14,6 +14,7 @@
 #include "comd_hip.h"
 #include "device_common.h"
 #include "lj_kernels.h"
+#include "lj_table_kernels.h"
 #include "eam_kernels.h"
 #include "step_kernels.h"
 #include "nl_kernels.h"
@@ -195,14 +196,49 @@ template <typename T> static T* dalloc(size_t n, bool zero = true)
    return p;
 }
 
-static void uploadTable(InterpolationObjectGpu* t, int n, real_t x0, real_t invDx, const real_t* hostValues)
+// tailPad: entries past the n + 3 of the table (the LJ table has one, see comdLjInterpolationTable)
+static void uploadTable(InterpolationObjectGpu* t, int n, real_t x0, real_t invDx, const real_t* hostValues, int tailPad = 0)
 {
    t->n = n; t->x0 = x0; t->invDx = invDx;
    t->xn = x0 + n / invDx;                     // gpu_utility.c:446, 460-461
    t->invDxHalf = invDx * 0.5;
    t->invDxXx0 = x0 * invDx;
-   t->values = dalloc<real_t>((size_t)n + 3, false);
-   HIP_CHECK(hipMemcpy(t->values, hostValues, ((size_t)n + 3) * sizeof(real_t), hipMemcpyHostToDevice));
+   if (!t->values) t->values = dalloc<real_t>((size_t)n + 3 + tailPad, false);
+   HIP_CHECK(hipMemcpy(t->values, hostValues, ((size_t)n + 3 + tailPad) * sizeof(real_t), hipMemcpyHostToDevice));
+}
+
+// The -I table (gpu_utility.c:349-372), restated with the reference's types and order of operations so that every sample is the reference's to the
+// bit: the expressions with 1.0 are evaluated in double in the single-precision build as well, and nothing is contracted into an fma.
+extern "C" int comdLjInterpolationTable(real_t sigma, real_t epsilon, real_t cutoff, real_t* x0, real_t* invDx, real_t* values)
+{
+#pragma clang fp contract(off)
+   const int n = 1000;
+   const real_t tx0 = 0.5 * sigma;
+   const real_t tinv = n / (cutoff - tx0);
+   if (x0) *x0 = tx0;
+   if (invDx) *invDx = tinv;
+   if (!values) return n;
+   const real_t rCut2 = cutoff * cutoff;
+   const real_t s6 = sigma * sigma * sigma * sigma * sigma * sigma;
+   const real_t rCut6 = s6 / (rCut2 * rCut2 * rCut2);
+   const real_t eShift = rCut6 * (rCut6 - 1.0);
+   for (int i = 0; i < n + 3; ++i) {
+      const real_t x = tx0 + (i - 1) / tinv;
+      const real_t r2 = 1.0 / (x * x);
+      const real_t r6 = s6 * r2 * r2 * r2;
+      values[i] = 4 * epsilon * (r6 * (r6 - 1.0) - eShift);
+   }
+   values[n + 3] = values[n + 2];      // a pair at r == xn reads v[n + 3]: one past the reference's array
+   return n;
+}
+
+extern "C" void initLJinterpolation(LjPotentialGpu* pot)
+{
+   real_t x0, invDx;
+   const int n = comdLjInterpolationTable(pot->sigma, pot->epsilon, pot->cutoff, &x0, &invDx, nullptr);
+   std::vector<real_t> v((size_t)n + 4);
+   comdLjInterpolationTable(pot->sigma, pot->epsilon, pot->cutoff, &x0, &invDx, v.data());
+   uploadTable(&pot->lj_interpolation, n, x0, invDx, v.data(), 1);
 }
 
 extern "C" void initLinkCellsGpu(LinkCellGpu* b, const GpuConfig* cfg)
@@ -249,6 +285,8 @@ extern "C" void AllocateGpu(SimGpu* sim, const GpuConfig* cfg)
    HIP_CHECK(hipMemcpy(sim->species_mass, &cfg->mass, sizeof(real_t), hipMemcpyHostToDevice));
 
    sim->lj_pot.cutoff = cfg->ljCutoff; sim->lj_pot.sigma = cfg->ljSigma; sim->lj_pot.epsilon = cfg->ljEpsilon;
+   if (!cfg->do_eam && cfg->ljTableValues)        // -I (gpu_utility.c:509-510)
+      uploadTable(&sim->lj_pot.lj_interpolation, cfg->ljTableN, cfg->ljTableX0, cfg->ljTableInvDx, cfg->ljTableValues, 1);
    if (cfg->do_eam) {
       sim->eam_pot.cutoff = cfg->eamCutoff;
       uploadTable(&sim->eam_pot.phi, cfg->nPhi, cfg->phiX0, cfg->phiInvDx, cfg->phiValues);
@@ -476,7 +514,8 @@ extern "C" void DestroyGpu(SimGpu* sim)
                     sim->atoms.neighborList.list16, sim->atoms.neighborList.stats, sim->atoms.neighborList.pairlist,
                     sim->boxes.boxIDLookUp, sim->boxes.boxIDLookUpReverse, sim->eam_pot.phiS.coefficients, sim->eam_pot.rhoS.coefficients,
                     sim->eam_pot.pairRows, sim->eam_pot.pairRowCount, sim->eam_pot.cellSel, sim->eam_pot.brickGroup, sim->eam_pot.brickList, sim->eam_pot.brickSel, sim->eam_pot.brickStats, sim->eam_pot.atomRows, sim->eam_pot.atomRowCount, sim->eam_pot.atomBrickSel,
-                    sim->atoms.neighborList.brickRows, sim->atoms.neighborList.brickRowCount, sim->adapterScan, sim->lj_pot.waveCand, sim->lj_pot.waveCandCount, sim->lj_pot.packedR[0], sim->lj_pot.packedR[1], sim->lj_pot.packedF[0], sim->lj_pot.packedF[1] };
+                    sim->atoms.neighborList.brickRows, sim->atoms.neighborList.brickRowCount, sim->adapterScan, sim->lj_pot.waveCand, sim->lj_pot.waveCandCount, sim->lj_pot.packedR[0], sim->lj_pot.packedR[1], sim->lj_pot.packedF[0], sim->lj_pot.packedF[1],
+                    sim->lj_pot.lj_interpolation.values };
    for (void* p : ptrs) if (p) HIP_CHECK(hipFree(p));
    if (sim->statusEvent) (void)hipEventDestroy((hipEvent_t)sim->statusEvent);
    if (sim->pinned) HIP_CHECK(hipHostFree(sim->pinned));
@@ -607,8 +646,11 @@ static void ljBoxMarginsF(const SimGpu* sim, real_t rc2, float* rc2Box, float* g
    *grow = (float)(1.0 + rel);
 }
 
-// thread_atom (the BASELINE-named kernel): candidate lists, then the force kernel
-static void launchLjThreadAtom(SimGpu* sim, const LjArgs& a, int num_cells, int* cells_list, comdStream_t stream)
+// The grid and the candidate lists of a thread_atom force call, shared by the analytic and the table kernel
+struct LjThreadAtomLaunch { int w, wavesPerBlock; unsigned nBlocks; bool prune; LjWaveLists wl; };
+
+// thread_atom (the BASELINE-named kernel): candidate lists (launched here), and the grid the force kernel needs
+static LjThreadAtomLaunch prepareLjThreadAtom(SimGpu* sim, const LjArgs& a, int num_cells, int* cells_list, comdStream_t stream)
 {
    // Measured on MI355X (LJ 80^3): a workgroup of the 3 live waves per cell runs the kernel in 3.94 ms, cap/64 = 4 waves per cell (the
    // tail wave exits at once) in 4.72 ms, single-wave workgroups in 5.64 ms.
@@ -691,8 +733,33 @@ static void launchLjThreadAtom(SimGpu* sim, const LjArgs& a, int num_cells, int*
                          sim->boxes.localMin[0], sim->boxes.localMin[1], sim->boxes.localMin[2]);
       hipLaunchKernelGGL(LJ_WaveCandidates, dim3((unsigned)ceilDiv(num_cells, 4)), dim3(256), 0, S(stream), a, wl, w);
    }
+   LjThreadAtomLaunch L; L.w = w; L.wavesPerBlock = wavesPerBlock; L.nBlocks = nBlocks; L.prune = prune; L.wl = wl;
+   return L;
+}
+
+static TableView ljTableView(const SimGpu* sim)
+{
+   const InterpolationObjectGpu& t = sim->lj_pot.lj_interpolation;
+   TableView tv; tv.v = t.values; tv.x0 = t.x0; tv.xn = t.xn; tv.invDx = t.invDx; tv.invDxHalf = t.invDxHalf; tv.invDxXx0 = t.invDxXx0;
+   return tv;
+}
+
+// table: the -I kernel (lj_table_kernels.h) on the same grid and lists
+static void launchLjThreadAtom(SimGpu* sim, const LjArgs& a, int num_cells, int* cells_list, comdStream_t stream, bool table)
+{
+   const LjThreadAtomLaunch L = prepareLjThreadAtom(sim, a, num_cells, cells_list, stream);
+   const int w = L.w, wavesPerBlock = L.wavesPerBlock;
+   const unsigned nBlocks = L.nBlocks;
+   const bool prune = L.prune;
+   const LjWaveLists& wl = L.wl;
    ForceTimer timer(sim, S(stream));                     // the force kernel proper (bench.py's roofline line; rocprof must agree with it)
-   if (prune) {
+   if (table) {
+      const TableView tv = ljTableView(sim);
+#define LAUNCH_TABLE(E, LISTED) hipLaunchKernelGGL((LJ_Force_thread_atom_table<E, LISTED>), dim3(nBlocks), dim3(64 * wavesPerBlock), 0, S(stream), a, w, wl, tv)
+      if (prune) { if (sim->needEnergy) LAUNCH_TABLE(true, true);  else LAUNCH_TABLE(false, true); }
+      else       { if (sim->needEnergy) LAUNCH_TABLE(true, false); else LAUNCH_TABLE(false, false); }
+#undef LAUNCH_TABLE
+   } else if (prune) {
       if (sim->needEnergy) hipLaunchKernelGGL((LJ_Force_thread_atom<true, true>), dim3(nBlocks), dim3(64 * wavesPerBlock), 0, S(stream), a, w, wl);
       else              hipLaunchKernelGGL((LJ_Force_thread_atom<false, true>), dim3(nBlocks), dim3(64 * wavesPerBlock), 0, S(stream), a, w, wl);
    } else {
@@ -702,11 +769,16 @@ static void launchLjThreadAtom(SimGpu* sim, const LjArgs& a, int num_cells, int*
    LAUNCH_CHECK();
 }
 
-extern "C" void ljForceGpuAsync(SimGpu* sim, int num_cells, int* cells_list, int method, comdStream_t stream)
+// table: -I (lj_pot.lj_interpolation), thread_atom and both list formats of thread_atom_nl
+static void ljForce(SimGpu* sim, int num_cells, int* cells_list, int method, comdStream_t stream, bool table)
 {
    if (num_cells <= 0) return;
    LjArgs a = makeLjArgs(sim, num_cells, cells_list);
-   if (method != THREAD_ATOM_NL && method != WARP_ATOM_NL && method != CTA_CELL) { launchLjThreadAtom(sim, a, num_cells, cells_list, stream); return; }
+   if (table) {
+      if (!sim->lj_pot.lj_interpolation.values) { fprintf(stderr, "ljForceGpu: interpolation requested but there is no LJ table: call initLJinterpolation first\n"); exit(-1); }
+      if (method == CTA_CELL) { fprintf(stderr, "ljForceGpu: interpolated LJ (-I) runs with thread_atom and thread_atom_nl, not cta_cell\n"); exit(-1); }
+   }
+   if (method != THREAD_ATOM_NL && method != WARP_ATOM_NL && method != CTA_CELL) { launchLjThreadAtom(sim, a, num_cells, cells_list, stream, table); return; }
    ForceTimer timer(sim, S(stream));
    if ((method == THREAD_ATOM_NL || method == WARP_ATOM_NL) && sim->atoms.neighborList.slabFormat) {
       NeighborListGpu* n = &sim->atoms.neighborList;
@@ -714,6 +786,15 @@ extern "C" void ljForceGpuAsync(SimGpu* sim, int num_cells, int* cells_list, int
       NlSlabView v; v.list = n->list16; v.count = n->nNeighbors; v.rows = n->slabRows;
       const int threads = ((n->maxCellAtoms + 63) / 64) * 64;
       const size_t lds = (size_t)3 * n->maxSlabAtoms * sizeof(real_t);
+      if (table) {
+         const TableView tv = ljTableView(sim);
+         allowDynamicLds((const void*)LJ_Force_nl_slabs_table<true>, lds);
+         allowDynamicLds((const void*)LJ_Force_nl_slabs_table<false>, lds);
+         if (sim->needEnergy) hipLaunchKernelGGL(LJ_Force_nl_slabs_table<true>, dim3(num_cells), dim3(threads), lds, S(stream), a, v, n->maxSlabAtoms, tv);
+         else              hipLaunchKernelGGL(LJ_Force_nl_slabs_table<false>, dim3(num_cells), dim3(threads), lds, S(stream), a, v, n->maxSlabAtoms, tv);
+         LAUNCH_CHECK();
+         return;
+      }
       allowDynamicLds((const void*)LJ_Force_nl_slabs<true>, lds);
       allowDynamicLds((const void*)LJ_Force_nl_slabs<false>, lds);
       if (sim->needEnergy) hipLaunchKernelGGL(LJ_Force_nl_slabs<true>, dim3(num_cells), dim3(threads), lds, S(stream), a, v, n->maxSlabAtoms);
@@ -721,7 +802,12 @@ extern "C" void ljForceGpuAsync(SimGpu* sim, int num_cells, int* cells_list, int
    } else if (method == THREAD_ATOM_NL || method == WARP_ATOM_NL) {
       const NlView nl = nlView(sim);
       const unsigned nBlocks = (unsigned)ceilDiv((long)num_cells * sim->maxAtoms, 256);
-      if (sim->needEnergy) hipLaunchKernelGGL(LJ_Force_thread_atom_nl<true>, dim3(nBlocks), dim3(256), 0, S(stream), a, nl);
+      if (table) {
+         const TableView tv = ljTableView(sim);
+         if (sim->needEnergy) hipLaunchKernelGGL(LJ_Force_thread_atom_nl_table<true>, dim3(nBlocks), dim3(256), 0, S(stream), a, nl, tv);
+         else              hipLaunchKernelGGL(LJ_Force_thread_atom_nl_table<false>, dim3(nBlocks), dim3(256), 0, S(stream), a, nl, tv);
+      }
+      else if (sim->needEnergy) hipLaunchKernelGGL(LJ_Force_thread_atom_nl<true>, dim3(nBlocks), dim3(256), 0, S(stream), a, nl);
       else              hipLaunchKernelGGL(LJ_Force_thread_atom_nl<false>, dim3(nBlocks), dim3(256), 0, S(stream), a, nl);
    } else if (method == CTA_CELL) {
       const size_t lds = ljCtaLdsBytes(sim->maxAtoms);
@@ -756,11 +842,15 @@ extern "C" void ljForceGpuAsync(SimGpu* sim, int num_cells, int* cells_list, int
    LAUNCH_CHECK();
 }
 
+extern "C" void ljForceGpuAsync(SimGpu* sim, int num_cells, int* cells_list, int method, comdStream_t stream)
+{
+   ljForce(sim, num_cells, cells_list, method, stream, sim->lj_pot.lj_interpolation.values != nullptr);
+}
+
 extern "C" void ljForceGpu(SimGpu* sim, int interpolation, int num_cells, int* cells_list, real_t plcutoff, int method)
 {
    (void)plcutoff;
-   if (interpolation != 0) { fprintf(stderr, "ljForceGpu: table-interpolated LJ (-I) is out of scope\n"); exit(-1); }
-   ljForceGpuAsync(sim, num_cells, cells_list, method, nullptr);
+   ljForce(sim, num_cells, cells_list, method, nullptr, interpolation != 0);
 }
 
 static EamArgs makeEamArgs(SimGpu* sim, int num_cells, int* cells_list)

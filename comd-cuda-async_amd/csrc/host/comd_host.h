@@ -269,6 +269,9 @@ typedef struct SimFlatSt {
    int *boundary_cells_h, *interior_cells_h, *boundary1_cells_h;
    int gpuAsync, gpuProfile;
    int ljInterpolation, spline, usePairlist;
+   real_t* ljTable;                 /* -I: the table of comdLjInterpolationTable (ljTableN + 4 entries), NULL otherwise */
+   int ljTableN;
+   real_t ljTableX0, ljTableInvDx;
    real_t skinDistance;
    int useNL;                       /* method is thread_atom_nl / warp_atom_nl */
    int interiorLaunched;            /* -a 1: redistributeAtoms has already started the interior cells' force work */
@@ -328,6 +331,7 @@ void     comdHaloExchangeHost(SimFlat* s, int (*load)(void*, void*, int, char*),
 void     comdFaceShift(SimFlat* s, int face, double out[3]);
 int      comdPutAtomInBox(SimFlat* s, int gid, int type, const double r[3], const double p[3]);
 int      comdEamTable(SimFlat* s, int which, double* x0, double* invDx, double* values);   /* 0 phi, 1 rho, 2 F; n + 3 padded samples */
+int      comdLjTable(SimFlat* s, double* x0, double* invDx, double* values);              /* -I: n + 4 padded samples; 0 without -I */
 int      comdNeighborListBuilds(SimFlat* s);              /* Verlet-list builds so far (*_nl methods) */
 void     comdGridInfo(SimFlat* s, int out[6]);            /* gridSize[3], nLocalBoxes, nTotalBoxes, maxAtoms */
 int      comdMain(int argc, char** argv);                /* the reference's main(): CoMD.c:86-187 */

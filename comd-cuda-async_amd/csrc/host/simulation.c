@@ -117,9 +117,11 @@ SimFlat* initSimulationHost(Command cmd)
    }
    else { printf("Error: You have to specify a valid method: -m [thread_atom,thread_atom_nl,cta_cell]\n"); exit(-1); }
    sim->useNL = sim->method == THREAD_ATOM_NL;
-   if (cmd.ljInterpolation) {
-      printf("Error: -I is outside this build's scope (SURVEY.md section 8f).\n"); exit(-1);
-   }
+   /* -I (CoMD.c, gpu_kernels.cu:76-84): LJ by table interpolation, for the thread-per-atom methods.  The reference runs the analytic cta_cell kernel
+    * with -I; this build refuses what it would not compute */
+   sim->ljInterpolation = cmd.ljInterpolation;
+   if (sim->ljInterpolation && cmd.doeam) { printf("Error: -I applies to LJ, not to EAM (-e).\n"); exit(-1); }
+   if (sim->ljInterpolation && sim->method == CTA_CELL) { printf("Error: -I applies to -m thread_atom, warp_atom and thread_atom_nl, not to cta_cell.\n"); exit(-1); }
    /* -P (CoMD.c:271, gpu_utility.c:474-500): cubic-spline tables in r^2 for phi and rho, for every force method (gpu_kernels.cu:164-226) */
    sim->spline = cmd.spline;
    if (sim->spline && !cmd.doeam) { printf("Error: -P applies to EAM (-e).\n"); exit(-1); }
@@ -130,6 +132,13 @@ SimFlat* initSimulationHost(Command cmd)
 
    sim->pot = initPotential(cmd.doeam, cmd.potDir, cmd.potName, cmd.potType);
    if (!cmd.doeam && cmd.ljCutoffSigmas > 0.0) sim->pot->cutoff = cmd.ljCutoffSigmas * ((LjPotential*)sim->pot)->sigma;
+   if (sim->ljInterpolation) {          /* gpu_utility.c:509-510: the table of the potential as set up, cutoff included */
+      LjPotential* lj = (LjPotential*)sim->pot;
+      sim->ljTableN = comdLjInterpolationTable(lj->sigma, lj->epsilon, lj->cutoff, &sim->ljTableX0, &sim->ljTableInvDx, NULL);
+      sim->ljTable = (real_t*)malloc(((size_t)sim->ljTableN + 4) * sizeof(real_t));
+      comdLjInterpolationTable(lj->sigma, lj->epsilon, lj->cutoff, &sim->ljTableX0, &sim->ljTableInvDx, sim->ljTable);
+      if (printRank() && !cmd.quiet) printf("LJ by table interpolation (-I): %d intervals from %f to %f Angstroms\n", sim->ljTableN, sim->ljTableX0, lj->cutoff);
+   }
    if (sim->spline) eamUseSplines(sim->pot);
    real_t latticeConstant = cmd.lat;
    if (cmd.lat < 0.0) latticeConstant = sim->pot->lat;
@@ -182,6 +191,7 @@ SimFlat* initSimulation(Command cmd)
    } else {
       LjPotential* lj = (LjPotential*)sim->pot;
       cfg.ljCutoff = lj->cutoff; cfg.ljSigma = lj->sigma; cfg.ljEpsilon = lj->epsilon;
+      cfg.ljTableN = sim->ljTableN; cfg.ljTableX0 = sim->ljTableX0; cfg.ljTableInvDx = sim->ljTableInvDx; cfg.ljTableValues = sim->ljTable;
    }
    int* nbrTable = (int*)malloc((size_t)sim->boxes->nLocalBoxes * 27 * sizeof(int));
    for (int iBox = 0; iBox < sim->boxes->nLocalBoxes; ++iBox) {       /* self first (gpu_utility.c:520-531) */
@@ -231,6 +241,7 @@ void destroySimulation(SimFlat** ps)
    destroyLinkCells(&s->boxes);
    destroyAtoms(s->atoms);
    free(s->boundary_cells_h); free(s->interior_cells_h); free(s->boundary1_cells_h);
+   free(s->ljTable);
    free(s->species); free(s->domain); free(s);
    *ps = NULL;
 }
@@ -415,6 +426,15 @@ int comdEamTable(SimFlat* s, int which, double* x0, double* invDx, double* value
    *x0 = t->x0; *invDx = t->invDx;
    if (values) for (int i = -1; i <= t->n + 1; ++i) values[i + 1] = t->values[i];
    return t->n;
+}
+
+/* the -I table as the device receives it: n, x0, invDx and the n + 4 samples (values[0] = leading pad, values[n + 3] = trailing pad); 0 without -I */
+int comdLjTable(SimFlat* s, double* x0, double* invDx, double* values)
+{
+   if (!s->ljTable) return 0;
+   *x0 = s->ljTableX0; *invDx = s->ljTableInvDx;
+   if (values) for (int i = 0; i < s->ljTableN + 4; ++i) values[i] = s->ljTable[i];
+   return s->ljTableN;
 }
 
 void comdGridInfo(SimFlat* s, int out[6])

@@ -65,6 +65,10 @@ typedef struct LjPotentialGpuSt {
                                         * force call; [1] is used by calls on a stream other than interior_stream when the force is split (-a 1) */
    float*    packedF[2];               /* device [nTotalBoxes * packedCap][4]: the same positions in single precision, relative to the corner of the local domain:
                                         * what the list build tests against its boxes (16 bytes per stencil atom instead of 24, fp32 arithmetic) */
+   /* -I (gpu_types.h:77): the shifted LJ energy tabulated for interpolate(), filled by AllocateGpu from GpuConfig.ljTable* or by initLJinterpolation.
+    * values != NULL is what makes ljForceGpuAsync run the table kernels (thread_atom, warp_atom, thread_atom_nl); NULL: the analytic ones.
+    * values has n + 4 entries: the reference's n + 3 and one trailing pad, read by a pair at r == xn (the cutoff) */
+   InterpolationObjectGpu lj_interpolation;
 } LjPotentialGpu;
 
 /* gpu_types.h:60-69: cubic spline in r^2 (-P, `spline` argument of eamForce*Gpu): coefficients {a,b,c,d} per table interval,
@@ -250,6 +254,10 @@ typedef struct GpuConfig {
    int    usePairlist;                            /* with skinDistance > 0: pairlist bits for LJ cta_cell instead of lists (CoMD.c:250-268) */
    int    maxNeighbors;                           /* list rows per atom; 0 = derive from cutoff + skin and the FCC density */
    real_t latticeConstant;                        /* for that estimate */
+   /* -I: the LJ table of comdLjInterpolationTable (host, ljTableN + 4 entries), or ljTableValues = NULL for the analytic potential */
+   int    ljTableN;
+   real_t ljTableX0, ljTableInvDx;
+   const real_t* ljTableValues;
 } GpuConfig;
 
 /* Host-side mirror of the slot arrays (CoMDTypes.h Atoms / gpu_utility.c:432-600 staging). */
@@ -312,12 +320,22 @@ void comdPollStatus(SimGpu* sim, comdStream_t stream, const char* where);
 
 /* ---- force: gpu_kernels.h:13-24 ------------------------------------------------------------ */
 /* ljForceGpu(SimGpu*, interpolation, num_cells, cells_list, plcutoff, method), gpu_kernels.cu:69-122.
- * cells_list (device) == NULL means cells 0..num_cells-1.  interpolation/plcutoff are accepted for
- * signature parity: interpolation must be 0 (table-LJ is out of scope; non-zero exits); plcutoff (cutoff + skin) is what the pairlist
- * bits are generated with when the lists were allocated with GpuConfig.usePairlist and method is CTA_CELL.
- * method THREAD_ATOM_NL / WARP_ATOM_NL walks the Verlet lists (buildNeighborListGpu must have run). */
+ * cells_list (device) == NULL means cells 0..num_cells-1.  interpolation != 0 (-I) evaluates the pairs by interpolation in
+ * lj_pot.lj_interpolation (gpu_lj_thread_atom.h:145-226) with THREAD_ATOM / WARP_ATOM and THREAD_ATOM_NL / WARP_ATOM_NL (either list
+ * format); it exits when no table was made (initLJinterpolation or GpuConfig.ljTableValues) and with CTA_CELL, where the reference
+ * silently runs the analytic kernel.  interpolation == 0 is the analytic potential whether or not a table exists.  plcutoff
+ * (cutoff + skin) is accepted for signature parity: the pairlist bits are generated with the cutoff + skin of the allocation.
+ * method THREAD_ATOM_NL / WARP_ATOM_NL walks the Verlet lists (buildNeighborListGpu must have run).
+ * ljForceGpuAsync (the reference's signature, no interpolation argument) takes the table path whenever lj_pot.lj_interpolation.values is set. */
 void ljForceGpu(SimGpu* sim, int interpolation, int num_cells, int* cells_list, real_t plcutoff, int method);
 void ljForceGpuAsync(SimGpu* sim, int num_cells, int* cells_list, int method, comdStream_t stream);
+/* initLJinterpolation(LjPotentialGpu*), gpu_utility.c:349-372: make the -I table from pot->sigma, epsilon, cutoff (comdLjInterpolationTable)
+ * and upload it to pot->lj_interpolation (allocated here when values is NULL; DestroyGpu frees it) */
+void initLJinterpolation(LjPotentialGpu* pot);
+/* The -I table on the host, the one place it is made (gpu_utility.c:349-372 restated): n = 1000 intervals from x0 = sigma/2 to the cutoff,
+ * invDx = n / (cutoff - x0), values[i] = 4 eps (r6 (r6 - 1) - eShift) at x0 + (i - 1) / invDx for i = 0 .. n + 2, and values[n + 3] = values[n + 2]
+ * (the trailing pad).  values (n + 4 entries) may be NULL to ask for n.  Returns n.  Needs no device. */
+int  comdLjInterpolationTable(real_t sigma, real_t epsilon, real_t cutoff, real_t* x0, real_t* invDx, real_t* values);
 /* The per-atom energy array e[] is read only by computeEnergy.  comdSetEnergyNeeded(0) tells the force wrappers that the
  * next evaluations feed no energy read, so they may skip the energy arithmetic; comdSetEnergyNeeded(1) (the default)
  * restores the reference behaviour of computing e[] on every call.  timestep() brackets all but its last step with it. */
