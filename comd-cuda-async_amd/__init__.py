@@ -128,6 +128,7 @@ def lib_host():
         lib.comdLjTable.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]
         lib.comdLjTable.restype = ctypes.c_int
         lib.comdEamTable.restype = ctypes.c_int
+        lib.comdVirial.argtypes = [vp, c_double_p]
         lib.comdNeighborListBuilds.argtypes = [vp]
         lib.comdNeighborListBuilds.restype = ctypes.c_int
         lib.comdSimBoxFromTuple.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -322,6 +323,28 @@ class Simulation:
         out = (ctypes.c_double * 3)()
         self.lib.comdGetEnergy(self.ptr, out)
         return out[0], out[1], int(out[2])
+
+    def virial(self):
+        """(W, K): the global pair virial sum_{i<j} r_ij f_ij^T and kinetic tensor sum_i p_i p_i^T / m_i of the current state, 3x3 float64 in eV.
+        Computed on the device from the current positions, momenta and (EAM) F'(rhobar) by computeVirial; the reference has no counterpart."""
+        np = self._np
+        out = (ctypes.c_double * 13)()
+        self.lib.comdVirial(self.ptr, out)
+        self._volume = out[12]
+
+        def sym(c):
+            xx, yy, zz, yz, xz, xy = c
+            return np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]], dtype=np.float64)
+        return sym(out[0:6]), sym(out[6:12])
+
+    def pressure_tensor(self):
+        """(K + W) / V in eV/A^3, V the volume of the global domain (positive: compressive).  1 eV/A^3 = 160.21766208 GPa."""
+        w, k = self.virial()
+        return (k + w) / self._volume
+
+    def pressure(self):
+        """trace(pressure_tensor()) / 3 in eV/A^3."""
+        return float(self._np.trace(self.pressure_tensor())) / 3.0
 
     @property
     def n_global(self):

@@ -20,6 +20,7 @@
 #include "nl_kernels.h"
 #include "eam_brick_kernels.h"
 #include "eam_atom_brick_kernels.h"
+#include "virial_kernels.h"
 
 static int g_rank = 0;
 
@@ -515,7 +516,7 @@ extern "C" void DestroyGpu(SimGpu* sim)
                     sim->boxes.boxIDLookUp, sim->boxes.boxIDLookUpReverse, sim->eam_pot.phiS.coefficients, sim->eam_pot.rhoS.coefficients,
                     sim->eam_pot.pairRows, sim->eam_pot.pairRowCount, sim->eam_pot.cellSel, sim->eam_pot.brickGroup, sim->eam_pot.brickList, sim->eam_pot.brickSel, sim->eam_pot.brickStats, sim->eam_pot.atomRows, sim->eam_pot.atomRowCount, sim->eam_pot.atomBrickSel,
                     sim->atoms.neighborList.brickRows, sim->atoms.neighborList.brickRowCount, sim->adapterScan, sim->lj_pot.waveCand, sim->lj_pot.waveCandCount, sim->lj_pot.packedR[0], sim->lj_pot.packedR[1], sim->lj_pot.packedF[0], sim->lj_pot.packedF[1],
-                    sim->lj_pot.lj_interpolation.values };
+                    sim->lj_pot.lj_interpolation.values, sim->virialBuf };
    for (void* p : ptrs) if (p) HIP_CHECK(hipFree(p));
    if (sim->statusEvent) (void)hipEventDestroy((hipEvent_t)sim->statusEvent);
    if (sim->pinned) HIP_CHECK(hipHostFree(sim->pinned));
@@ -1568,6 +1569,50 @@ extern "C" void computeEnergy(SimGpu* sim, real_t* eLocal)
    HIP_CHECK(hipMemcpyAsync(sim->pinned, out, 2 * sizeof(real_t), hipMemcpyDeviceToHost, st));
    HIP_CHECK(hipStreamSynchronize(st));
    eLocal[0] = sim->pinned[0]; eLocal[1] = sim->pinned[1];
+}
+
+// Not in the reference: the pair virial and the kinetic tensor (virial_kernels.h), one kernel instance per pair function of the force paths
+extern "C" void computeVirial(SimGpu* sim, real_t* out12)
+{
+   hipStream_t st = S(sim->boundary_stream);
+   if (sim->interior_stream) HIP_CHECK(hipStreamSynchronize(S(sim->interior_stream)));      // -a 1: the interior cells' force work is done
+   if (!sim->virialBuf) sim->virialBuf = dalloc<double>((size_t)(VIRIAL_BLOCKS + 1) * VIRIAL_N, false);
+   VirialArgs v;
+   v.rx = sim->atoms.r.x; v.ry = sim->atoms.r.y; v.rz = sim->atoms.r.z;
+   v.px = sim->atoms.p.x; v.py = sim->atoms.p.y; v.pz = sim->atoms.p.z;
+   v.iSpecies = sim->atoms.iSpecies; v.speciesMass = sim->species_mass;
+   v.nAtoms = sim->boxes.nAtoms; v.nbr = sim->neighbor_cells;
+   v.nLocalBoxes = sim->boxes.nLocalBoxes; v.cap = sim->maxAtoms; v.chunks = ceilDiv(sim->maxAtoms, WAVE);
+   v.partial = sim->virialBuf;
+   double* out = sim->virialBuf + (size_t)VIRIAL_BLOCKS * VIRIAL_N;
+   const dim3 grid(VIRIAL_BLOCKS), block(256);
+   if (!sim->do_eam) {
+      const LjArgs a = makeLjArgs(sim, sim->boxes.nLocalBoxes, nullptr);
+      v.rc2 = a.rc2;
+      if (sim->lj_pot.lj_interpolation.values) {
+         VirialLjTable p; p.t = ljTableView(sim);
+         hipLaunchKernelGGL(Virial_thread_atom<VirialLjTable>, grid, block, 0, st, v, p);
+      } else {
+         VirialLj p; p.a = a;
+         hipLaunchKernelGGL(Virial_thread_atom<VirialLj>, grid, block, 0, st, v, p);
+      }
+   } else {
+      const EamPotentialGpu& e = sim->eam_pot;
+      v.rc2 = e.cutoff * e.cutoff;
+      if (e.phiS.coefficients && e.rhoS.coefficients) {
+         VirialEam<true> p; p.phi = e.phi; p.rho = e.rho; p.phiS = e.phiS; p.rhoS = e.rhoS; p.dfEmbed = e.dfEmbed; p.dfi = R(0.0);
+         hipLaunchKernelGGL(Virial_thread_atom<VirialEam<true>>, grid, block, 0, st, v, p);
+      } else {
+         VirialEam<false> p; p.phi = e.phi; p.rho = e.rho; p.phiS = e.phiS; p.rhoS = e.rhoS; p.dfEmbed = e.dfEmbed; p.dfi = R(0.0);
+         hipLaunchKernelGGL(Virial_thread_atom<VirialEam<false>>, grid, block, 0, st, v, p);
+      }
+   }
+   hipLaunchKernelGGL(Virial_Final, dim3(1), dim3(256), 0, st, sim->virialBuf, VIRIAL_BLOCKS, out);
+   LAUNCH_CHECK();
+   double h[VIRIAL_N];
+   HIP_CHECK(hipMemcpyAsync(h, out, sizeof h, hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+   for (int c = 0; c < VIRIAL_N; ++c) out12[c] = (real_t)h[c];
 }
 
 // ---- redistribute ---------------------------------------------------------------------------------------------------

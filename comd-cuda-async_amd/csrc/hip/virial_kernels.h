@@ -1,0 +1,209 @@
+// virial_kernels.h -- the pair virial and the kinetic tensor for gfx950 (computeVirial, comd_hip.h).  The reference has no counterpart.
+//
+//   W_ab = sum_{i<j} r_ij,a f_ij,b     (r_ij = r_i - r_j to the image j interacts with, f_ij the force on i due to j)
+//   K_ab = sum_i p_i,a p_i,b / m_i
+// Components in the order xx yy zz yz xz xy.  Every instance evaluates the pair through the device helper of the force kernels of its
+// mode -- ljPair, ljTablePair, interpolate<CLAMP> of phi and rho, interpolateSpline -- so the virial is the one of the forces that move the atoms:
+//   LJ:  f_ij = ljPair's f_pair (x 24 eps s6 once per lane) or ljTablePair's -v'(r)/r d
+//   EAM: f_ij = -(phi'(r) + (F'_i + F'_j) rho'(r)) / r d, F'_j read from dfEmbed, whose halo slots the force exchange has filled.
+//
+// Mapping: the shape of LJ_Force_thread_atom.  One wave = one 64-slot chunk of a local cell (a cell of more than 64 slots takes several
+// chunks), lane = i atom, the 27-cell stencil walked with the neighbour j wave-uniform (its position and F'_j through the scalar unit).
+// A chunk of at most 32 atoms -- every EAM cell, the tail chunk of an LJ cell -- is replicated across the lanes, each copy walking a share
+// of the stencil cells, as the tail wave of LJ_Force_thread_atom is.
+// Only local atoms are i, j runs over local and halo slots, so every pair is seen from both sides and weighs 1/2.
+// The link cells of the *_nl methods and of -L are sized for cutoff + skin and are not re-binned between list builds: an atom has moved
+// less than skin/2 since, so two atoms within the plain cutoff now were within cutoff + skin of each other when the cells were filled, i.e.
+// in neighbouring cells.  The 27-cell walk with the plain cutoff therefore finds every pair the lists hold.
+//
+// Reduction: each lane accumulates its 6 + 6 components in real_t, the workgroup sums them in double in a fixed order and writes one row of 12
+// partials; Virial_Final adds the rows in a fixed order (no atomics: runs are bit-reproducible).  The kernels read r, p, dfEmbed and the cell
+// tables and write nothing but their partial rows.
+#pragma once
+#include "device_common.h"
+#include "lj_kernels.h"
+#include "lj_table_kernels.h"
+#include "eam_kernels.h"
+
+#define VIRIAL_N 12                    // 6 virial + 6 kinetic components
+#define VIRIAL_BLOCKS 2048             // rows of partials: fixed, so the order of the sums does not depend on the system
+
+struct VirialArgs {
+   const real_t* __restrict__ rx; const real_t* __restrict__ ry; const real_t* __restrict__ rz;
+   const real_t* __restrict__ px; const real_t* __restrict__ py; const real_t* __restrict__ pz;
+   const int* __restrict__ iSpecies; const real_t* __restrict__ speciesMass;
+   const int* __restrict__ nAtoms;
+   const int* __restrict__ nbr;        // [nLocal*27], self first
+   int nLocalBoxes, cap, chunks;       // chunks = 64-slot chunks per cell
+   real_t rc2;
+   double* __restrict__ partial;       // [gridDim.x][VIRIAL_N]
+};
+
+// The pair functors: begin(iOff) once per i atom, then operator() per accepted pair returns f_ij / scale in (gx, gy, gz).
+struct VirialLj {
+   LjArgs a;
+   __host__ __device__ real_t scale() const { return LJ_FORCE_SCALE(a); }
+   __device__ void begin(size_t) {}
+   __device__ void operator()(real_t dx, real_t dy, real_t dz, real_t r2, size_t, real_t& gx, real_t& gy, real_t& gz) const
+   {
+      real_t e = R(0.0);
+      ljPair<false>(dx, dy, dz, r2, a, gx, gy, gz, e);
+   }
+};
+
+struct VirialLjTable {
+   TableView t;
+   __host__ __device__ real_t scale() const { return R(1.0); }
+   __device__ void begin(size_t) {}
+   __device__ void operator()(real_t dx, real_t dy, real_t dz, real_t r2, size_t, real_t& gx, real_t& gy, real_t& gz) const
+   {
+      real_t e = R(0.0);
+      ljTablePair<false>(dx, dy, dz, r2, t, gx, gy, gz, e);
+   }
+};
+
+// SPLINE: the -P cubic splines in r^2 (drho, dphi are (1/r) d/dr already); else the quadratic tables in r
+template <bool SPLINE>
+struct VirialEam {
+   InterpolationObjectGpu phi, rho;
+   InterpolationSplineObjectGpu phiS, rhoS;
+   const real_t* __restrict__ dfEmbed;
+   real_t dfi;
+   __host__ __device__ real_t scale() const { return R(1.0); }
+   __device__ void begin(size_t iOff) { dfi = dfEmbed[iOff]; }
+   __device__ void operator()(real_t dx, real_t dy, real_t dz, real_t r2, size_t jOff, real_t& gx, real_t& gy, real_t& gz) const
+   {
+      real_t v, dphi, drho;
+      real_t s;
+      if (SPLINE) {
+         interpolateSpline(phiS, r2, v, dphi);
+         interpolateSpline(rhoS, r2, v, drho);
+         s = dphi + (dfi + dfEmbed[jOff]) * drho;
+      } else {
+         const real_t ir = rsqrtR(r2), r = r2 * ir;
+         interpolate(makeTable(phi, phi.values), r, v, dphi);
+         interpolate(makeTable(rho, rho.values), r, v, drho);
+         s = (dphi + (dfi + dfEmbed[jOff]) * drho) * ir;
+      }
+      gx = -s * dx; gy = -s * dy; gz = -s * dz;
+   }
+};
+
+// sum over the 64 lanes in double, in a fixed order
+__device__ __forceinline__ double waveSumD(double v)
+{
+#pragma unroll
+   for (int m = 32; m >= 1; m >>= 1) v += bpermuteR(v, laneId() ^ m);
+   return v;
+}
+
+template <class PAIR>
+__global__ __launch_bounds__(256)
+void Virial_thread_atom(VirialArgs v, PAIR pair)
+{
+   __shared__ double sAcc[4][VIRIAL_N];
+   const int lane = laneId(), wave = (int)threadIdx.x >> 6;
+   real_t acc[VIRIAL_N];
+#pragma unroll
+   for (int c = 0; c < VIRIAL_N; ++c) acc[c] = R(0.0);
+
+   // each workgroup takes a contiguous run of chunks (neighbouring cells share stencil cells), dealt XCD-contiguously; its waves interleave
+   const long nWork = (long)v.nLocalBoxes * v.chunks;
+   const long per = (nWork + gridDim.x - 1) / gridDim.x;
+   const long w0 = (long)xcdRemap(blockIdx.x, gridDim.x) * per;
+   const long w1 = w0 + per < nWork ? w0 + per : nWork;
+   for (long w = w0 + wave; w < w1; w += 4) {
+      const int iBox = uniform((int)(w / v.chunks));
+      const int first = uniform((int)(w - (long)iBox * v.chunks)) * WAVE;
+      const int ni = uniform(v.nAtoms[iBox]);
+      if (first >= ni) continue;
+      // a chunk of m <= 32 atoms (EAM cells, the tail chunk of an LJ cell) is replicated: reps copies of its atoms, copy q walks the stencil
+      // cells q, q + reps, ... (the neighbour then differs between copies: vector loads instead of the scalar stream of a full chunk)
+      const int m = ni - first < WAVE ? ni - first : WAVE;
+      int reps = 1;
+      while (reps < 16 && 2 * reps * m <= WAVE) reps *= 2;
+      const int span = WAVE / reps, q = lane / span;
+      const int ia = first + (lane & (span - 1));
+      const bool active = ia < first + m;
+      const size_t iOff = (size_t)iBox * v.cap + (active ? ia : first);
+      const real_t xi = v.rx[iOff], yi = v.ry[iOff], zi = v.rz[iOff];
+      pair.begin(iOff);
+      real_t wxx = R(0.0), wyy = R(0.0), wzz = R(0.0), wyz = R(0.0), wxz = R(0.0), wxy = R(0.0);
+      auto test = [&](real_t xj, real_t yj, real_t zj, size_t jOff) {
+         const real_t dx = xi - xj, dy = yi - yj, dz = zi - zj;
+         const real_t r2 = dx*dx + dy*dy + dz*dz;
+         if (active && r2 <= v.rc2 && r2 > R(0.0)) {
+            real_t gx = R(0.0), gy = R(0.0), gz = R(0.0);
+            pair(dx, dy, dz, r2, jOff, gx, gy, gz);
+            wxx = fmaR(dx, gx, wxx); wyy = fmaR(dy, gy, wyy); wzz = fmaR(dz, gz, wzz);
+            wyz = fmaR(dy, gz, wyz); wxz = fmaR(dx, gz, wxz); wxy = fmaR(dx, gy, wxy);
+         }
+      };
+      const int* __restrict__ nb = v.nbr + (size_t)iBox * 27;
+      if (reps > 1) {
+         for (int k = q; k < 27; k += reps) {
+            const int jBox = nb[k];
+            const int nj = v.nAtoms[jBox];
+            const size_t base = (size_t)jBox * v.cap;
+            for (int j = 0; j < nj; ++j) test(v.rx[base + j], v.ry[base + j], v.rz[base + j], base + j);
+         }
+      } else for (int k = 0; k < 27; ++k) {
+         const int jBox = uniform(nb[k]);
+         const int nj = uniform(v.nAtoms[jBox]);
+         const size_t base = (size_t)jBox * v.cap;
+         const real_t* __restrict__ qx = v.rx + base;
+         const real_t* __restrict__ qy = v.ry + base;
+         const real_t* __restrict__ qz = v.rz + base;
+         // as ljCellLoop: 8 wave-uniform neighbours per batch of scalar loads, then their tests
+         int j = 0;
+         for (; j + 8 <= nj; j += 8) {
+            real_t xs[8], ys[8], zs[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { xs[u] = qx[j + u]; ys[u] = qy[j + u]; zs[u] = qz[j + u]; }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) test(xs[u], ys[u], zs[u], base + j + u);
+         }
+         for (; j < nj; ++j) test(qx[j], qy[j], qz[j], base + j);
+      }
+      if (active) {
+         const real_t h = R(0.5) * pair.scale();
+         acc[0] = fmaR(h, wxx, acc[0]); acc[1] = fmaR(h, wyy, acc[1]); acc[2] = fmaR(h, wzz, acc[2]);
+         acc[3] = fmaR(h, wyz, acc[3]); acc[4] = fmaR(h, wxz, acc[4]); acc[5] = fmaR(h, wxy, acc[5]);
+      }
+      if (active && q == 0) {
+         const real_t invMass = R(1.0) / v.speciesMass[v.iSpecies[iOff]];
+         const real_t qx = v.px[iOff], qy = v.py[iOff], qz = v.pz[iOff];
+         acc[6] = fmaR(qx * qx, invMass, acc[6]); acc[7] = fmaR(qy * qy, invMass, acc[7]); acc[8] = fmaR(qz * qz, invMass, acc[8]);
+         acc[9] = fmaR(qy * qz, invMass, acc[9]); acc[10] = fmaR(qx * qz, invMass, acc[10]); acc[11] = fmaR(qx * qy, invMass, acc[11]);
+      }
+   }
+#pragma unroll
+   for (int c = 0; c < VIRIAL_N; ++c) {
+      const double s = waveSumD((double)acc[c]);
+      if (lane == 0) sAcc[wave][c] = s;
+   }
+   __syncthreads();
+   if (threadIdx.x < VIRIAL_N) {
+      const int c = threadIdx.x;
+      v.partial[(size_t)blockIdx.x * VIRIAL_N + c] = (sAcc[0][c] + sAcc[1][c]) + (sAcc[2][c] + sAcc[3][c]);
+   }
+}
+
+// the rows of partials -> out[VIRIAL_N], in a fixed order
+__global__ __launch_bounds__(256)
+void Virial_Final(const double* __restrict__ partial, int nPartial, double* __restrict__ out)
+{
+   __shared__ double sAcc[4][VIRIAL_N];
+   const int lane = laneId(), wave = (int)threadIdx.x >> 6;
+   for (int c = 0; c < VIRIAL_N; ++c) {
+      double a = 0.0;
+      for (int i = threadIdx.x; i < nPartial; i += blockDim.x) a += partial[(size_t)i * VIRIAL_N + c];
+      a = waveSumD(a);
+      if (lane == 0) sAcc[wave][c] = a;
+   }
+   __syncthreads();
+   if (threadIdx.x < VIRIAL_N) {
+      const int c = threadIdx.x;
+      out[c] = (sAcc[0][c] + sAcc[1][c]) + (sAcc[2][c] + sAcc[3][c]);
+   }
+}

@@ -3,7 +3,8 @@
  * Extensions (long options only): --maxAtoms N (link-cell slot capacity; the reference fixes it at
  * compile time with -DMAXATOMS), --maxNeighbors N (Verlet-list rows per atom for the *_nl methods; the reference's
  * MAXNEIGHBORLISTSIZE), --quiet, --ljCutoffSigmas F (the reference hard-wires 5; 2.5 meets its documented LJ cohesive energy),
- * --deviceTimers (also COMD_DEVICE_TIMERS=1: HIP-event timing of the phases in the reference's timer table). */
+ * --deviceTimers (also COMD_DEVICE_TIMERS=1: HIP-event timing of the phases in the reference's timer table),
+ * --pressure (a Pressure(GPa) column in the report: pair virial + kinetic tensor, which the reference does not compute). */
 #include "comd_host.h"
 #include <getopt.h>
 #include <stdlib.h>
@@ -67,6 +68,7 @@ Command parseCommandLine(int argc, char** argv)
       { "quiet",         0,  0, 'i', &cmd.quiet,          0, "no stdout report" },
       { "ljCutoffSigmas", 0, 1, 'd', &cmd.ljCutoffSigmas, 0, "LJ cutoff in sigmas (5 as in ljForce.c:114; 2.5 reproduces the cohesive energy of CoMD.c:897)" },
       { "deviceTimers",  0,  0, 'i', &cmd.deviceTimers,   0, "time the phases of timestep() with HIP events on the device (the host timers of the reference see launches, not kernels)" },
+      { "pressure",      0,  0, 'i', &cmd.pressure,       0, "print the pressure (virial + kinetic, in GPa) at every printed step" },
    };
    const int nDefs = (int)(sizeof defs / sizeof defs[0]);
 

@@ -43,6 +43,7 @@ typedef struct CommandSt {
    int quiet;             /* extension: suppress the stdout report (library use) */
    int deviceTimers;      /* extension: HIP-event timing of the phases of timestep() (the reference's host timers are not device-synchronised) */
    double ljCutoffSigmas; /* extension (tests): LJ cutoff in sigmas; 5 = the reference (ljForce.c:114), 2.5 = upstream CoMD, whose cohesive energy CoMD.c:897 documents */
+   int pressure;          /* extension: pressure column in the report (virial + kinetic tensor at every printed step, the reference has none) */
 } Command;
 
 Command parseCommandLine(int argc, char** argv);
@@ -278,6 +279,8 @@ typedef struct SimFlatSt {
    int nlBuilds;                    /* list builds so far (reported) */
    int quiet, cmdDoeam;
    int iStepPrev, firstPrint;       /* printThings state (static locals in CoMD.c:466-467) */
+   int pressure;                    /* --pressure: printThings shows the pressure computePressure left in W, K, V */
+   real_t W[6], K[6], V;            /* computePressure: global pair virial and kinetic tensor in eV (xx yy zz yz xz xy), volume in A^3 */
 } SimFlat;
 
 SimFlat* initSimulation(Command cmd);
@@ -294,12 +297,17 @@ void setBoundaryCellsHost(SimFlat* sim, HaloExchange* hh);
 double timestep(SimFlat* s, int n, real_t dt);
 void computeForce(SimFlat* s);
 void kineticEnergyGpu(SimFlat* s);
+/* not in the reference: W, K (summed over ranks) and V of the current state, after a complete force evaluation */
+void computePressure(SimFlat* s);
+/* pressure tensor (K + W) / V in eV/A^3 and its trace / 3, and the conversion to GPa */
+#define eVperA3inGPa 160.21766208
+double pressureOf(const SimFlat* s);
 void redistributeAtoms(SimFlat* sim);
 void ensureInteriorForceLaunched(SimFlat* sim);
 
 /* ---- performanceTimers.h ---- */
 enum TimerHandle { totalTimer, loopTimer, timestepTimer, positionTimer, velocityTimer, redistributeTimer, atomHaloTimer,
-                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, numberOfTimers };
+                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, numberOfTimers };
 void profileStart(enum TimerHandle handle);
 void profileStop(enum TimerHandle handle);
 double getElapsedTime(enum TimerHandle handle);
@@ -333,6 +341,7 @@ int      comdPutAtomInBox(SimFlat* s, int gid, int type, const double r[3], cons
 int      comdEamTable(SimFlat* s, int which, double* x0, double* invDx, double* values);   /* 0 phi, 1 rho, 2 F; n + 3 padded samples */
 int      comdLjTable(SimFlat* s, double* x0, double* invDx, double* values);              /* -I: n + 4 padded samples; 0 without -I */
 int      comdNeighborListBuilds(SimFlat* s);              /* Verlet-list builds so far (*_nl methods) */
+void     comdVirial(SimFlat* s, double out[13]);          /* computePressure, then {W[6], K[6], V}: global pair virial and kinetic tensor (eV), volume (A^3) */
 void     comdGridInfo(SimFlat* s, int out[6]);            /* gridSize[3], nLocalBoxes, nTotalBoxes, maxAtoms */
 int      comdMain(int argc, char** argv);                /* the reference's main(): CoMD.c:86-187 */
 void     comdDestroy(SimFlat* s);

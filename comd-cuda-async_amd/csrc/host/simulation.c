@@ -101,7 +101,7 @@ SimFlat* initSimulationHost(Command cmd)
    sim->cmdDoeam = cmd.doeam;
    sim->nSteps = cmd.nSteps; sim->printRate = cmd.printRate; sim->dt = cmd.dt;
    sim->gpuAsync = cmd.gpuAsync; sim->gpuProfile = cmd.gpuProfile;
-   sim->quiet = cmd.quiet; sim->iStepPrev = -1; sim->firstPrint = 1;
+   sim->quiet = cmd.quiet; sim->iStepPrev = -1; sim->firstPrint = 1; sim->pressure = cmd.pressure;
    if (sim->gpuProfile) sim->nSteps = 0;
 
    if (!strcmp(cmd.method, "thread_atom")) sim->method = THREAD_ATOM;
@@ -265,7 +265,8 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
       s->firstPrint = 0;
       fprintf(screenOut,
               "#                                                                                         Performance\n"
-              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms\n");
+              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms%s\n",
+              s->pressure ? "    Pressure(GPa)" : "");
       fflush(screenOut);
    }
    real_t time = iStep * s->dt;
@@ -274,8 +275,23 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
    real_t eU = s->ePotential / s->atoms->nGlobal;
    real_t Temp = (s->eKinetic / s->atoms->nGlobal) / (kB_eV * 1.5);
    double timePerAtom = 1.0e6 * elapsedTime / (double)(nEval * s->atoms->nLocal);
-   fprintf(screenOut, " %6d %10.2f %18.12f %18.12f %18.12f %12.4f %10.4f %12d\n",
+   fprintf(screenOut, " %6d %10.2f %18.12f %18.12f %18.12f %12.4f %10.4f %12d",
            iStep, time, eTotal, eU, eK, Temp, timePerAtom, s->atoms->nGlobal);
+   if (s->pressure) fprintf(screenOut, " %16.10f", pressureOf(s) * eVperA3inGPa);
+   fprintf(screenOut, "\n");
+}
+
+/* --pressure: the final pressure and tensor (K + W) / V, components xx yy zz yz xz xy */
+static void printPressureYaml(FILE* file, SimFlat* s)
+{
+   if (!printRank() || !file) return;
+   static const char* name[6] = { "xx", "yy", "zz", "yz", "xz", "xy" };
+   fprintf(file, "Pressure:\n");
+   fprintf(file, "  Units: GPa\n");
+   fprintf(file, "  Pressure: %.12e\n", pressureOf(s) * eVperA3inGPa);
+   for (int c = 0; c < 6; ++c) fprintf(file, "  P%s: %.12e\n", name[c], ((double)s->K[c] + s->W[c]) / s->V * eVperA3inGPa);
+   fprintf(file, "\n");
+   fflush(file);
 }
 
 Validate* initValidate(SimFlat* sim)
@@ -374,6 +390,7 @@ int comdMain(int argc, char** argv)
       startTimer(commReduceTimer);
       sumAtoms(sim);
       stopTimer(commReduceTimer);
+      if (sim->pressure) { startTimer(pressureTimer); computePressure(sim); stopTimer(pressureTimer); }
       printThings(sim, iStep, getElapsedTime(timestepTimer));
       startTimer(timestepTimer);
       timestep(sim, printRate, sim->dt);
@@ -382,8 +399,10 @@ int comdMain(int argc, char** argv)
    }
    profileStop(loopTimer);
    sumAtoms(sim);
+   if (sim->pressure) { startTimer(pressureTimer); computePressure(sim); stopTimer(pressureTimer); }
    printThings(sim, iStep, getElapsedTime(timestepTimer));
    timestampBarrier("Ending simulation\n");
+   if (sim->pressure) printPressureYaml(yamlFile, sim);
 
    validateResult(validate, sim);
    profileStop(totalTimer);
@@ -416,6 +435,14 @@ SimFlat* comdCreateHostOnly(int argc, char** argv)
 const HostAtoms* comdHostAtoms(SimFlat* s) { return &s->atoms->h; }
 
 int comdNeighborListBuilds(SimFlat* s) { return s->nlBuilds; }
+
+/* computePressure on the current state: out = {W[6], K[6], V} (global, eV and A^3) */
+void comdVirial(SimFlat* s, double out[13])
+{
+   computePressure(s);
+   for (int c = 0; c < 6; ++c) { out[c] = s->W[c]; out[6 + c] = s->K[c]; }
+   out[12] = s->V;
+}
 
 /* EAM table `which` (0 phi, 1 rho, 2 F) as the device receives it: n, x0, invDx and the n + 3 padded samples (values[0] = leading pad) */
 int comdEamTable(SimFlat* s, int which, double* x0, double* invDx, double* values)

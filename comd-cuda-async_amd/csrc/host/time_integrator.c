@@ -75,6 +75,20 @@ void kineticEnergyGpu(SimFlat* s)
    s->eKinetic = eSum[1];
 }
 
+void computePressure(SimFlat* s)
+{
+   real_t local[12], sum[12];
+   computeVirial(&s->gpu, local);
+   addRealParallel(local, sum, 12);
+   for (int c = 0; c < 6; ++c) { s->W[c] = sum[c]; s->K[c] = sum[6 + c]; }
+   s->V = s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2];
+}
+
+double pressureOf(const SimFlat* s)
+{
+   return ((double)s->K[0] + s->K[1] + s->K[2] + s->W[0] + s->W[1] + s->W[2]) / (3.0 * s->V);
+}
+
 static void launchInteriorForce(SimFlat* sim)
 {
    SimGpu* g = &sim->gpu;

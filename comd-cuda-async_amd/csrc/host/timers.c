@@ -14,7 +14,7 @@
 
 static const char* timerName[numberOfTimers] = {
    "total", "loop", "timestep", "  position", "  velocity", "  redistribute", "    atomHalo",
-   "  force", "    eamHalo", "commHalo", "commReduce", "  neighborList"
+   "  force", "    eamHalo", "commHalo", "commReduce", "  neighborList", "pressure"
 };
 
 typedef struct { uint64_t start, total, count, elapsed; int minRank, maxRank; double minValue, maxValue, average, stdev; } Timers;

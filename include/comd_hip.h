@@ -232,6 +232,7 @@ typedef struct SimGpuSt {
    HashTableGpu d_hashTable;
    int          genPairlist;
    int*         d_updateLinkCellsRequired;   /* device [1], zero: the reference's list mode copies it back to ask "did an atom change cells?" (timestep.c:329) */
+   double*      virialBuf;             /* device: the workgroups' partial sums for computeVirial, allocated by its first call */
 } SimGpu;
 
 /* Everything AllocateGpu needs to know about the rank's geometry and potential.
@@ -383,6 +384,16 @@ void advanceVelocityVelocityPositionGpu(SimGpu* sim, real_t dtKick1, real_t dtKi
 /* computeEnergy(SimFlat*, real_t eLocal[2]), gpu_kernels.cu:1045-1059: {sum e, sum p^2/2m} of local atoms.
  * Deterministic two-stage reduction (the reference uses fp64 atomics). Blocks until the result is on the host. */
 void computeEnergy(SimGpu* sim, real_t* eLocal);
+/* Not in the reference (CoMD computes no virial): this rank's share of the pair virial and of the kinetic tensor, in eV,
+ *   out12[0..5]  W_ab = sum over pairs i<j of r_ij,a f_ij,b  (r_ij = r_i - r_j to the image j interacts with, f_ij the force on i due to j),
+ *   out12[6..11] K_ab = sum over local atoms of p_a p_b / m,
+ * each in the order xx yy zz yz xz xy.  A pair of a local and a halo atom counts 1/2 here (the other half belongs to the rank or image that
+ * owns the halo atom), so the sum over ranks is the global tensor.  The pair force is that of the force kernels of the simulation's
+ * potential and mode (LJ analytic or -I table, EAM quadratic tables or -P splines) evaluated on the current positions, with EAM's F'(rhobar)
+ * from dfEmbed including its halo slots: call it after a complete force evaluation (timestep, computeForce).  Any method.  Launched on the
+ * stream computeEnergy uses, after the force work of both streams of the overlap mode; deterministic two-stage reduction; reads r, p and
+ * dfEmbed only.  Blocks until the result is on the host. */
+void computeVirial(SimGpu* sim, real_t* out12);
 
 /* ---- redistribute: gpu_kernels.h:84-86 ------------------------------------------------------ */
 /* updateLinkCellsGpu(SimFlat*), gpu_kernels.cu:469-504: empty the halo cells, move every local atom whose
