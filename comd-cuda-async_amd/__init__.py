@@ -129,6 +129,12 @@ def lib_host():
         lib.comdLjTable.restype = ctypes.c_int
         lib.comdEamTable.restype = ctypes.c_int
         lib.comdVirial.argtypes = [vp, c_double_p]
+        lib.comdSetLangevin.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_int]
+        lib.comdSetLangevin.restype = ctypes.c_int
+        lib.comdGetLangevin.argtypes = [vp, c_double_p, ctypes.POINTER(ctypes.c_uint64)]
+        lib.comdGetLangevin.restype = ctypes.c_int
+        lib.comdStepCount.argtypes = [vp]
+        lib.comdStepCount.restype = ctypes.c_uint64
         lib.comdNeighborListBuilds.argtypes = [vp]
         lib.comdNeighborListBuilds.restype = ctypes.c_int
         lib.comdSimBoxFromTuple.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -275,6 +281,26 @@ class Simulation:
         v = np.empty(n + 4)
         self.lib.comdLjTable(self.ptr, ctypes.byref(x0), ctypes.byref(inv), v.ctypes.data_as(ctypes.c_void_p))
         return x0.value, inv.value, v
+
+    # --- Langevin thermostat (not in the reference: comd-hip --langevin, --langevinTemp, --langevinDamp, --seed) ---
+    def set_langevin(self, temperature, damp_fs=100.0, seed=None, on=True):
+        """BAOAB Langevin thermostat from the next step() on: target `temperature` in K, damping time `damp_fs` in fs, Philox key `seed` (None:
+        keep the current one, the --seed value or its default).  on=False: plain NVE again (the settings are kept)."""
+        if seed is None:
+            seed = self.langevin()["seed"]
+        if self.lib.comdSetLangevin(self.ptr, float(temperature), float(damp_fs), int(seed) & (2 ** 64 - 1), 1 if on else 0) != 0:
+            raise ValueError(f"set_langevin: need temperature >= 0 and damp_fs > 0 (got {temperature}, {damp_fs})")
+
+    def langevin(self):
+        """The thermostat settings: {"on", "temperature" (K), "damp_fs", "seed"}."""
+        out, seed = (ctypes.c_double * 2)(), ctypes.c_uint64(0)
+        on = self.lib.comdGetLangevin(self.ptr, out, ctypes.byref(seed))
+        return {"on": bool(on), "temperature": out[0], "damp_fs": out[1], "seed": int(seed.value)}
+
+    @property
+    def step_count(self):
+        """Steps taken since creation, over all step() calls: the step index of the thermostat's noise."""
+        return int(self.lib.comdStepCount(self.ptr))
 
     @property
     def nl_builds(self):

@@ -21,6 +21,7 @@
 #include "eam_brick_kernels.h"
 #include "eam_atom_brick_kernels.h"
 #include "virial_kernels.h"
+#include "langevin_kernels.h"
 
 static int g_rank = 0;
 
@@ -1552,6 +1553,37 @@ extern "C" void advanceVelocityVelocityPositionGpu(SimGpu* sim, real_t dtKick1, 
                       sim->atoms.r.x, sim->atoms.r.y, sim->atoms.r.z, sim->atoms.p.x, sim->atoms.p.y, sim->atoms.p.z,
                       sim->atoms.f.x, sim->atoms.f.y, sim->atoms.f.z, sim->atoms.iSpecies, sim->species_mass,
                       sim->boxes.nAtoms, sim->boxes.nLocalBoxes, sim->maxAtoms, dtKick1, dtKick2, dtDrift, sk, integratorLaneBits(sim));
+   LAUNCH_CHECK();
+}
+
+// BAOAB Langevin forms of the two launches above (langevin_kernels.h; no counterpart in the reference): same grid, stream and skin check
+static LangevinO langevinOf(real_t c1, real_t c2, real_t kT, uint64_t seed, uint64_t step)
+{
+   LangevinO o = { c1, c2, kT, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step, (uint32_t)(step >> 32) };
+   return o;
+}
+
+extern "C" void advanceVelocityPositionLangevinGpu(SimGpu* sim, real_t dtKick, real_t dtHalfDrift, real_t c1, real_t c2, real_t kT,
+                                                   uint64_t seed, uint64_t step)
+{
+   const SkinCheck sk = skinCheckOf(sim);
+   hipLaunchKernelGGL(AdvanceVelocityPositionLangevin, integratorGrid(sim), dim3(256), 0, S(sim->boundary_stream),
+                      sim->atoms.r.x, sim->atoms.r.y, sim->atoms.r.z, sim->atoms.p.x, sim->atoms.p.y, sim->atoms.p.z,
+                      sim->atoms.f.x, sim->atoms.f.y, sim->atoms.f.z, sim->atoms.iSpecies, sim->atoms.gid, sim->species_mass,
+                      sim->boxes.nAtoms, sim->boxes.nLocalBoxes, sim->maxAtoms, dtKick, dtHalfDrift, langevinOf(c1, c2, kT, seed, step), sk,
+                      integratorLaneBits(sim));
+   LAUNCH_CHECK();
+}
+
+extern "C" void advanceVelocityVelocityPositionLangevinGpu(SimGpu* sim, real_t dtKick1, real_t dtKick2, real_t dtHalfDrift, real_t c1, real_t c2,
+                                                           real_t kT, uint64_t seed, uint64_t step)
+{
+   const SkinCheck sk = skinCheckOf(sim);
+   hipLaunchKernelGGL(AdvanceVelocityVelocityPositionLangevin, integratorGrid(sim), dim3(256), 0, S(sim->boundary_stream),
+                      sim->atoms.r.x, sim->atoms.r.y, sim->atoms.r.z, sim->atoms.p.x, sim->atoms.p.y, sim->atoms.p.z,
+                      sim->atoms.f.x, sim->atoms.f.y, sim->atoms.f.z, sim->atoms.iSpecies, sim->atoms.gid, sim->species_mass,
+                      sim->boxes.nAtoms, sim->boxes.nLocalBoxes, sim->maxAtoms, dtKick1, dtKick2, dtHalfDrift, langevinOf(c1, c2, kT, seed, step),
+                      sk, integratorLaneBits(sim));
    LAUNCH_CHECK();
 }
 

@@ -4,9 +4,11 @@
  * compile time with -DMAXATOMS), --maxNeighbors N (Verlet-list rows per atom for the *_nl methods; the reference's
  * MAXNEIGHBORLISTSIZE), --quiet, --ljCutoffSigmas F (the reference hard-wires 5; 2.5 meets its documented LJ cohesive energy),
  * --deviceTimers (also COMD_DEVICE_TIMERS=1: HIP-event timing of the phases in the reference's timer table),
- * --pressure (a Pressure(GPa) column in the report: pair virial + kinetic tensor, which the reference does not compute). */
+ * --pressure (a Pressure(GPa) column in the report: pair virial + kinetic tensor, which the reference does not compute),
+ * --langevin, --langevinTemp K, --langevinDamp FS, --seed N (BAOAB Langevin thermostat; the reference integrates NVE only). */
 #include "comd_host.h"
 #include <getopt.h>
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -35,6 +37,7 @@ Command parseCommandLine(int argc, char** argv)
    cmd.nSteps = 100; cmd.printRate = 10;
    cmd.ljCutoffSigmas = 5.0;
    cmd.dt = 1.0; cmd.lat = -1.0; cmd.temperature = 600.0; cmd.initialDelta = 0.0; cmd.relativeSkinDistance = 0.1;
+   cmd.langevinTemp = NAN; cmd.langevinDamp = COMD_LANGEVIN_DAMP; cmd.seed = COMD_LANGEVIN_SEED;
    int help = 0;
 
    const ArgDef defs[] = {
@@ -69,6 +72,10 @@ Command parseCommandLine(int argc, char** argv)
       { "ljCutoffSigmas", 0, 1, 'd', &cmd.ljCutoffSigmas, 0, "LJ cutoff in sigmas (5 as in ljForce.c:114; 2.5 reproduces the cohesive energy of CoMD.c:897)" },
       { "deviceTimers",  0,  0, 'i', &cmd.deviceTimers,   0, "time the phases of timestep() with HIP events on the device (the host timers of the reference see launches, not kernels)" },
       { "pressure",      0,  0, 'i', &cmd.pressure,       0, "print the pressure (virial + kinetic, in GPa) at every printed step" },
+      { "langevin",      0,  0, 'i', &cmd.langevin,       0, "BAOAB Langevin thermostat (NVT) in the integrator" },
+      { "langevinTemp",  0,  1, 'd', &cmd.langevinTemp,   0, "Langevin target temperature (K; default: the -T value)" },
+      { "langevinDamp",  0,  1, 'd', &cmd.langevinDamp,   0, "Langevin damping time tau (fs; default 100)" },
+      { "seed",          0,  1, 'u', &cmd.seed,           0, "key of the Langevin noise (Philox4x32-10)" },
    };
    const int nDefs = (int)(sizeof defs / sizeof defs[0]);
 
@@ -93,6 +100,7 @@ Command parseCommandLine(int argc, char** argv)
       switch (d->type) {
          case 'i': *(int*)d->ptr = atoi(optarg); break;
          case 'd': *(double*)d->ptr = atof(optarg); break;
+         case 'u': *(uint64_t*)d->ptr = strtoull(optarg, NULL, 0); break;
          case 's': strncpy((char*)d->ptr, optarg, (size_t)d->size - 1); ((char*)d->ptr)[d->size - 1] = '\0'; break;
       }
    }
@@ -102,6 +110,7 @@ Command parseCommandLine(int argc, char** argv)
       if (strcmp(cmd.potType, "setfl") == 0) strcpy(cmd.potName, "Cu01.eam.alloy");
       if (strcmp(cmd.potType, "funcfl") == 0) strcpy(cmd.potName, "Cu_u6.eam");
    }
+   if (isnan(cmd.langevinTemp)) cmd.langevinTemp = cmd.temperature;
    if (help) { printArgs(defs, nDefs); exit(2); }
    return cmd;
 }
@@ -130,10 +139,17 @@ void printCmdYaml(FILE* file, Command* cmd)
            "  GPU async opt: %d\n"
            "  GPU profiling mode: %d\n"
            "  GPU method: %s\n"
-           "  Space-filling (Hilbert): %d\n"
-           "\n",
+           "  Space-filling (Hilbert): %d\n",
            cmd->doeam, cmd->potDir, cmd->potName, cmd->potType, cmd->nx, cmd->ny, cmd->nz,
            cmd->xproc, cmd->yproc, cmd->zproc, cmd->lat, cmd->nSteps, cmd->printRate, cmd->dt,
            cmd->temperature, cmd->initialDelta, cmd->gpuAsync, cmd->gpuProfile, cmd->method, cmd->doHilbert);
+   if (cmd->langevin)
+      fprintf(file,
+              "  Langevin thermostat: 1\n"
+              "  Langevin temperature: %g K\n"
+              "  Langevin damping: %g fs\n"
+              "  Langevin seed: %llu\n",
+              cmd->langevinTemp, cmd->langevinDamp, (unsigned long long)cmd->seed);
+   fprintf(file, "\n");
    fflush(file);
 }

@@ -44,7 +44,14 @@ typedef struct CommandSt {
    int deviceTimers;      /* extension: HIP-event timing of the phases of timestep() (the reference's host timers are not device-synchronised) */
    double ljCutoffSigmas; /* extension (tests): LJ cutoff in sigmas; 5 = the reference (ljForce.c:114), 2.5 = upstream CoMD, whose cohesive energy CoMD.c:897 documents */
    int pressure;          /* extension: pressure column in the report (virial + kinetic tensor at every printed step, the reference has none) */
+   int langevin;          /* extension: BAOAB Langevin thermostat (NVT) in the integrator; the reference integrates NVE only */
+   double langevinTemp;   /* extension: its target in K; NAN until given = the -T value */
+   double langevinDamp;   /* extension: its damping time tau in fs (default 100) */
+   uint64_t seed;         /* extension: the key of its Philox noise (default COMD_LANGEVIN_SEED) */
 } Command;
+
+#define COMD_LANGEVIN_SEED 0x436f4d44ull     /* "CoMD" */
+#define COMD_LANGEVIN_DAMP 100.0
 
 Command parseCommandLine(int argc, char** argv);
 void printCmdYaml(FILE* file, Command* cmd);
@@ -281,6 +288,10 @@ typedef struct SimFlatSt {
    int iStepPrev, firstPrint;       /* printThings state (static locals in CoMD.c:466-467) */
    int pressure;                    /* --pressure: printThings shows the pressure computePressure left in W, K, V */
    real_t W[6], K[6], V;            /* computePressure: global pair virial and kinetic tensor in eV (xx yy zz yz xz xy), volume in A^3 */
+   int langevin;                    /* --langevin / comdSetLangevin: timestep() runs the BAOAB Langevin kernels */
+   double langevinTemp, langevinDamp;   /* target (K) and damping time tau (fs) */
+   uint64_t langevinSeed;           /* Philox key */
+   uint64_t stepCount;              /* global step index: 0 at creation, one per step of timestep(), the same on every rank (the noise counter) */
 } SimFlat;
 
 SimFlat* initSimulation(Command cmd);
@@ -341,6 +352,11 @@ int      comdPutAtomInBox(SimFlat* s, int gid, int type, const double r[3], cons
 int      comdEamTable(SimFlat* s, int which, double* x0, double* invDx, double* values);   /* 0 phi, 1 rho, 2 F; n + 3 padded samples */
 int      comdLjTable(SimFlat* s, double* x0, double* invDx, double* values);              /* -I: n + 4 padded samples; 0 without -I */
 int      comdNeighborListBuilds(SimFlat* s);              /* Verlet-list builds so far (*_nl methods) */
+/* not in the reference: the Langevin thermostat from the next timestep() call on (on = 0: NVE again).  -1 and nothing changed if tempK < 0 or
+ * tauFs <= 0 */
+int      comdSetLangevin(SimFlat* s, double tempK, double tauFs, uint64_t seed, int on);
+int      comdGetLangevin(SimFlat* s, double out[2], uint64_t* seed);    /* on/off; out = {tempK, tauFs} */
+uint64_t comdStepCount(SimFlat* s);                       /* steps taken since creation */
 void     comdVirial(SimFlat* s, double out[13]);          /* computePressure, then {W[6], K[6], V}: global pair virial and kinetic tensor (eV), volume (A^3) */
 void     comdGridInfo(SimFlat* s, int out[6]);            /* gridSize[3], nLocalBoxes, nTotalBoxes, maxAtoms */
 int      comdMain(int argc, char** argv);                /* the reference's main(): CoMD.c:86-187 */

@@ -129,6 +129,12 @@ SimFlat* initSimulationHost(Command cmd)
    sim->usePairlist = cmd.usePairlist;
    if (sim->usePairlist && (cmd.doeam || sim->method != CTA_CELL)) { printf("Error: -L applies to LJ with -m cta_cell.\n"); exit(-1); }
    sim->useNL = sim->useNL || sim->usePairlist;        /* frozen slots between rebuilds, positional halo refresh */
+   /* --langevin (not in the reference): BAOAB Langevin thermostat in the integrator, refused with a damping time or a target it cannot use */
+   if (!(cmd.langevinDamp > 0.0)) { printf("Error: --langevinDamp must be > 0 fs (got %g).\n", cmd.langevinDamp); exit(-1); }
+   if (cmd.langevinTemp < 0.0 && (cmd.langevin || cmd.langevinTemp != cmd.temperature)) {
+      printf("Error: --langevinTemp must be >= 0 K (got %g).\n", cmd.langevinTemp); exit(-1);
+   }
+   sim->langevin = cmd.langevin; sim->langevinTemp = cmd.langevinTemp; sim->langevinDamp = cmd.langevinDamp; sim->langevinSeed = cmd.seed;
 
    sim->pot = initPotential(cmd.doeam, cmd.potDir, cmd.potName, cmd.potType);
    if (!cmd.doeam && cmd.ljCutoffSigmas > 0.0) sim->pot->cutoff = cmd.ljCutoffSigmas * ((LjPotential*)sim->pot)->sigma;
@@ -435,6 +441,21 @@ SimFlat* comdCreateHostOnly(int argc, char** argv)
 const HostAtoms* comdHostAtoms(SimFlat* s) { return &s->atoms->h; }
 
 int comdNeighborListBuilds(SimFlat* s) { return s->nlBuilds; }
+
+int comdSetLangevin(SimFlat* s, double tempK, double tauFs, uint64_t seed, int on)
+{
+   if (!(tempK >= 0.0) || !(tauFs > 0.0)) return -1;
+   s->langevin = on != 0; s->langevinTemp = tempK; s->langevinDamp = tauFs; s->langevinSeed = seed;
+   return 0;
+}
+
+int comdGetLangevin(SimFlat* s, double out[2], uint64_t* seed)
+{
+   out[0] = s->langevinTemp; out[1] = s->langevinDamp; *seed = s->langevinSeed;
+   return s->langevin;
+}
+
+uint64_t comdStepCount(SimFlat* s) { return s->stepCount; }
 
 /* computePressure on the current state: out = {W[6], K[6], V} (global, eV and A^3) */
 void comdVirial(SimFlat* s, double out[13])

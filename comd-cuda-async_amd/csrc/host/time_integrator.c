@@ -4,19 +4,35 @@
  * include/comd_hip.h; the only blocking device round-trip per step on one rank is none at all
  * (the reference has >= 20) -- energies are fetched every printRate steps. */
 #include "comd_host.h"
+#include <math.h>
 #include <stdlib.h>
 
 static void advanceVelocity(SimFlat* s, real_t dt) { advanceVelocityGpu(&s->gpu, dt); }
 
+/* --langevin (not in the reference): BAOAB, the O update between the two half drifts of each step (hip/langevin_kernels.h).  c1, c2 from
+ * this call's dt, in double */
+typedef struct { int on; real_t c1, c2, kT; uint64_t seed; } Langevin;
+static Langevin langevinOf(const SimFlat* s, real_t dt)
+{
+   Langevin l = { s->langevin, 0, 0, 0, s->langevinSeed };
+   if (l.on) {
+      const double c1 = exp(-(double)dt / s->langevinDamp);
+      l.c1 = (real_t)c1; l.c2 = (real_t)sqrt(1.0 - c1 * c1); l.kT = (real_t)(kB_eV * s->langevinTemp);
+   }
+   return l;
+}
+
 double timestep(SimFlat* s, int nSteps, real_t dt)
 {
+   const Langevin lv = langevinOf(s, dt);
    for (int ii = 0; ii < nSteps; ++ii) {
       /* half kick + drift fused in one kernel (same arithmetic as advanceVelocity(dt/2) then advancePosition(dt)); from the second step
        * on they ride with the previous step's closing half kick (below) */
       if (ii == 0) {
          startTimer(velocityTimer);
          startTimer(positionTimer);
-         advanceVelocityPositionGpu(&s->gpu, 0.5 * dt, dt);
+         if (lv.on) advanceVelocityPositionLangevinGpu(&s->gpu, 0.5 * dt, 0.5 * dt, lv.c1, lv.c2, lv.kT, lv.seed, s->stepCount);
+         else advanceVelocityPositionGpu(&s->gpu, 0.5 * dt, dt);
          stopTimer(positionTimer);
          stopTimer(velocityTimer);
       }
@@ -42,10 +58,12 @@ double timestep(SimFlat* s, int nSteps, real_t dt)
          /* closing half kick of this step + opening half kick and drift of the next: one pass over the atoms, the two kicks still two
           * separate roundings (bit-identical to the three calls of timestep.c:52-58, 95) */
          startTimer(positionTimer);
-         advanceVelocityVelocityPositionGpu(&s->gpu, 0.5 * dt, 0.5 * dt, dt);
+         if (lv.on) advanceVelocityVelocityPositionLangevinGpu(&s->gpu, 0.5 * dt, 0.5 * dt, 0.5 * dt, lv.c1, lv.c2, lv.kT, lv.seed, s->stepCount + 1);
+         else advanceVelocityVelocityPositionGpu(&s->gpu, 0.5 * dt, 0.5 * dt, dt);
          stopTimer(positionTimer);
       }
       stopTimer(velocityTimer);
+      s->stepCount++;
    }
    kineticEnergyGpu(s);
    return s->ePotential;

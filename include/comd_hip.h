@@ -22,6 +22,8 @@
 #ifndef COMD_HIP_H
 #define COMD_HIP_H
 
+#include <stdint.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -381,6 +383,17 @@ void advanceVelocityPositionGpu(SimGpu* sim, real_t dtKick, real_t dtDrift);
 /* the second half kick of a step and the first half kick + drift of the next in one pass: bit-identical to advanceVelocityGpu(dtKick1)
  * followed by advanceVelocityPositionGpu(dtKick2, dtDrift) */
 void advanceVelocityVelocityPositionGpu(SimGpu* sim, real_t dtKick1, real_t dtKick2, real_t dtDrift);
+/* Not in the reference (CoMD integrates NVE only): the BAOAB Langevin thermostat fused into the two launches above.  The steps are
+ * B p += dtKick f, A r += dtHalfDrift p/m, O p = c1 p + c2 sqrt(m kT) xi, A r += dtHalfDrift p/m, with c1 = exp(-dt/tau), c2 = sqrt(1 - c1^2)
+ * (computed by the caller from the dt of the step), kT = kB T in eV and m the species mass.  xi: three N(0,1) from one Philox4x32-10 call
+ * with key (seed low 32 bits, seed high 32 bits) and counter ((uint32) gid, step low 32 bits, step high 32 bits, 0), by Box-Muller in
+ * real_t; step is the global index of the step the O update belongs to.  Local atoms only; the same grid, stream and skin
+ * check as the NVE launches, which they replace one for one. */
+void advanceVelocityPositionLangevinGpu(SimGpu* sim, real_t dtKick, real_t dtHalfDrift, real_t c1, real_t c2, real_t kT, uint64_t seed, uint64_t step);
+/* the closing half kick of a step (dtKick1), then B A O A of the next (dtKick2, dtHalfDrift): the two kicks stay two roundings, as in
+ * advanceVelocityVelocityPositionGpu */
+void advanceVelocityVelocityPositionLangevinGpu(SimGpu* sim, real_t dtKick1, real_t dtKick2, real_t dtHalfDrift, real_t c1, real_t c2, real_t kT,
+                                                uint64_t seed, uint64_t step);
 /* computeEnergy(SimFlat*, real_t eLocal[2]), gpu_kernels.cu:1045-1059: {sum e, sum p^2/2m} of local atoms.
  * Deterministic two-stage reduction (the reference uses fp64 atomics). Blocks until the result is on the host. */
 void computeEnergy(SimGpu* sim, real_t* eLocal);
