@@ -50,6 +50,75 @@ static void allowDynamicLds(const void* fn, size_t lds)
    if (lds > g) { HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); g = lds; }
 }
 
+// ---- tuning: the COMD_* environment variables of this file, read once per simulation ---------------------------------------
+// A variable changed after AllocateGpu no longer reaches that simulation.  All are optional, for tests, A/B runs and diagnosis (README.md has the same table).
+struct ComdTuning {
+   //                             variable                      meaning                                                                                  default
+   bool   nlGlobal;            // COMD_NL_GLOBAL (set)          Verlet lists in the plain 32-bit global-slot format, not the LDS-relative 16-bit ones      off
+   bool   eamNlLds;            // COMD_EAM_NL=lds               round 3's EAM list kernel (a wave stages every cell's stencil), not rows of the brick kernel  off
+   int    ljWaves;             // COMD_LJ_WAVES=k (> 0)         at most k waves per cell in LJ_Force_thread_atom (tests: the extra-chunk path)              cap/64
+   bool   ljPrune;             // COMD_LJ_PRUNE=0               LJ thread_atom walks all 27 cells, no candidate lists                                       lists
+   int    ljListCap;           // COMD_LJ_LIST_CAP=n (> 0)      candidate rows of n entries, rounded up to 8 (tests: rows too short fall back to the walk)  70 % of a stencil
+   double ljListBudgetMb;      // COMD_LJ_LIST_BUDGET_MB=x      memory the LJ candidate lists may take (tests: the fallback to the plain walk)              what is free
+   bool   ljCtaSlabs;          // COMD_LJ_CTA_SLABS=1           LJ cta_cell in its slab form                                                                box-pruned form
+   bool   eamCtaCell;          // COMD_EAM_CTA=cell             round 2's EAM cta_cell kernel (a wave stages every cell's stencil itself)                   brick kernel
+   bool   eamThreadAtomCell;   // COMD_EAM_THREAD_ATOM=cell     round 2's EAM thread_atom kernel, not the thread-per-atom kernel on the brick image         brick image
+   bool   eamGroups;           // COMD_EAM_GROUPS=0             the overlap mode's boundary / interior launches take the host's lists cell by cell          whole bricks
+   int    eamBrickBy, eamBrickBz;      // COMD_EAM_BRICK=by,bz  cells of a brick of cta_cell and the list method (each >= 1, by * bz <= 64, block staged)   4,2
+   int    eamImage;            // COMD_EAM_IMAGE=n (>= 64)      records of the brick's LDS image, rounded up to 8 (tests: bricks that outgrow it)           fullest block
+   int    eamAblate;           // COMD_EAM_ABLATE=bits          EamBrickArgs.debug: parts of the brick kernels switched off (profiling; wrong results)      0
+   bool   eamClamp;            // COMD_EAM_CLAMP=1              the brick kernels keep the table clamps of interpolate() where no pair needs them           dropped
+   int    eamAtomRows;         // COMD_EAM_ATOM_ROWS=n (8..128) bytes of a thread's row in thread_atom, rounded down to 8 (tests: rows that overflow)       sphere + 50 %
+   bool   eamAtomHandover;     // COMD_EAM_ATOM_HANDOVER=0      pass 3 of thread_atom tests again, reads no rows of pass 1                                  hand-over
+   int    eamAtomBrickBy, eamAtomBrickBz;      // COMD_EAM_ATOM_BRICK=by,bz      cells of a thread_atom brick (as COMD_EAM_BRICK)                          first fit of 4,4 ...
+   int    eamAtomLdsPad;       // COMD_EAM_ATOM_LDS_PAD=n       bytes of LDS a thread_atom launch asks for beyond its need (fewer workgroups per CU)        0
+   int    eamCtaWaves;         // COMD_EAM_CTA_WAVES=k (1..8)   waves per workgroup of COMD_EAM_CTA=cell                                                    4
+   int    eamStencil;          // COMD_EAM_STENCIL=n (>= 64)    records of the LDS slice of COMD_EAM_CTA=cell, rounded up to 8                              density + 20-30 %
+   bool   nlSync;              // COMD_NL_SYNC=1                the deferred "rebuild the lists?" test (COMD_NL_DEFERRED) blocks every step                 off
+   bool   eamListsEveryBuild;  // COMD_EAM_LISTS_EVERY_BUILD (set)  the brick lists of the EAM list method remade at every list build                      kept while they fit
+   bool   nlBankOrder;         // COMD_NL_BANK_ORDER=1          LJ Verlet rows ordered by LDS bank class at build time (an experiment)                      off
+   double nlMargin;            // COMD_NL_MARGIN=x (0 <= x < 1) the deferred test's margin as a fraction of skin/2 (tests: force the stop); < 0 = unset     4 / list life
+};
+static ComdTuning readTuning()
+{
+   auto env = getenv;
+   auto num = [&](const char* name) { const char* e = env(name); return e ? atoi(e) : 0; };                  // 0 when unset
+   auto is = [&](const char* name, const char* value) { const char* e = env(name); return e && !strcmp(e, value); };
+   auto isZero = [&](const char* name) { const char* e = env(name); return e && atoi(e) == 0; };             // set, and to 0
+   auto shape = [&](const char* name, int* by, int* bz) { const char* e = env(name); if (!(e && sscanf(e, "%d,%d", by, bz) == 2 && *by >= 1 && *bz >= 1 && *by * *bz <= 64)) *by = *bz = 0; };
+   ComdTuning t;
+   t.nlGlobal = env("COMD_NL_GLOBAL") != nullptr;
+   t.eamNlLds = is("COMD_EAM_NL", "lds");
+   t.ljWaves = num("COMD_LJ_WAVES") > 0 ? num("COMD_LJ_WAVES") : 0;
+   t.ljPrune = !isZero("COMD_LJ_PRUNE");
+   t.ljListCap = num("COMD_LJ_LIST_CAP") > 0 ? (num("COMD_LJ_LIST_CAP") + 7) & ~7 : 0;
+   t.ljListBudgetMb = env("COMD_LJ_LIST_BUDGET_MB") ? atof(env("COMD_LJ_LIST_BUDGET_MB")) : INFINITY;
+   t.ljCtaSlabs = num("COMD_LJ_CTA_SLABS") != 0;
+   t.eamCtaCell = is("COMD_EAM_CTA", "cell");
+   t.eamThreadAtomCell = is("COMD_EAM_THREAD_ATOM", "cell");
+   t.eamGroups = !isZero("COMD_EAM_GROUPS");
+   shape("COMD_EAM_BRICK", &t.eamBrickBy, &t.eamBrickBz);
+   t.eamImage = num("COMD_EAM_IMAGE") >= 64 ? (num("COMD_EAM_IMAGE") + 7) / 8 * 8 : 0;
+   t.eamAblate = num("COMD_EAM_ABLATE");
+   t.eamClamp = num("COMD_EAM_CLAMP") != 0;
+   t.eamAtomRows = num("COMD_EAM_ATOM_ROWS") >= 8 && num("COMD_EAM_ATOM_ROWS") <= 128 ? num("COMD_EAM_ATOM_ROWS") / 8 * 8 : 0;
+   t.eamAtomHandover = !isZero("COMD_EAM_ATOM_HANDOVER");
+   shape("COMD_EAM_ATOM_BRICK", &t.eamAtomBrickBy, &t.eamAtomBrickBz);
+   t.eamAtomLdsPad = num("COMD_EAM_ATOM_LDS_PAD");
+   t.eamCtaWaves = num("COMD_EAM_CTA_WAVES") >= 1 && num("COMD_EAM_CTA_WAVES") <= 8 ? num("COMD_EAM_CTA_WAVES") : 0;
+   t.eamStencil = num("COMD_EAM_STENCIL") >= 64 ? (num("COMD_EAM_STENCIL") + 7) / 8 * 8 : 0;
+   t.nlSync = num("COMD_NL_SYNC") != 0;
+   t.eamListsEveryBuild = env("COMD_EAM_LISTS_EVERY_BUILD") != nullptr;
+   t.nlBankOrder = num("COMD_NL_BANK_ORDER") != 0;
+   t.nlMargin = env("COMD_NL_MARGIN") && atof(env("COMD_NL_MARGIN")) >= 0.0 && atof(env("COMD_NL_MARGIN")) < 1.0 ? atof(env("COMD_NL_MARGIN")) : -1.0;
+   return t;
+}
+// AllocateGpu fills SimGpu.tuning; a SimGpu that reaches a launch wrapper without it gets its record here
+static const ComdTuning& tuningOf(SimGpu* sim) { if (!sim->tuning) sim->tuning = new ComdTuning(readTuning()); return *(const ComdTuning*)sim->tuning; }
+// The density estimates behind the sizing of rows, lists and LDS images: the perfect FCC lattice, 4 atoms per lat^3 (GpuConfig.latticeConstant; 0: copper)
+static double latticeConstantOf(const SimGpu* sim) { return sim->latticeConstant > 0.0 ? sim->latticeConstant : 3.615; }
+static const double SPHERE_VOLUME = 4.18879020478639;      // of radius 1
+
 
 // ---- force-kernel timing (bench.py roofline leg): per simulation, SimGpu.timing -----------------------------------
 // Two classes of launches are timed apart: kind 0 the force kernels proper (the kernel the roofline object names), kind 1 what a force
@@ -270,6 +339,7 @@ extern "C" void AllocateGpu(SimGpu* sim, const GpuConfig* cfg)
    sim->latticeConstant = cfg->latticeConstant;
    sim->do_eam = cfg->do_eam;
    sim->mass = cfg->mass;
+   const ComdTuning& tune = tuningOf(sim);
    if (cfg->maxAtoms < 1 || cfg->maxAtoms > 1024) { fprintf(stderr, "AllocateGpu: maxAtoms %d outside [1,1024]\n", cfg->maxAtoms); exit(-1); }
    if (!cfg->do_eam && (cfg->maxAtoms % 64) != 0) { fprintf(stderr, "AllocateGpu: LJ needs maxAtoms %% 64 == 0 (got %d)\n", cfg->maxAtoms); exit(-1); }
 
@@ -314,13 +384,13 @@ extern "C" void AllocateGpu(SimGpu* sim, const GpuConfig* cfg)
       nl->maxNeighbors = cfg->maxNeighbors;
       if (nl->maxNeighbors <= 0) {
          // atoms inside the list sphere at the perfect-lattice density (4 per lat^3), + 20 % and 24 for thermal crowding
-         const double rl = cutoff + cfg->skinDistance, lat = cfg->latticeConstant > 0.0 ? cfg->latticeConstant : 3.615;
-         const double expect = 4.0 / (lat * lat * lat) * 4.18879020478639 * rl * rl * rl;
+         const double rl = cutoff + cfg->skinDistance, lat = latticeConstantOf(sim);
+         const double expect = 4.0 / (lat * lat * lat) * SPHERE_VOLUME * rl * rl * rl;
          nl->maxNeighbors = ((int)(1.2 * expect) + 24 + 7) / 8 * 8;
       }
       if (nl->maxNeighbors > 27 * cfg->maxAtoms) nl->maxNeighbors = 27 * cfg->maxAtoms;
       const size_t localSlots = (size_t)cfg->nLocalBoxes * cfg->maxAtoms;
-      nl->slabFormat = !cfg->usePairlist && !cfg->do_eam && cfg->maxAtoms % 64 == 0 && cfg->maxAtoms <= 512 && !getenv("COMD_NL_GLOBAL");
+      nl->slabFormat = !cfg->usePairlist && !cfg->do_eam && cfg->maxAtoms % 64 == 0 && cfg->maxAtoms <= 512 && !tune.nlGlobal;
       if (cfg->usePairlist) {
          if (cfg->do_eam) { fprintf(stderr, "AllocateGpu: pairlists (-L) are an LJ cta_cell feature\n"); exit(-1); }
          nl->slabFormat = 3;
@@ -328,7 +398,7 @@ extern "C" void AllocateGpu(SimGpu* sim, const GpuConfig* cfg)
          nl->pairlistWaves = (threads + 63) / 64;
          nl->pairlist = dalloc<unsigned>((size_t)cfg->nLocalBoxes * nl->pairlistWaves * LJ_CTA_SLABS * LJ_PL_WORDS);
          nl->pairlistBuildId = -1;
-      } else if (cfg->do_eam && !getenv("COMD_NL_GLOBAL") && !(getenv("COMD_EAM_NL") && !strcmp(getenv("COMD_EAM_NL"), "lds"))
+      } else if (cfg->do_eam && !tune.nlGlobal && !tune.eamNlLds
                  && (double)cfg->nTotalBoxes * cfg->maxAtoms * sizeof(real_t) < 4294967296.0) {
          // [round 4] EAM: rows of the brick kernel (eam_brick_kernels.h, LISTED): 16-bit record numbers in the LDS image of the atom's brick, kept from one
          // list build to the next.  Any table size (setfl tables and -P coefficients are read through L2), any cell capacity.
@@ -344,7 +414,7 @@ extern "C" void AllocateGpu(SimGpu* sim, const GpuConfig* cfg)
          nl->brickQuads = (words + 3) / 4;
          nl->brickRows = dalloc<unsigned>((size_t)cfg->nLocalBoxes * nl->brickRounds * nl->brickQuads * 64 * 4, false);
          nl->brickRowCount = dalloc<unsigned short>(localSlots);
-      } else if (cfg->do_eam && cfg->maxAtoms <= 64 && eamCtaTableBytes(1, cfg->nRho, cfg->nPhi) <= 32 * 1024 && !getenv("COMD_NL_GLOBAL")) {
+      } else if (cfg->do_eam && cfg->maxAtoms <= 64 && eamCtaTableBytes(1, cfg->nRho, cfg->nPhi) <= 32 * 1024 && !tune.nlGlobal) {
          // EAM with LDS-sized tables: 16-bit entries into the wave's staging of the whole 27-cell stencil
          nl->slabFormat = 2;
          nl->slabRows = nl->maxNeighbors;
@@ -506,6 +576,7 @@ extern "C" void DestroyGpu(SimGpu* sim)
       for (auto& ev : t->pool) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
       delete t;
    }
+   delete (ComdTuning*)sim->tuning;
    void* ptrs[] = { sim->boxes.nAtoms, sim->atoms.r.x, sim->atoms.r.y, sim->atoms.r.z, sim->atoms.p.x, sim->atoms.p.y, sim->atoms.p.z,
                     sim->atoms.f.x, sim->atoms.f.y, sim->atoms.f.z, sim->atoms.e, sim->atoms.iSpecies, sim->atoms.gid,
                     sim->neighbor_cells, sim->species_mass, sim->eam_pot.phi.values, sim->eam_pot.rho.values, sim->eam_pot.f.values,
@@ -660,13 +731,14 @@ static LjThreadAtomLaunch prepareLjThreadAtom(SimGpu* sim, const LjArgs& a, int 
    // estimate stay correct (their waves take extra chunks).  COMD_LJ_WAVES=k forces k (tests use 1 to exercise the extra-chunk path).
    int w = sim->maxAtoms / 64;
    if (sim->max_atoms_cell > 0 && (sim->max_atoms_cell + 16 + 63) / 64 < w) w = (sim->max_atoms_cell + 16 + 63) / 64;
-   { const char* e = getenv("COMD_LJ_WAVES"); if (e && atoi(e) > 0 && atoi(e) < w) w = atoi(e); }
+   const ComdTuning& tune = tuningOf(sim);
+   if (tune.ljWaves && tune.ljWaves < w) w = tune.ljWaves;
    const int wavesPerBlock = w <= 4 ? w : 4;
    const unsigned nBlocks = w <= 4 ? (unsigned)num_cells : (unsigned)ceilDiv((long)num_cells * w, 4);
    // candidate lists of the waves (lj_kernels.h): rows sized for 70 % of the fullest stencil the host has seen -- the part of 27 cells
    // within the cutoff of a whole cell's box is 76 %, of a 64-atom slab of it 61 % -- and a wave whose row is too short walks the stencil.
    // COMD_LJ_PRUNE=0 switches the lists off (A/B measurements); COMD_LJ_LIST_CAP=n forces rows of n entries (tests: the fallback).
-   const bool pruneEnv = !(getenv("COMD_LJ_PRUNE") && atoi(getenv("COMD_LJ_PRUNE")) == 0);
+   const bool pruneEnv = tune.ljPrune;
    LjPotentialGpu* lj = &sim->lj_pot;
    if (pruneEnv && !lj->waveCand && lj->packedCap == 0) {
       // the fullest cell right now (one blocking read, once per simulation; SimGpu.max_atoms_cell may not have been filled in yet)
@@ -678,7 +750,7 @@ static LjThreadAtomLaunch prepareLjThreadAtom(SimGpu* sim, const LjArgs& a, int 
       const int occ = fullest + 16 < sim->maxAtoms ? fullest + 16 : sim->maxAtoms;
       lj->waveCandWaves = w;
       lj->waveCandCap = ((int)(0.70 * 27 * occ) + 7) & ~7;
-      { const char* e = getenv("COMD_LJ_LIST_CAP"); if (e && atoi(e) > 0) lj->waveCandCap = (atoi(e) + 7) & ~7; }
+      if (tune.ljListCap) lj->waveCandCap = tune.ljListCap;
       lj->packedCap = ((occ + 7) & ~7) < sim->maxAtoms ? ((occ + 7) & ~7) : sim->maxAtoms;     // a stencil with a fuller cell falls back to the walk
       // list entries are 32-bit byte offsets into the packed records
       // ~250 B of list per atom (18 GB at 256^3) + the packed records (2.9 GB each): when that does not fit what the device has free (keeping 2 GB
@@ -688,7 +760,7 @@ static LjThreadAtomLaunch prepareLjThreadAtom(SimGpu* sim, const LjArgs& a, int 
       size_t freeB = 0, totalB = 0;
       HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
       if ((double)sim->boxes.nTotalBoxes * lj->packedCap * sizeof(LjPos4) >= 4294967296.0) lj->packedCap = -1;     // no lists for this simulation
-      else if (listBytes + 2.0e9 > (double)freeB || (getenv("COMD_LJ_LIST_BUDGET_MB") && listBytes > 1.0e6 * atof(getenv("COMD_LJ_LIST_BUDGET_MB")))) {
+      else if (listBytes + 2.0e9 > (double)freeB || listBytes > 1.0e6 * tune.ljListBudgetMb) {
          fprintf(stderr, "Rank %d: LJ candidate lists need %.1f GB, %.1f GB are free: running without them (the plain 27-cell walk, ~1.4x slower)\n",
                  g_rank, listBytes / 1e9, (double)freeB / 1e9);
          lj->packedCap = -1;
@@ -827,7 +899,7 @@ static void ljForce(SimGpu* sim, int num_cells, int* cells_list, int method, com
       pl.plCut2 = (sim->lj_pot.cutoff + n->skinDistance) * (sim->lj_pot.cutoff + n->skinDistance);
 #define LAUNCH_CTA(PLV) do { if (sim->needEnergy) hipLaunchKernelGGL((LJ_Force_cta_cell<PLV, true>), dim3(num_cells), dim3(threads), lds, S(stream), a, sim->status, pl); \
                             else              hipLaunchKernelGGL((LJ_Force_cta_cell<PLV, false>), dim3(num_cells), dim3(threads), lds, S(stream), a, sim->status, pl); } while (0)
-      if (n->slabFormat != 3 && !(getenv("COMD_LJ_CTA_SLABS") && atoi(getenv("COMD_LJ_CTA_SLABS")) != 0)) {
+      if (n->slabFormat != 3 && !tuningOf(sim).ljCtaSlabs) {
          // the default form: every wave stages its own box-pruned candidates (COMD_LJ_CTA_SLABS=1: the slab kernel, for A/B runs)
          real_t rc2Box, grow;
          ljBoxMargins(sim, a.rc2, &rc2Box, &grow);
@@ -855,481 +927,7 @@ extern "C" void ljForceGpu(SimGpu* sim, int interpolation, int num_cells, int* c
    ljForce(sim, num_cells, cells_list, method, nullptr, interpolation != 0);
 }
 
-static EamArgs makeEamArgs(SimGpu* sim, int num_cells, int* cells_list)
-{
-   EamArgs a;
-   a.rx = sim->atoms.r.x; a.ry = sim->atoms.r.y; a.rz = sim->atoms.r.z;
-   a.fx = sim->atoms.f.x; a.fy = sim->atoms.f.y; a.fz = sim->atoms.f.z; a.e = sim->atoms.e;
-   a.rhobar = sim->eam_pot.rhobar; a.dfEmbed = sim->eam_pot.dfEmbed;
-   a.nAtoms = sim->boxes.nAtoms; a.nbr = sim->neighbor_cells; a.cells = cells_list;
-   a.nCells = num_cells; a.cap = sim->maxAtoms;
-   a.rc2 = sim->eam_pot.cutoff * sim->eam_pot.cutoff;
-   a.phi = sim->eam_pot.phi; a.rho = sim->eam_pot.rho; a.f = sim->eam_pot.f;
-   a.phiS = sim->eam_pot.phiS; a.rhoS = sim->eam_pot.rhoS;
-   a.sel = nullptr; a.tag = 0;
-   return a;
-}
-
-// thread per atom: lanes per cell = the fullest cell the host has seen (+ 2), as a power of two; persistent workgroups when the tables
-// sit in the LDS (8 per CU's worth of 256 CUs), one workgroup per 256 / lanesPerCell cells otherwise
-template <int STEP>
-static void launchEamThreadAtom(SimGpu* sim, const EamArgs& a, int num_cells, hipStream_t st, bool spline)
-{
-   int want = sim->max_atoms_cell > 0 ? sim->max_atoms_cell + 2 : sim->maxAtoms;
-   if (want > sim->maxAtoms) want = sim->maxAtoms;
-   int lanes = 4;
-   while (lanes < want && lanes < 256) lanes *= 2;
-   const int nGroups = ceilDiv(num_cells, 256 / lanes);
-   const size_t tableBytes = eamCtaTableBytes(STEP, a.rho.n, a.phi.n);
-   if (spline) {
-      hipLaunchKernelGGL((EAM_Force_thread_atom<STEP, true, false>), dim3(nGroups), dim3(256), 0, st, a, lanes);
-   } else if (tableBytes <= 32 * 1024) {
-      const int grid = nGroups < 4096 ? nGroups : 4096;
-      hipLaunchKernelGGL((EAM_Force_thread_atom<STEP, false, true>), dim3(grid), dim3(256), tableBytes, st, a, lanes);
-   } else {
-      hipLaunchKernelGGL((EAM_Force_thread_atom<STEP, false, false>), dim3(nGroups), dim3(256), 0, st, a, lanes);
-   }
-   LAUNCH_CHECK();
-}
-
-// cta_cell, brick form (eam_brick_kernels.h): a workgroup stages the cells around a brick of 1 x BY x BZ cells once and its waves take the
-// brick's cells one at a time.  COMD_EAM_BRICK="by,bz" overrides the brick (experiments).  The Verlet-list method of EAM (slabFormat 4) runs on the
-// same kernel with LISTED = true: rows built once per list build, both passes read them back.
-static bool eamListedBrick(const SimGpu* sim, int method)
-{
-   return (method == THREAD_ATOM_NL || method == WARP_ATOM_NL) && sim->atoms.neighborList.slabFormat == 4;
-}
-static bool eamBrickPath(const SimGpu* sim, int method)
-{
-   if (eamListedBrick(sim, method)) return true;
-   return method == CTA_CELL && !(getenv("COMD_EAM_CTA") && !strcmp(getenv("COMD_EAM_CTA"), "cell"))
-          && (double)sim->boxes.nTotalBoxes * sim->maxAtoms * sizeof(real_t) < 4294967296.0;      // (the brick kernel stages with 32-bit byte offsets)
-}
-
-// thread_atom on the brick image (eam_atom_brick_kernels.h).  COMD_EAM_THREAD_ATOM=cell keeps round 2's kernel (a share of a wave per cell, candidates streamed
-// through L2; A/B runs), as do arrays of 4 GiB or more (the staging uses 32-bit byte offsets).
-static bool eamAtomBrickPath(const SimGpu* sim, int method)
-{
-   return (method == THREAD_ATOM || method == WARP_ATOM) && !(getenv("COMD_EAM_THREAD_ATOM") && !strcmp(getenv("COMD_EAM_THREAD_ATOM"), "cell"))
-          && (double)sim->boxes.nTotalBoxes * sim->maxAtoms * sizeof(real_t) < 4294967296.0;
-}
-
-// The overlap mode's two lists as brick groups (eam_brick_kernels.h ClassifyBrickCells): 1 = this is the launch over SimGpu.boundary_cells, 2 = over
-// SimGpu.interior_cells, 0 = any other list (cell marks).  COMD_EAM_GROUPS=0 keeps the lists as they are given (A/B runs, tests).
-static int eamBrickGroupOf(const SimGpu* sim, const int* cells_list, int num_cells, int method)
-{
-   if (!cells_list || !(eamBrickPath(sim, method) || eamAtomBrickPath(sim, method))) return 0;
-   if (getenv("COMD_EAM_GROUPS") && atoi(getenv("COMD_EAM_GROUPS")) == 0) return 0;
-   if (cells_list == sim->boundary_cells && num_cells == sim->n_boundary_cells) return 1;
-   if (cells_list == sim->interior_cells && num_cells == sim->n_interior_cells) return 2;
-   return 0;
-}
-
-// The brick shape of a simulation: 1 x 4 x 2 cells unless COMD_EAM_BRICK says otherwise; fixed by the first launch (rows index the image of that shape).
-static void eamBrickShape(SimGpu* sim, bool listed, int* by, int* bz)
-{
-   if (!sim->eam_pot.brickBy) {
-      int y = 4, z = 2;
-      const int maxCells = listed ? (EAM_BRICK_STAGE_LISTED * 256) / 32 : EAM_BRICK_MAX_CELLS;      // what the staging loop covers (eam_brick_kernels.h)
-      const char* e = getenv("COMD_EAM_BRICK"); int ey = 0, ez = 0;
-      if (e && sscanf(e, "%d,%d", &ey, &ez) == 2 && ey >= 1 && ez >= 1 && 3 * (ey + 2) * (ez + 2) <= maxCells && ey * ez <= 64) { y = ey; z = ez; }
-      sim->eam_pot.brickBy = y; sim->eam_pot.brickBz = z;
-   }
-   *by = sim->eam_pot.brickBy; *bz = sim->eam_pot.brickBz;
-}
-
-static void eamBrickGeometry(SimGpu* sim, bool listed, EamBrickArgs* b)
-{
-   memset(b, 0, sizeof *b);
-   for (int k = 0; k < 3; ++k) { b->geom.g[k] = sim->boxes.gridSize[k]; b->geom.lmin[k] = sim->boxes.localMin[k]; b->geom.lmax[k] = sim->boxes.localMax[k]; b->geom.inv[k] = sim->boxes.invBoxSize[k]; }
-   b->geom.nLocal = sim->boxes.nLocalBoxes; b->geom.nTotal = sim->boxes.nTotalBoxes;
-   b->geom.lookup = sim->boxes.boxIDLookUp; b->geom.reverse = sim->boxes.boxIDLookUpReverse;
-   eamBrickShape(sim, listed, &b->by, &b->bz);
-   b->nby = ceilDiv(b->geom.g[1], b->by); b->nbz = ceilDiv(b->geom.g[2], b->bz);
-}
-
-// The image must hold the atoms of the fullest BLOCK (3 x (by + 2) x (bz + 2) cells), not the mean: the lattice and the cell grid are incommensurate,
-// and at 80^3 the blocks of a 1 x 4 x 2 brick hold 755 atoms on average and up to 918.  A brick whose block outgrows the image takes the
-// thread-per-atom form (correct, many times slower), so the occupancies are read once, the fullest block of this brick shape is found and the image
-// sized for it + 1 % + 8 (blocks gain or lose a handful of atoms through their surface as the lattice moves).  Both passes use that size.
-// Called by the first launch; by every Verlet-list build (the cells were just re-binned); and again when comdEamBrickStats finds bricks in the fall-back.
-static int eamBrickSizeImage(SimGpu* sim, const EamBrickArgs& b, hipStream_t st, bool listed)
-{
-   const double cellVol = 1.0 / (sim->boxes.invBoxSize[0] * sim->boxes.invBoxSize[1] * sim->boxes.invBoxSize[2]);
-   const double lat = sim->latticeConstant > 0.0 ? sim->latticeConstant : 3.615;
-   std::vector<int> counts((size_t)sim->boxes.nTotalBoxes), lookup;
-   HIP_CHECK(hipMemcpyAsync(counts.data(), sim->boxes.nAtoms, counts.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-   if (sim->boxes.boxIDLookUp) {
-      lookup.resize((size_t)sim->boxes.nLocalBoxes);
-      HIP_CHECK(hipMemcpyAsync(lookup.data(), sim->boxes.boxIDLookUp, lookup.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-   }
-   HIP_CHECK(hipStreamSynchronize(st));
-   CellGeom hg = b.geom; hg.lookup = lookup.empty() ? nullptr : lookup.data(); hg.reverse = nullptr;
-   const int gx = hg.g[0], gy = hg.g[1], gz = hg.g[2];
-   // per (y, z) row of three x cells, then the (by + 2) x (bz + 2) window of rows around every brick
-   long fullest = 0;
-   std::vector<int> row3((size_t)gx * (gy + 2) * (gz + 2));
-   for (int z = -1; z <= gz; ++z) for (int y = -1; y <= gy; ++y) for (int x = 0; x < gx; ++x)
-      row3[(size_t)x + (size_t)gx * ((y + 1) + (size_t)(gy + 2) * (z + 1))] =
-         counts[comdBoxFromTuple(&hg, x - 1, y, z)] + counts[comdBoxFromTuple(&hg, x, y, z)] + counts[comdBoxFromTuple(&hg, x + 1, y, z)];
-   // (only blocks made of local cells count: with -a 1 the first launch runs while the halo cells are still being filled; the lattice is periodic, the
-   // blocks at the faces are no fuller than those inside.  A grid too small to have such blocks takes the mean density + 25 %.)
-   for (int bzI = 0; bzI < b.nbz; ++bzI) for (int byI = 0; byI < b.nby; ++byI) for (int x = 1; x < gx - 1; ++x) {
-      if (byI * b.by - 1 < 0 || byI * b.by + b.by > gy - 1 || bzI * b.bz - 1 < 0 || bzI * b.bz + b.bz > gz - 1) continue;
-      long sum = 0;
-      for (int z = bzI * b.bz - 1; z <= bzI * b.bz + b.bz; ++z)
-         for (int y = byI * b.by - 1; y <= byI * b.by + b.by; ++y) sum += row3[(size_t)x + (size_t)gx * ((y + 1) + (size_t)(gy + 2) * (z + 1))];
-      if (sum > fullest) fullest = sum;
-   }
-   if (fullest == 0) fullest = (long)(1.25 * 3 * (b.by + 2) * (b.bz + 2) * cellVol * 4.0 / (lat * lat * lat));
-   int cap = (((int)(fullest * 1.01) + 8 + (listed ? 1 : 0) + 7) / 8) * 8;      // (listed launches keep one more record: the far-away one that pads odd rows)
-   if (cap < 256) cap = 256;
-   if (cap > 4096) cap = 4096;                            // 16-bit numbers would reach 65535; beyond 4096 records the cells take the thread-per-atom form
-   { const char* e = getenv("COMD_EAM_IMAGE"); if (e && atoi(e) >= 64) cap = (atoi(e) + 7) / 8 * 8; }      // experiments / tests: force the fallback
-   return cap;
-}
-
-// Verlet rows: the brick lists of a list build.  The occupancies are final (the atom exchange has run) and frozen until the next build, so the host can
-// look at every block once: the image is sized for what the passes can keep four workgroups per CU with, a brick whose block would outgrow it is listed as
-// its two z halves (eam_brick_kernels.h), and the boundary / interior launches of the overlap mode get their lists of whole bricks here as well.
-static size_t eamBrickTableDoubles(const SimGpu* sim, int step, int spline)
-{
-   const EamPotentialGpu& e = sim->eam_pot;
-   if (step == 0 || spline || eamCtaTableBytes(step, e.rho.n, e.phi.n) > 32 * 1024) return 0;
-   const bool sameGrid = e.phi.n == e.rho.n && e.phi.x0 == e.rho.x0 && e.phi.invDx == e.rho.invDx;
-   return step == 1 ? (size_t)2 * (e.rho.n + 3) + (sameGrid ? 0 : (e.phi.n + 3 - (e.rho.n + 3))) : (size_t)(e.rho.n + 3);
-}
-
-static void eamBrickBuildLists(SimGpu* sim, hipStream_t st, int spline)
-{
-   NeighborListGpu* n = &sim->atoms.neighborList;
-   EamBrickArgs b;
-   eamBrickGeometry(sim, true, &b);
-   const int gx = b.geom.g[0], gy = b.geom.g[1], gz = b.geom.g[2], nBricks = gx * b.nby * b.nbz;
-   std::vector<int> counts((size_t)sim->boxes.nTotalBoxes), lookup, boundary((size_t)(sim->boundary_cells ? sim->n_boundary_cells : 0));
-   HIP_CHECK(hipMemcpyAsync(counts.data(), sim->boxes.nAtoms, counts.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-   if (sim->boxes.boxIDLookUp) {
-      lookup.resize((size_t)sim->boxes.nLocalBoxes);
-      HIP_CHECK(hipMemcpyAsync(lookup.data(), sim->boxes.boxIDLookUp, lookup.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-   }
-   if (!boundary.empty()) HIP_CHECK(hipMemcpyAsync(boundary.data(), sim->boundary_cells, boundary.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-   HIP_CHECK(hipStreamSynchronize(st));
-   CellGeom hg = b.geom; hg.lookup = lookup.empty() ? nullptr : lookup.data(); hg.reverse = nullptr;
-   // atoms of the three x cells around (x, y, z), y and z from -1 to g
-   std::vector<int> row3((size_t)gx * (gy + 2) * (gz + 2));
-   auto r3 = [&](int x, int y, int z) -> int& { return row3[(size_t)x + (size_t)gx * ((y + 1) + (size_t)(gy + 2) * (z + 1))]; };
-   for (int z = -1; z <= gz; ++z) for (int y = -1; y <= gy; ++y) for (int x = 0; x < gx; ++x)
-      r3(x, y, z) = counts[comdBoxFromTuple(&hg, x - 1, y, z)] + counts[comdBoxFromTuple(&hg, x, y, z)] + counts[comdBoxFromTuple(&hg, x + 1, y, z)];
-   // records in the image of the brick part [z0, z0 + nz) of brick (x, byI, bzI): the kernel stages rows y0-1 .. y0+by and planes z0-1 .. z0+nz that lie inside -1 .. g
-   auto blockAtoms = [&](int x, int byI, int z0, int nz) {
-      long sum = 0;
-      for (int z = z0 - 1; z <= z0 + nz && z <= gz; ++z)
-         for (int y = byI * b.by - 1; y <= byI * b.by + b.by && y <= gy; ++y) sum += r3(x, y, z);
-      return sum;
-   };
-   std::vector<long> whole((size_t)nBricks);
-   long fullest = 0;
-   for (int i = 0; i < nBricks; ++i) {
-      const int x = i % gx, byI = (i / gx) % b.nby, bzI = i / (gx * b.nby);
-      whole[i] = blockAtoms(x, byI, bzI * b.bz, b.bz);
-      if (whole[i] > fullest) fullest = whole[i];
-   }
-   // the largest image that leaves four workgroups per CU (160 KB of LDS in 1280-byte granules) in pass 1 and in pass 3
-   const int waves = 4;
-   auto perCu = [&](int step, int cap) {
-      const size_t lds = eamBrickLdsBytes(step, true, eamBrickTableDoubles(sim, step, spline), cap, n->brickRowLen, waves);
-      return lds > 160 * 1024 ? 0 : (int)(160 * 1024 / (((lds + 1279) / 1280) * 1280));
-   };
-   int capFull = (((int)fullest + 1 + 7) / 8) * 8;            // (+ 1: the far-away record; nothing moves between builds, so no head-room)
-   if (capFull < 256) capFull = 256;
-   int cap = capFull;
-   if (cap <= 4096 && (perCu(1, cap) < 4 || perCu(3, cap) < 4) && b.bz % 2 == 0) {
-      int fit = cap;
-      while (fit > 256 && (perCu(1, fit) < 4 || perCu(3, fit) < 4)) fit -= 8;
-      long split = 0;
-      for (int i = 0; i < nBricks; ++i) split += whole[i] + 1 > fit;
-      if (split * 10 <= nBricks) cap = fit;                  // worth it while at most one brick in ten is staged twice
-   }
-   if (cap > 4096) cap = 4096;
-   { const char* e = getenv("COMD_EAM_IMAGE"); if (e && atoi(e) >= 64) cap = (atoi(e) + 7) / 8 * 8; }      // experiments / tests: force halves and the fall-back
-   sim->eam_pot.brickImageCap = cap;
-   const int headroom = cap / 32 > 8 ? cap / 32 : 8;
-   // the lists: [0, stride) bricks that hold a boundary cell, [stride, 2 stride) the others, [2 stride, 3 stride) all of them; brick order, halves adjacent
-   std::vector<char> isBoundary((size_t)sim->boxes.nLocalBoxes, 0);
-   for (int c : boundary) if (c >= 0 && c < sim->boxes.nLocalBoxes) isBoundary[c] = 1;
-   const int stride = 2 * nBricks;
-   std::vector<int> lists((size_t)3 * stride, 0), group((size_t)sim->boxes.nLocalBoxes, 2);
-   int cnt[3] = { 0, 0, 0 };
-   for (int i = 0; i < nBricks; ++i) {
-      const int x = i % gx, by0 = ((i / gx) % b.nby) * b.by, bz0 = (i / (gx * b.nby)) * b.bz;
-      bool any = false;
-      for (int dz = 0; dz < b.bz; ++dz) for (int dy = 0; dy < b.by; ++dy)
-         if (by0 + dy < gy && bz0 + dz < gz) any = any || isBoundary[comdBoxFromTuple(&hg, x, by0 + dy, bz0 + dz)];
-      for (int dz = 0; dz < b.bz; ++dz) for (int dy = 0; dy < b.by; ++dy)
-         if (by0 + dy < gy && bz0 + dz < gz) group[comdBoxFromTuple(&hg, x, by0 + dy, bz0 + dz)] = any ? 1 : 2;
-      const int g = any ? 0 : 1;
-      // (a brick within 3 % of the image goes in halves too: the lists outlive this build -- atoms wander between cells from one build to the next -- and a brick
-      // that outgrows the image later takes the thread-per-atom form until the lists are made again)
-      const bool halves = whole[i] + 1 > cap - headroom && b.bz % 2 == 0 && bz0 + b.bz / 2 < gz;      // (an upper half outside the grid would be an empty workgroup)
-      const int e[2] = { halves ? i | (1 << 28) : i, i | (2 << 28) };
-      for (int k = 0; k < (halves ? 2 : 1); ++k) { lists[(size_t)g * stride + cnt[g]++] = e[k]; lists[(size_t)2 * stride + cnt[2]++] = e[k]; }
-   }
-   if (sim->eam_pot.brickList && sim->eam_pot.brickListStride != stride) { HIP_CHECK(hipFree(sim->eam_pot.brickList)); sim->eam_pot.brickList = nullptr; }
-   if (!sim->eam_pot.brickList) sim->eam_pot.brickList = dalloc<int>((size_t)3 * stride, false);
-   if (!sim->eam_pot.brickGroup) sim->eam_pot.brickGroup = dalloc<int>((size_t)sim->boxes.nLocalBoxes, false);
-   HIP_CHECK(hipMemcpyAsync(sim->eam_pot.brickList, lists.data(), lists.size() * sizeof(int), hipMemcpyHostToDevice, st));
-   HIP_CHECK(hipMemcpyAsync(sim->eam_pot.brickGroup, group.data(), group.size() * sizeof(int), hipMemcpyHostToDevice, st));
-   HIP_CHECK(hipStreamSynchronize(st));                      // (the vectors go out of scope; the other stream of the overlap mode reads the lists too)
-   sim->eam_pot.brickCount[0] = cnt[0]; sim->eam_pot.brickCount[1] = cnt[1]; sim->eam_pot.brickCountAll = cnt[2]; sim->eam_pot.brickListStride = stride;
-   sim->eam_pot.brickGroupBy = b.by; sim->eam_pot.brickGroupBz = b.bz;
-   sim->eam_pot.brickListMakes++;
-}
-
-// The bricks of the boundary and of the interior launch as lists, for the brick shape in `b` (built once per shape; eam_pot.brickGroup marks the cells for
-// kernels over cells).  Shared by cta_cell and thread_atom on the brick image.
-static void eamBrickGroupLists(SimGpu* sim, const EamBrickArgs& b, hipStream_t st)
-{
-   if (sim->eam_pot.brickGroup && sim->eam_pot.brickGroupBy == b.by && sim->eam_pot.brickGroupBz == b.bz) return;
-   if (!sim->eam_pot.brickGroup) sim->eam_pot.brickGroup = dalloc<int>((size_t)sim->boxes.nLocalBoxes, false);
-   if (!sim->eam_pot.cellSel) {
-      sim->eam_pot.cellSel = dalloc<int>((size_t)sim->boxes.nLocalBoxes, false);
-      HIP_CHECK(hipMemsetAsync(sim->eam_pot.cellSel, 0, (size_t)sim->boxes.nLocalBoxes * sizeof(int), st));
-   }
-   const int tag = ++sim->eam_pot.selTag;
-   const EamBrickArgs g = b;
-   if (sim->n_boundary_cells > 0)
-      hipLaunchKernelGGL(MarkCells, dim3(ceilDiv(sim->n_boundary_cells, 256)), dim3(256), 0, st, sim->boundary_cells, sim->n_boundary_cells, sim->eam_pot.cellSel, tag);
-   const int nBricks = b.geom.g[0] * b.nby * b.nbz;
-   if (sim->eam_pot.brickList) HIP_CHECK(hipFree(sim->eam_pot.brickList));
-   sim->eam_pot.brickList = dalloc<int>((size_t)2 * nBricks, false);
-   hipLaunchKernelGGL(ClassifyBrickCells, dim3(ceilDiv(nBricks, 256)), dim3(256), 0, st, g, sim->eam_pot.cellSel, tag, sim->eam_pot.brickGroup, sim->eam_pot.brickList);
-   // the bricks of either group as a list (built once; the other stream of the overlap mode reads groups and lists too, so wait here):
-   // [0, n1) the bricks that hold a boundary cell, [nBricks, nBricks + n2) the others, each in brick order
-   std::vector<int> cls((size_t)nBricks), lists((size_t)2 * nBricks, 0);
-   HIP_CHECK(hipMemcpyAsync(cls.data(), sim->eam_pot.brickList, (size_t)nBricks * sizeof(int), hipMemcpyDeviceToHost, st));
-   HIP_CHECK(hipStreamSynchronize(st));
-   int n1 = 0, n2 = 0;
-   for (int i = 0; i < nBricks; ++i) { if (cls[i] == 1) lists[n1++] = i; else lists[(size_t)nBricks + n2++] = i; }
-   HIP_CHECK(hipMemcpyAsync(sim->eam_pot.brickList, lists.data(), lists.size() * sizeof(int), hipMemcpyHostToDevice, st));
-   HIP_CHECK(hipStreamSynchronize(st));
-   sim->eam_pot.brickCount[0] = n1; sim->eam_pot.brickCount[1] = n2; sim->eam_pot.brickListStride = nBricks;
-   sim->eam_pot.brickGroupBy = b.by; sim->eam_pot.brickGroupBz = b.bz;
-}
-
-template <int STEP>
-static void launchEamBrick(SimGpu* sim, const EamArgs& a, int num_cells, int* cells_list, hipStream_t st, int spline, bool listed, int method)
-{
-   const size_t tableBytes = eamCtaTableBytes(STEP == 0 ? 1 : STEP, a.rho.n, a.phi.n);
-   const bool tablesInLds = STEP != 0 && !spline && tableBytes <= 32 * 1024;      // funcfl tables (500 samples) live in the LDS; setfl (10000) and spline coefficients stay in L2
-   const bool sameGrid = a.phi.n == a.rho.n && a.phi.x0 == a.rho.x0 && a.phi.invDx == a.rho.invDx;
-   size_t tableDoubles = 0;
-   if (tablesInLds) tableDoubles = STEP == 1 ? (size_t)2 * (a.rho.n + 3) + (sameGrid ? 0 : (a.phi.n + 3 - (a.rho.n + 3))) : (size_t)(a.rho.n + 3);
-   EamBrickArgs b;
-   eamBrickGeometry(sim, listed, &b);
-   const double lat = sim->latticeConstant > 0.0 ? sim->latticeConstant : 3.615;
-   if (!sim->eam_pot.brickImageCap) sim->eam_pot.brickImageCap = eamBrickSizeImage(sim, b, st, listed);
-   b.imageCap = sim->eam_pot.brickImageCap;
-   if (!sim->eam_pot.brickStats) sim->eam_pot.brickStats = dalloc<int>(2);
-   b.stats = sim->eam_pot.brickStats;
-   if (listed) {
-      NeighborListGpu* n = &sim->atoms.neighborList;
-      b.rows = n->brickRowLen; b.rowsG = n->brickRows; b.rowCountG = n->brickRowCount;
-      b.listRounds = n->brickRounds; b.listQuads = n->brickQuads;
-      const real_t rBuild = sim->eam_pot.cutoff + n->skinDistance;
-      b.rBuild2 = rBuild * rBuild;
-   } else {
-      // rows per atom: the cutoff sphere at that density + 50 %, a multiple of 8
-      const double rc = sim->eam_pot.cutoff;
-      int rows = ((int)(4.18879020478639 * rc * rc * rc * 4.0 / (lat * lat * lat) * 1.5) + 7) / 8 * 8;
-      if (rows < 32) rows = 32;
-      if (rows > 256) rows = 256;
-      const int lanesMin = (rows + 15) / 16, roundAtoms = 64 / lanesMin < 16 ? 64 / lanesMin : 16;      // (as the kernel derives them from `rows`)
-      const int rounds = (sim->maxAtoms + roundAtoms - 1) / roundAtoms;
-      if (!sim->eam_pot.pairRows) {                             // rows pass 1 leaves for pass 3: per (cell, round) [2 quads][64 lanes] 16-byte elements
-         const size_t slotsLocal = (size_t)sim->boxes.nLocalBoxes * sim->maxAtoms;
-         sim->eam_pot.pairRows = dalloc<unsigned>((size_t)sim->boxes.nLocalBoxes * rounds * 2 * 64 * 4, false);
-         sim->eam_pot.pairRowCount = dalloc<unsigned short>(slotsLocal, false);      // (written by pass 1 before pass 3 reads it; no zeroing that could race with that)
-         sim->eam_pot.pairRowLen = rows;
-      }
-      b.rows = sim->eam_pot.pairRowLen; b.rowsG = sim->eam_pot.pairRows; b.rowCountG = sim->eam_pot.pairRowCount;
-      b.listRounds = rounds; b.listQuads = 2;
-      if (!sim->eam_pot.brickSel) {      // (zeroed on the launch stream, like the cell marks below)
-         sim->eam_pot.brickSel = dalloc<unsigned long long>((size_t)sim->boxes.nLocalBoxes, false);
-         HIP_CHECK(hipMemsetAsync(sim->eam_pot.brickSel, 0, (size_t)sim->boxes.nLocalBoxes * sizeof(unsigned long long), st));
-      }
-      b.brickSel = sim->eam_pot.brickSel;
-   }
-   b.fuseEmbed = sim->fuseEmbed; b.status = sim->status;
-   { const char* e = getenv("COMD_EAM_ABLATE"); b.debug = e ? atoi(e) : 0; }
-   const int group = eamBrickGroupOf(sim, cells_list, num_cells, method);
-   if (listed) {           // the lists of the last list build (eamBrickBuildLists): all bricks, or the whole bricks of the boundary / interior launch
-      if (!sim->eam_pot.brickList) { fprintf(stderr, "eamForce: thread_atom_nl needs buildNeighborListGpu before the first force call\n"); exit(-1); }
-      b.brickList = sim->eam_pot.brickList + (size_t)(group ? group - 1 : 2) * sim->eam_pot.brickListStride;
-   }
-   if (group && !listed) {            // the boundary / interior launch of the overlap mode: whole bricks (a brick with cells of both lists would be staged twice per pass)
-      eamBrickGroupLists(sim, b, st);
-      // every cell of a listed brick is selected: no marks to look at (the embedding pass, a kernel over cells, uses brickGroup)
-      b.brickList = sim->eam_pot.brickList + (group == 1 ? 0 : sim->eam_pot.brickListStride);
-   } else if (cells_list && !group) {      // a launch over any other cell list: mark the cells, every brick looks at its own
-      if (!sim->eam_pot.cellSel) {
-         // zeroed ON THE LAUNCH STREAM: hipMemset returns before the device has finished, and the -a 1 streams are non-blocking -- a zeroing on
-         // the null stream can land after the marks of the first launch (seen once in four-rank runs: a first force evaluation that skipped cells)
-         sim->eam_pot.cellSel = dalloc<int>((size_t)sim->boxes.nLocalBoxes, false);
-         HIP_CHECK(hipMemsetAsync(sim->eam_pot.cellSel, 0, (size_t)sim->boxes.nLocalBoxes * sizeof(int), st));
-      }
-      b.sel = sim->eam_pot.cellSel; b.tag = ++sim->eam_pot.selTag;
-      ForceTimer aux(sim, st, 1);
-      hipLaunchKernelGGL(MarkCells, dim3(ceilDiv(num_cells, 256)), dim3(256), 0, st, cells_list, num_cells, sim->eam_pot.cellSel, b.tag);
-   }
-   const int waves = 4;     // EAM_Force_cta_brick is written for 256 threads: __launch_bounds__(256, 4), staging loops of STAGE x 256 tasks
-   if (listed && 3 * (b.by + 2) * (b.bz + 2) * 32 > EAM_BRICK_STAGE_LISTED * 64 * waves) { fprintf(stderr, "eamForce: a brick of 1 x %d x %d cells has more cells around it than a listed launch stages\n", b.by, b.bz); exit(-1); }
-   const size_t lds = eamBrickLdsBytes(STEP, listed, tableDoubles, b.imageCap, b.rows, waves);
-   if (lds > 160 * 1024) { fprintf(stderr, "eamForce: cta_cell needs %zu bytes of LDS for this box\n", lds); exit(-1); }
-   const int grid = group ? sim->eam_pot.brickCount[group - 1] : listed ? sim->eam_pot.brickCountAll : b.geom.g[0] * b.nby * b.nbz;
-   if (grid <= 0) return;
-   // the table clamps of interpolate() are dead weight when every pair the kernel evaluates lies inside the tables: 0 < r <= cutoff (rows hold pairs inside the cutoff;
-   // listed pairs are evaluated at min(r, cutoff)), tables from x0 <= 0 up to xn >= cutoff.  COMD_EAM_CLAMP=1 keeps them (A/B runs).
-   const double rcut = sim->eam_pot.cutoff * (1.0 + 4e-16);
-   const bool clampFree = !spline && a.phi.x0 <= R(0.0) && a.rho.x0 <= R(0.0) && rcut <= (double)a.phi.xn && rcut <= (double)a.rho.xn
-                          && !(getenv("COMD_EAM_CLAMP") && atoi(getenv("COMD_EAM_CLAMP")) != 0);
-#define COMD_LAUNCH_EAM_BRICK(STP, TAB, SPL, LST, CLP) do { \
-      allowDynamicLds((const void*)EAM_Force_cta_brick<STP, TAB, SPL, LST, CLP>, lds); \
-      hipLaunchKernelGGL((EAM_Force_cta_brick<STP, TAB, SPL, LST, CLP>), dim3(grid), dim3(64 * waves), lds, st, a, b); } while (0)
-#define COMD_LAUNCH_EAM_BRICK_C(STP, TAB, LST) do { if (clampFree) COMD_LAUNCH_EAM_BRICK(STP, TAB, false, LST, false); else COMD_LAUNCH_EAM_BRICK(STP, TAB, false, LST, true); } while (0)
-   if (STEP == 0)        COMD_LAUNCH_EAM_BRICK(0, false, false, true, true);
-   else if (listed) {
-      if (spline)           COMD_LAUNCH_EAM_BRICK((STEP == 0 ? 1 : STEP), false, true, true, true);
-      else if (tablesInLds) COMD_LAUNCH_EAM_BRICK_C((STEP == 0 ? 1 : STEP), true, true);
-      else                  COMD_LAUNCH_EAM_BRICK_C((STEP == 0 ? 1 : STEP), false, true);
-   } else {
-      if (spline)           COMD_LAUNCH_EAM_BRICK((STEP == 0 ? 1 : STEP), false, true, false, true);
-      else if (tablesInLds) COMD_LAUNCH_EAM_BRICK_C((STEP == 0 ? 1 : STEP), true, false);
-      else                  COMD_LAUNCH_EAM_BRICK_C((STEP == 0 ? 1 : STEP), false, false);
-   }
-#undef COMD_LAUNCH_EAM_BRICK_C
-#undef COMD_LAUNCH_EAM_BRICK
-   LAUNCH_CHECK();
-}
-
-template <int STEP>
-static void launchEamAtomBrick(SimGpu* sim, const EamArgs& a, int num_cells, int* cells_list, hipStream_t st, int spline)
-{
-   const size_t tableBytes = eamCtaTableBytes(STEP, a.rho.n, a.phi.n);
-   const bool tablesInLds = !spline && tableBytes <= 32 * 1024;
-   const bool sameGrid = a.phi.n == a.rho.n && a.phi.x0 == a.rho.x0 && a.phi.invDx == a.rho.invDx;
-   auto tableDoublesOf = [&](int step) -> size_t {
-      if (!tablesInLds) return 0;
-      return step == 1 ? (size_t)2 * (a.rho.n + 3) + (sameGrid ? 0 : (a.phi.n + 3 - (a.rho.n + 3))) : (size_t)(a.rho.n + 3);
-   };
-   const double lat = sim->latticeConstant > 0.0 ? sim->latticeConstant : 3.615;
-   const double rc = sim->eam_pot.cutoff;
-   // a row per thread (bytes: a neighbour is its offset inside its run of the image): the cutoff sphere at the lattice's density + 50 %, a multiple of 8 (an atom
-   // with more neighbours walks its stencil a second time); further down it gives up to a fifth of that when the LDS so freed buys a workgroup per CU in pass 1
-   const double inSphere = 4.18879020478639 * rc * rc * rc * 4.0 / (lat * lat * lat);
-   int rows = ((int)(inSphere * 1.5) + 7) / 8 * 8;
-   if (rows < 32) rows = 32;
-   if (rows > 128) rows = 128;
-   int rowsForced = 0;
-   { const char* e = getenv("COMD_EAM_ATOM_ROWS"); if (e && atoi(e) >= 8 && atoi(e) <= 128) rows = rowsForced = atoi(e) / 8 * 8; }      // tests: rows that overflow
-   EamBrickArgs b;
-   { const int by = sim->eam_pot.brickBy, bz = sim->eam_pot.brickBz; eamBrickGeometry(sim, false, &b); sim->eam_pot.brickBy = by; sim->eam_pot.brickBz = bz; }      // (the grid; the shape is this method's own)
-   const double perCell = 4.0 / (lat * lat * lat) / (sim->boxes.invBoxSize[0] * sim->boxes.invBoxSize[1] * sim->boxes.invBoxSize[2]);      // atoms of a cell at the lattice's density
-   // the threads that take atoms: whole waves for the brick's atoms + 8 % (a fuller brick's threads take a second atom)
-   auto rowThreadsOf = [&](double atoms) { int t = ((int)(atoms * 1.08) + 63) / 64 * 64; return t < 64 ? 64 : t > EAM_ATOM_BRICK_THREADS ? EAM_ATOM_BRICK_THREADS : t; };
-   // The brick: as many atoms as the workgroup has threads, the block within the 192 cells the staging covers, two workgroups per CU (80 KB of LDS each) in
-   // both passes.  Tried in this order; COMD_EAM_ATOM_BRICK="by,bz" overrides.  Fixed by the first launch, the image is sized again when bricks outgrow it.
-   const bool handOver = !(getenv("COMD_EAM_ATOM_HANDOVER") && atoi(getenv("COMD_EAM_ATOM_HANDOVER")) == 0) && rows <= 16 * EAM_ATOM_ROW_CHUNKS;
-   if (!sim->eam_pot.atomBrickBy || !sim->eam_pot.atomBrickImageCap) {
-      // (larger bricks stage fewer cells per atom and fill six waves -- and are slower: 1 x 5 x 5 1.39 ms, 1 x 4 x 6 1.42, 1 x 5 x 6 1.68 against 1.21 at 80^3; two large
-      //  workgroups per CU overlap one's staging with the other's arithmetic less than three small ones)
-      static const int shapes[][2] = { { 4, 4 }, { 4, 3 }, { 4, 2 }, { 2, 2 }, { 2, 1 }, { 1, 1 } };
-      int ey = 0, ez = 0;
-      { const char* e = getenv("COMD_EAM_ATOM_BRICK"); if (!(e && sscanf(e, "%d,%d", &ey, &ez) == 2 && ey >= 1 && ez >= 1 && 3 * (ey + 2) * (ez + 2) <= EAM_ATOM_MAX_CELLS && ey * ez <= 64)) ey = ez = 0; }
-      const int nShapes = (int)(sizeof shapes / sizeof shapes[0]);
-      for (int k = sim->eam_pot.atomBrickBy ? nShapes - 1 : 0; k < nShapes; ++k) {
-         if (sim->eam_pot.atomBrickBy) { b.by = sim->eam_pot.atomBrickBy; b.bz = sim->eam_pot.atomBrickBz; }      // (re-sizing: the shape stays)
-         else if (ey) { b.by = ey; b.bz = ez; }
-         else { b.by = shapes[k][0]; b.bz = shapes[k][1]; }
-         b.nby = ceilDiv(b.geom.g[1], b.by); b.nbz = ceilDiv(b.geom.g[2], b.bz);
-         const int cap = eamBrickSizeImage(sim, b, st, false);
-         const bool last = ey || sim->eam_pot.atomBrickBy || k == nShapes - 1;
-         const int rt = rowThreadsOf(perCell * b.by * b.bz);
-         const size_t lds1 = eamAtomBrickLdsBytes(1, tableDoublesOf(1), cap, rows, rt, true), lds3 = eamAtomBrickLdsBytes(3, tableDoublesOf(3), cap, rows, rt, !handOver);
-         if (last || (perCell * b.by * b.bz <= 1.05 * EAM_ATOM_BRICK_THREADS && lds1 <= 80 * 1024 && lds3 <= 80 * 1024)) {
-            sim->eam_pot.atomBrickBy = b.by; sim->eam_pot.atomBrickBz = b.bz; sim->eam_pot.atomBrickImageCap = cap;
-            break;
-         }
-      }
-   }
-   b.by = sim->eam_pot.atomBrickBy; b.bz = sim->eam_pot.atomBrickBz;
-   b.nby = ceilDiv(b.geom.g[1], b.by); b.nbz = ceilDiv(b.geom.g[2], b.bz);
-   b.imageCap = sim->eam_pot.atomBrickImageCap;
-   b.listRounds = rowThreadsOf(perCell * b.by * b.bz);      // (EAM_Force_atom_brick reads its row threads here)
-   auto perCu = [&](size_t bytes) { return bytes > 160 * 1024 ? 0 : (int)(160 * 1024 / (((bytes + 1279) / 1280) * 1280)); };      // (the LDS is handed out in 1280-byte granules)
-   if (!rowsForced) {
-      const int least = ((int)(inSphere * 1.2) + 7) / 8 * 8;
-      int best = rows, bestWgs = perCu(eamAtomBrickLdsBytes(1, tableDoublesOf(1), b.imageCap, rows, b.listRounds, true));
-      for (int r = rows - 8; r >= least && r >= 32; r -= 8) {
-         const int wgs = perCu(eamAtomBrickLdsBytes(1, tableDoublesOf(1), b.imageCap, r, b.listRounds, true));
-         if (wgs > bestWgs) { bestWgs = wgs; best = r; }
-      }
-      rows = best;
-   }
-   b.rows = rows;
-   if (!sim->eam_pot.brickStats) sim->eam_pot.brickStats = dalloc<int>(2);
-   b.stats = sim->eam_pot.brickStats;
-   b.fuseEmbed = sim->fuseEmbed; b.status = sim->status;
-   { const char* e = getenv("COMD_EAM_ABLATE"); b.debug = e ? atoi(e) : 0; }
-   // the rows pass 1 leaves for pass 3 (eam_atom_brick_kernels.h; COMD_EAM_ATOM_HANDOVER=0: pass 3 tests again, A/B runs)
-   const int rowCap = b.listRounds <= 192 ? 256 : 512;      // atoms of a brick that can leave a row (a brick fuller than that: its last atoms walk again in pass 3)
-   if (handOver && rows <= 16 * EAM_ATOM_ROW_CHUNKS) {
-      const size_t nBricks = (size_t)b.geom.g[0] * b.nby * b.nbz;
-      if (!sim->eam_pot.atomRows) {
-         sim->eam_pot.atomRows = dalloc<unsigned>(nBricks * EAM_ATOM_ROW_CHUNKS * rowCap * 4, false);
-         sim->eam_pot.atomRowCount = dalloc<unsigned short>(nBricks * rowCap * 2, false);      // (a 32-bit word per atom: the three runs' counts)
-         sim->eam_pot.atomBrickSel = dalloc<unsigned long long>((size_t)sim->boxes.nLocalBoxes, false);
-         HIP_CHECK(hipMemsetAsync(sim->eam_pot.atomBrickSel, 0, (size_t)sim->boxes.nLocalBoxes * sizeof(unsigned long long), st));
-      }
-      if (STEP == 1) sim->eam_pot.atomRowsValid = 1;
-      if (STEP == 1 || sim->eam_pot.atomRowsValid) { b.rowsG = sim->eam_pot.atomRows; b.rowCountG = sim->eam_pot.atomRowCount; b.brickSel = sim->eam_pot.atomBrickSel; }
-   }
-   const int group = eamBrickGroupOf(sim, cells_list, num_cells, THREAD_ATOM);
-   if (group) {      // the boundary / interior launch of the overlap mode: whole bricks, as cta_cell (a brick with cells of both lists would be staged twice per pass)
-      eamBrickGroupLists(sim, b, st);
-      b.brickList = sim->eam_pot.brickList + (group == 1 ? 0 : sim->eam_pot.brickListStride);
-   } else if (cells_list) {      // a launch over any other cell list: mark the cells, every brick looks at its own (zeroed on the launch stream, see launchEamBrick)
-      if (!sim->eam_pot.cellSel) {
-         sim->eam_pot.cellSel = dalloc<int>((size_t)sim->boxes.nLocalBoxes, false);
-         HIP_CHECK(hipMemsetAsync(sim->eam_pot.cellSel, 0, (size_t)sim->boxes.nLocalBoxes * sizeof(int), st));
-      }
-      b.sel = sim->eam_pot.cellSel; b.tag = ++sim->eam_pot.selTag;
-      ForceTimer aux(sim, st, 1);
-      hipLaunchKernelGGL(MarkCells, dim3(ceilDiv(num_cells, 256)), dim3(256), 0, st, cells_list, num_cells, sim->eam_pot.cellSel, b.tag);
-   }
-   // pass 3 keeps rows in the LDS only when it has none to read: what they would take is the third workgroup of a CU
-   b.listQuads = ((STEP == 3 && b.rowsG) ? 0 : 1) | (rowCap << 8);
-   size_t lds = eamAtomBrickLdsBytes(STEP, tableDoublesOf(STEP), b.imageCap, b.rows, b.listRounds, (b.listQuads & 1) != 0);
-   { const char* e = getenv("COMD_EAM_ATOM_LDS_PAD"); if (e) lds += (size_t)atoi(e); }      // experiments: fewer workgroups per CU
-   if (lds > 160 * 1024) { fprintf(stderr, "eamForce: thread_atom needs %zu bytes of LDS for this box\n", lds); exit(-1); }
-   const int grid = group ? sim->eam_pot.brickCount[group - 1] : b.geom.g[0] * b.nby * b.nbz;
-   if (grid <= 0) return;
-   // threads: the waves that take atoms, and enough to ask for the 16 first slots of every block cell in EAM_BRICK_STAGE rounds
-   const int nThreads = (b.listRounds > 256 || 3 * (b.by + 2) * (b.bz + 2) * 16 > EAM_BRICK_STAGE * 256) ? EAM_ATOM_BRICK_THREADS : 256;
-   const double rcut = sim->eam_pot.cutoff * (1.0 + 4e-16);      // (as launchEamBrick: the table clamps are dead weight when every evaluated pair lies inside the tables)
-   const bool clampFree = !spline && a.phi.x0 <= R(0.0) && a.rho.x0 <= R(0.0) && rcut <= (double)a.phi.xn && rcut <= (double)a.rho.xn
-                          && !(getenv("COMD_EAM_CLAMP") && atoi(getenv("COMD_EAM_CLAMP")) != 0);
-#define COMD_LAUNCH_EAM_ATOM_BRICK(TAB, SPL, CLP) do { \
-      allowDynamicLds((const void*)EAM_Force_atom_brick<STEP, TAB, SPL, CLP>, lds); \
-      hipLaunchKernelGGL((EAM_Force_atom_brick<STEP, TAB, SPL, CLP>), dim3(grid), dim3(nThreads), lds, st, a, b); } while (0)
-   if (spline)           COMD_LAUNCH_EAM_ATOM_BRICK(false, true, true);
-   else if (tablesInLds) { if (clampFree) COMD_LAUNCH_EAM_ATOM_BRICK(true, false, false); else COMD_LAUNCH_EAM_ATOM_BRICK(true, false, true); }
-   else                  { if (clampFree) COMD_LAUNCH_EAM_ATOM_BRICK(false, false, false); else COMD_LAUNCH_EAM_ATOM_BRICK(false, false, true); }
-#undef COMD_LAUNCH_EAM_ATOM_BRICK
-   LAUNCH_CHECK();
-}
-
-// cta_cell: size the brick image again at the next launch (between two force evaluations only: pass 1 and pass 3 of one evaluation must stage alike)
-extern "C" void comdEamBrickResize(SimGpu* sim) { sim->eam_pot.brickImageCap = 0; sim->eam_pot.atomBrickImageCap = 0; }
+#include "eam_launch.h"      // the EAM launch layer: makeEamArgs ... eamForce3Gpu
 
 // what the force wrappers decided for this simulation (bench.py records it beside the numbers): {LJ thread_atom candidate lists in use (0: the 27-cell walk),
 // records of the EAM brick image, Verlet-list format (comd_hip.h slabFormat), cells per EAM brick}
@@ -1340,154 +938,6 @@ extern "C" void comdForcePathInfo(SimGpu* sim, int out[4])
    out[2] = sim->atoms.neighborList.slabFormat;
    out[3] = (sim->eam_pot.brickBy ? sim->eam_pot.brickBy * sim->eam_pot.brickBz : sim->eam_pot.atomBrickBy * sim->eam_pot.atomBrickBz) + 256 * sim->eam_pot.brickListMakes;      // (cells per brick in the low byte, times the brick lists were made above)
 }
-
-extern "C" void comdEamBrickStats(SimGpu* sim, int out[3])
-{
-   out[0] = out[1] = out[2] = 0;
-   if (!sim->eam_pot.brickStats) return;
-   int h[2];
-   HIP_CHECK(hipDeviceSynchronize());
-   HIP_CHECK(hipMemcpy(h, sim->eam_pot.brickStats, sizeof h, hipMemcpyDeviceToHost));
-   HIP_CHECK(hipMemset(sim->eam_pot.brickStats + 1, 0, sizeof(int)));
-   const bool atomBrick = !sim->eam_pot.brickBy && sim->eam_pot.atomBrickBy;      // (thread_atom on the brick image: its shape, its image)
-   int by = atomBrick ? sim->eam_pot.atomBrickBy : sim->eam_pot.brickBy ? sim->eam_pot.brickBy : 4, bz = atomBrick ? sim->eam_pot.atomBrickBz : sim->eam_pot.brickBz ? sim->eam_pot.brickBz : 2;
-   out[0] = h[1]; out[1] = sim->boxes.gridSize[0] * ceilDiv(sim->boxes.gridSize[1], by) * ceilDiv(sim->boxes.gridSize[2], bz);
-   out[2] = atomBrick ? sim->eam_pot.atomBrickImageCap : sim->eam_pot.brickImageCap;
-}
-
-template <int STEP>
-static void launchEamPair(SimGpu* sim, int num_cells, int* cells_list, int method, hipStream_t st, int spline)
-{
-   if (num_cells <= 0) return;
-   EamArgs a = makeEamArgs(sim, num_cells, cells_list);
-   ForceTimer timer(sim, st);
-   if (spline) {
-      // -P (gpu_kernels.cu:164-226): cubic splines in r^2 for phi and rho, coefficient tables read through L2 (16 KB each for funcfl)
-      if (!a.phiS.coefficients || !a.rhoS.coefficients) { fprintf(stderr, "eamForce: spline != 0 but no spline tables were given to AllocateGpu\n"); exit(-1); }
-      if ((method == THREAD_ATOM || method == WARP_ATOM) && !eamAtomBrickPath(sim, method)) {
-         launchEamThreadAtom<STEP>(sim, a, num_cells, st, true);
-         return;
-      }
-   }
-   if (eamAtomBrickPath(sim, method)) {
-      launchEamAtomBrick<STEP>(sim, a, num_cells, cells_list, st, spline);
-      return;
-   }
-   if (STEP == 1) sim->eam_pot.atomRowsValid = 0;      // (another method's pass 1: the rows EAM_Force_atom_brick left are not this evaluation's)
-   if (eamListedBrick(sim, method)) {
-      if (sim->atoms.neighborList.nBuilds == 0) { fprintf(stderr, "the *_nl methods need buildNeighborListGpu before the first force call\n"); exit(-1); }
-      launchEamBrick<STEP>(sim, a, num_cells, cells_list, st, spline, true, method);
-      return;
-   } else if ((method == THREAD_ATOM_NL || method == WARP_ATOM_NL) && sim->atoms.neighborList.slabFormat == 2) {
-      NeighborListGpu* n = &sim->atoms.neighborList;
-      (void)nlView(sim);
-      NlSlabView v; v.list = n->list16; v.count = n->nNeighbors; v.rows = n->slabRows;
-      const bool sameGrid = a.phi.n == a.rho.n && a.phi.x0 == a.rho.x0 && a.phi.invDx == a.rho.invDx;
-      const size_t lds = eamNlLdsBytes(STEP, a.rho.n, a.phi.n, sameGrid, n->maxSlabAtoms, spline != 0);
-      if (lds > 160 * 1024) { fprintf(stderr, "eamForce: %d atoms in a 27-cell stencil do not fit the LDS\n", n->maxSlabAtoms); exit(-1); }
-      const int grid = ceilDiv(num_cells, EAM_NL_WAVES * 8);        // each wave walks ~8 consecutive cells
-      if (spline) {
-         allowDynamicLds((const void*)EAM_Force_nl_lds<STEP, true>, lds);
-         hipLaunchKernelGGL((EAM_Force_nl_lds<STEP, true>), dim3(grid), dim3(64 * EAM_NL_WAVES), lds, st, a, v, n->maxSlabAtoms);
-      } else {
-         allowDynamicLds((const void*)EAM_Force_nl_lds<STEP, false>, lds);
-         hipLaunchKernelGGL((EAM_Force_nl_lds<STEP, false>), dim3(grid), dim3(64 * EAM_NL_WAVES), lds, st, a, v, n->maxSlabAtoms);
-      }
-   } else if (method == THREAD_ATOM_NL || method == WARP_ATOM_NL) {
-      const NlView nl = nlView(sim);
-      const size_t tableBytes = eamCtaTableBytes(STEP, a.rho.n, a.phi.n);
-      const unsigned nBlocks = (unsigned)ceilDiv((long)num_cells * sim->maxAtoms, 256);
-      if (spline)                       hipLaunchKernelGGL((EAM_Force_thread_atom_nl<STEP, false, true>), dim3(nBlocks), dim3(256), 0, st, a, nl);
-      else if (tableBytes <= 32 * 1024) hipLaunchKernelGGL((EAM_Force_thread_atom_nl<STEP, true, false>), dim3(nBlocks), dim3(256), tableBytes, st, a, nl);
-      else                              hipLaunchKernelGGL((EAM_Force_thread_atom_nl<STEP, false, false>), dim3(nBlocks), dim3(256), 0, st, a, nl);
-   } else if (eamBrickPath(sim, method)) {
-      launchEamBrick<STEP>(sim, a, num_cells, cells_list, st, spline, false, method);
-      return;
-   } else if (method == CTA_CELL) {
-      // COMD_EAM_CTA=cell: round 2's form, a wave stages the stencil of every cell for itself (nl_kernels.h EAM_Force_cta_cell); kept for A/B runs
-      const size_t tableBytes = eamCtaTableBytes(STEP, a.rho.n, a.phi.n);
-      const bool tablesInLds = !spline && tableBytes <= 32 * 1024;      // funcfl tables (500 samples) live in the LDS; setfl (10000) and spline coefficients stay in L2
-      const bool sameGrid = a.phi.n == a.rho.n && a.phi.x0 == a.rho.x0 && a.phi.invDx == a.rho.invDx;
-      // a stencil of 27 cells at the perfect-lattice density + 30 % (thermal crowding, cells fuller than the mean), whole staging rounds of 64
-      const double cellVol = 1.0 / (sim->boxes.invBoxSize[0] * sim->boxes.invBoxSize[1] * sim->boxes.invBoxSize[2]);
-      const double lat = sim->latticeConstant > 0.0 ? sim->latticeConstant : 3.615;
-      const double perStencil = 27.0 * cellVol * 4.0 / (lat * lat * lat);
-      int stencil = (((int)(perStencil * 1.30) + 16 + 7) / 8) * 8;
-      if (stencil < 128) stencil = 128;
-      if (stencil > 27 * sim->maxAtoms) stencil = ((27 * sim->maxAtoms + 7) / 8) * 8;
-      if (stencil > 1024) stencil = 1024;                    // beyond that a cell takes the thread-per-atom form inside the same kernel
-      // rows per atom: the cutoff sphere at that density + 50 %, a multiple of 8
-      const double rc = sim->eam_pot.cutoff;
-      int rows = ((int)(4.18879020478639 * rc * rc * rc * 4.0 / (lat * lat * lat) * 1.5) + 7) / 8 * 8;
-      if (rows < 32) rows = 32;
-      // 4 waves per workgroup, one per SIMD (5 or 6 land unevenly on the four SIMDs of a CU: measured 3.4-3.7 ms against 2.6 at 80^3)
-      int waves = 4;
-      { const char* e = getenv("COMD_EAM_CTA_WAVES"); if (e && atoi(e) >= 1 && atoi(e) <= 8) waves = atoi(e); }
-      if (rows > 256) rows = 256;                            // the hand-over holds 16 lanes x 8 trips x 2 numbers per atom
-      if (!sim->eam_pot.pairRows) {                          // first cta_cell launch: rows pass 1 leaves for pass 3
-         const size_t slotsLocal = (size_t)sim->boxes.nLocalBoxes * sim->maxAtoms;
-         sim->eam_pot.pairRows = dalloc<unsigned>(slotsLocal * EAM_ROW_WORDS, false);
-         sim->eam_pot.pairRowCount = dalloc<unsigned short>(slotsLocal, false);
-         sim->eam_pot.pairRowLen = rows;
-      }
-      // The LDS slice decides how many workgroups share a CU (gfx950 hands the LDS out in 1280-byte granules, 160 KB per CU), and these kernels
-      // live on latency hiding: at 80^3 a slice of 384 records leaves room for two workgroups per CU in either pass, one of 376 for three
-      // (measured: pass 1 1.43 -> 1.08 ms).  Shrink the slice, down to the density + 20 %, when that buys a workgroup in pass 1 or pass 3;
-      // both passes must use the same size (a cell either has rows or takes the thread-per-atom form, in both).
-      {
-         auto perCu = [&](int step, int st) {
-            const size_t b = eamCtaCellLdsBytes(step, a.rho.n, a.phi.n, tablesInLds, sameGrid, st, rows, waves);
-            return b > 160 * 1024 ? 0 : (int)(160 * 1024 / (((b + 1279) / 1280) * 1280));
-         };
-         const int lo = (((int)(perStencil * 1.20) + 16 + 7) / 8) * 8;
-         int best = stencil, bestScore = perCu(1, stencil) + perCu(3, stencil);
-         for (int st = stencil - 8; st >= lo && st >= 128; st -= 8) {
-            const int score = perCu(1, st) + perCu(3, st);
-            if (score > bestScore) { bestScore = score; best = st; }
-         }
-         stencil = best;
-      }
-      { const char* e = getenv("COMD_EAM_STENCIL"); if (e && atoi(e) >= 64) stencil = (atoi(e) + 7) / 8 * 8; }      // experiments: LDS slice size
-      const size_t lds = eamCtaCellLdsBytes(STEP, a.rho.n, a.phi.n, tablesInLds, sameGrid, stencil, rows, waves);
-      if (lds > 160 * 1024) { fprintf(stderr, "eamForce: cta_cell needs %zu bytes of LDS for this box\n", lds); exit(-1); }
-      const int grid = ceilDiv(num_cells, waves * 8);        // each wave walks ~8 consecutive cells
-#define COMD_LAUNCH_EAM_CTA(TAB, SPL) do { \
-         allowDynamicLds((const void*)EAM_Force_cta_cell<STEP, TAB, SPL>, lds); \
-         hipLaunchKernelGGL((EAM_Force_cta_cell<STEP, TAB, SPL>), dim3(grid), dim3(64 * waves), lds, st, a, stencil, rows, sim->eam_pot.pairRows, sim->eam_pot.pairRowCount, sim->fuseEmbed, sim->status); } while (0)
-      if (spline)           COMD_LAUNCH_EAM_CTA(false, true);
-      else if (tablesInLds) COMD_LAUNCH_EAM_CTA(true, false);
-      else                  COMD_LAUNCH_EAM_CTA(false, false);
-#undef COMD_LAUNCH_EAM_CTA
-   } else {
-      launchEamThreadAtom<STEP>(sim, a, num_cells, st, false);
-      return;
-   }
-   LAUNCH_CHECK();
-}
-
-extern "C" void eamForce1GpuAsync(SimGpu* sim, int num_cells, int* cells_list, int method, comdStream_t stream, int spline)
-{ launchEamPair<1>(sim, num_cells, cells_list, method, S(stream), spline); }
-
-extern "C" void eamForce2GpuAsync(SimGpu* sim, int num_cells, int* cells_list, int method, comdStream_t stream, int spline)
-{
-   (void)spline;                            /* F(rhobar) is quadratic in both modes (gpu_utility.c:443) */
-   if (num_cells <= 0) return;
-   if (sim->fuseEmbed && (method == CTA_CELL || eamListedBrick(sim, method) || eamAtomBrickPath(sim, method))) return;      /* eamForce1Gpu[Async] has done it for these cells (SimGpu.fuseEmbed) */
-   EamArgs a = makeEamArgs(sim, num_cells, cells_list);
-   // cta_cell in the overlap mode: pass 1 took whole bricks (launchEamBrick), the embedding follows the same groups over all local cells
-   const int group = sim->eam_pot.brickGroup ? eamBrickGroupOf(sim, cells_list, num_cells, method) : 0;
-   if (group) { a.cells = nullptr; a.nCells = num_cells = sim->boxes.nLocalBoxes; a.sel = sim->eam_pot.brickGroup; a.tag = group; }
-   ForceTimer timer(sim, S(stream));
-   hipLaunchKernelGGL(EAM_Force_embed, dim3(ceilDiv((long)num_cells * sim->maxAtoms, 256)), dim3(256), 0, S(stream), a);
-   LAUNCH_CHECK();
-}
-
-extern "C" void eamForce3GpuAsync(SimGpu* sim, int num_cells, int* cells_list, int method, comdStream_t stream, int spline)
-{ launchEamPair<3>(sim, num_cells, cells_list, method, S(stream), spline); }
-
-extern "C" void eamForce1Gpu(SimGpu* sim, int method, int spline) { eamForce1GpuAsync(sim, sim->boxes.nLocalBoxes, nullptr, method, nullptr, spline); }
-extern "C" void eamForce2Gpu(SimGpu* sim, int method, int spline) { eamForce2GpuAsync(sim, sim->boxes.nLocalBoxes, nullptr, method, nullptr, spline); }
-extern "C" void eamForce3Gpu(SimGpu* sim, int method, int spline) { eamForce3GpuAsync(sim, sim->boxes.nLocalBoxes, nullptr, method, nullptr, spline); }
 
 extern "C" void updateNeighborsGpu(SimGpu*, int*) {}
 extern "C" void updateNeighborsGpuAsync(SimGpu*, int*, int, int*, comdStream_t) {}
@@ -1909,8 +1359,7 @@ extern "C" int neighborListUpdateRequiredGpu(SimGpu* sim)
 extern "C" int comdNeighborListUpdateDeferredGpu(SimGpu* sim)
 {
    NeighborListGpu* n = &sim->atoms.neighborList;
-   const char* envSync = getenv("COMD_NL_SYNC");
-   const bool forceSync = envSync && atoi(envSync) != 0;
+   const bool forceSync = tuningOf(sim).nlSync;
    if (forceSync || !n->checkFused || n->forceRebuildFlag || n->lastInterval <= 0 || n->softHalf2 <= R(0.0)) return neighborListUpdateRequiredGpu(sim);
    n->checkFused = 0;
    const int G = n->driftCount, k = G - n->buildDrift;       // drift kernels so far, since the build
@@ -1959,7 +1408,7 @@ static void buildNeighborListImpl(SimGpu* sim, int method, int boundaryFlag)
          HIP_CHECK(hipEventSynchronize((hipEvent_t)n->brickStatsEvent));      // recorded a whole list life ago
          if (n->brickStatsMirror[1] > 0) sim->eam_pot.brickListsValid = 0;
       }
-      if (getenv("COMD_EAM_LISTS_EVERY_BUILD")) sim->eam_pot.brickListsValid = 0;      // (A/B runs, tests)
+      if (tuningOf(sim).eamListsEveryBuild) sim->eam_pot.brickListsValid = 0;      // (A/B runs, tests)
       if (!sim->eam_pot.brickListsValid) {
          eamBrickBuildLists(sim, st, sim->eam_pot.phiS.coefficients != nullptr);      // (sizes the image as well)
          sim->eam_pot.brickListsValid = 1;
@@ -1967,7 +1416,8 @@ static void buildNeighborListImpl(SimGpu* sim, int method, int boundaryFlag)
       EamArgs a = makeEamArgs(sim, sim->boxes.nLocalBoxes, nullptr);
       if (!sim->eam_pot.brickStats) sim->eam_pot.brickStats = dalloc<int>(2);
       HIP_CHECK(hipMemsetAsync(sim->eam_pot.brickStats, 0, 2 * sizeof(int), st));
-      launchEamBrick<0>(sim, a, sim->boxes.nLocalBoxes, nullptr, st, 0, true, THREAD_ATOM_NL);
+      launchEamBrick<0>(sim, a, sim->boxes.nLocalBoxes, nullptr, st, EamTablePlan(a.phi, a.rho, 0), true, THREAD_ATOM_NL);
+      LAUNCH_CHECK();
       HIP_CHECK(hipMemcpyAsync(n->brickStatsMirror, sim->eam_pot.brickStats, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
       if (!n->brickStatsEvent) { hipEvent_t e; HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); n->brickStatsEvent = (void*)e; }
       HIP_CHECK(hipEventRecord((hipEvent_t)n->brickStatsEvent, st));
@@ -2014,7 +1464,7 @@ static void buildNeighborListImpl(SimGpu* sim, int method, int boundaryFlag)
          // COMD_NL_BANK_ORDER=1: rows ordered by LDS bank class (nl_kernels.h): 2 x 16 counters of 16 bits per thread behind the records.  An experiment that settled a
          // question (profiles/r04_experiments/README.md): it takes 45 % of the bank-conflict cycles out of LJ_Force_nl_slabs and 1.3 % of its time -- the kernel is bound by
          // VALU issue, not by the LDS -- while the build goes from 11 to 79 ms.  Off by default.
-         const int bankOrder = getenv("COMD_NL_BANK_ORDER") && atoi(getenv("COMD_NL_BANK_ORDER")) != 0;
+         const int bankOrder = tuningOf(sim).nlBankOrder;
          const int groupCap = NL_GROUP_CELLS * sim->maxAtoms;
          const size_t lds = (size_t)3 * groupCap * sizeof(real_t) + (bankOrder ? (size_t)2 * 16 * sim->maxAtoms * sizeof(unsigned short) : 0);
          allowDynamicLds((const void*)BuildNeighborListSlabs, lds);
@@ -2052,7 +1502,7 @@ extern "C" void buildNeighborListGpu(SimGpu* sim, int method, int boundaryFlag)
    double frac = n->lastInterval > 0 ? 4.0 / n->lastInterval : 0.0;      // two steps' worth of twice the average growth per step
    if (frac < 0.1) frac = 0.1;
    if (frac > 0.6) frac = 0.6;
-   { const char* e = getenv("COMD_NL_MARGIN"); if (e && atof(e) >= 0.0 && atof(e) < 1.0) frac = atof(e); }      // tests: force the stop
+   if (tuningOf(sim).nlMargin >= 0.0) frac = tuningOf(sim).nlMargin;      // tests: force the stop
    n->softHalf2 = n->lastInterval > 0 ? (real_t)((1.0 - frac) * (1.0 - frac)) * n->skinDistanceHalf2 : R(0.0);
 }
 

@@ -217,6 +217,7 @@ typedef struct SimGpuSt {
    int          msgBoundAtoms;         /* > 0: load{Force,Position}BufferFromGpu flag status[2] when the listed cells hold more atoms than this
                                         * (the size both ends of a halo message agreed on beforehand, see CommTransport.sendrecv2sized) */
    void*        timing;                /* comdForceTiming*: event pool of this simulation, NULL = off */
+   void*        tuning;                /* private to the device library: the COMD_* environment variables as AllocateGpu found them (hip/comd_device.hip ComdTuning) */
    real_t       latticeConstant;       /* GpuConfig.latticeConstant (0: 3.615): density estimate behind the LDS sizing of the cell kernels */
    int          fuseEmbed;             /* host switch, default 0: with method CTA_CELL (and the list method on brick rows, and THREAD_ATOM on the brick image) eamForce1Gpu[Async] also does the work of eamForce2Gpu[Async] for the
                                         * cells it covers (F(rhobar), F'(rhobar) need nothing but the atom's own rhobar) and eamForce2Gpu[Async] returns at

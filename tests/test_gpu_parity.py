@@ -150,7 +150,7 @@ def test_lj_wave_candidate_lists_and_their_fallbacks(gpu, orc, monkeypatch, env)
 def test_eam_overlap_mode_takes_whole_bricks(gpu, orc, monkeypatch, env):
     """-a 1 launches every EAM pass once over the boundary cells and once over the interior cells.  cta_cell makes that split at brick
     granularity (every cell of a brick that holds a boundary cell goes with the boundary launch: no brick is staged twice per pass;
-    comd_device.hip eamBrickGroupOf).  Forces, energies, densities and dF/drho after three steps must be the oracle's -- with the groups,
+    eam_launch.h eamBrickGroupOf).  Forces, energies, densities and dF/drho after three steps must be the oracle's -- with the groups,
     with the lists taken cell by cell (COMD_EAM_GROUPS=0), and with a brick shape that does not divide the grid."""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
