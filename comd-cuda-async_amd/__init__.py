@@ -129,6 +129,12 @@ def lib_host():
         lib.comdLjTable.restype = ctypes.c_int
         lib.comdEamTable.restype = ctypes.c_int
         lib.comdVirial.argtypes = [vp, c_double_p]
+        lib.comdPairHistogram.argtypes = [vp, ctypes.c_int, ctypes.c_double, c_double_p]
+        lib.comdPairHistogram.restype = ctypes.c_int
+        lib.comdCutoff.argtypes = [vp]
+        lib.comdCutoff.restype = ctypes.c_double
+        lib.comdVolume.argtypes = [vp]
+        lib.comdVolume.restype = ctypes.c_double
         lib.comdSetLangevin.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_int]
         lib.comdSetLangevin.restype = ctypes.c_int
         lib.comdGetLangevin.argtypes = [vp, c_double_p, ctypes.POINTER(ctypes.c_uint64)]
@@ -224,6 +230,14 @@ def rccl_unique_id():
     if lib_hip().comdCommGetUniqueId(buf) != 0:
         raise RuntimeError("comdCommGetUniqueId failed")
     return buf.raw
+
+
+def _whole_pairs(np, halved):
+    """int64 pair counts from comdPairHistogram's halved ordered counts.  A pair whose two sides (it is seen once from either atom, across a
+    periodic face against a shifted image) round to different sides of a bin edge leaves a half in each of two neighbouring bins.  The
+    cumulative sums are floored, which moves each such pair whole into the upper of its two bins: the total is exact and no pair is lost."""
+    below = np.floor(np.concatenate([[0.0], np.cumsum(halved)]))      # multiples of 1/2 below 2^53: the sums are exact
+    return np.diff(below).astype(np.int64)
 
 
 class Simulation:
@@ -371,6 +385,35 @@ class Simulation:
     def pressure(self):
         """trace(pressure_tensor()) / 3 in eV/A^3."""
         return float(self._np.trace(self.pressure_tensor())) / 3.0
+
+    # --- structure (not in the reference: comd-hip --rdf, --rdfMax, --rdfFile) ---
+    @property
+    def cutoff(self):
+        """The force cutoff of the potential in use, in Angstroms."""
+        return self.lib.comdCutoff(self.ptr)
+
+    def pair_histogram(self, n_bins, r_max=None):
+        """(edges float64[n_bins + 1], counts int64[n_bins]): the global number of unordered pairs of the current state in n_bins uniform bins
+        [k dr, (k + 1) dr) up to r_max Angstroms (None: the force cutoff, which is also the most it can be); 1 <= n_bins <= 4096.  Counted on the
+        device by computePairHistogram, summed over the ranks (every rank gets the global result); valid whenever virial() is."""
+        np = self._np
+        n_bins = int(n_bins)
+        out = np.zeros(max(n_bins, 1), dtype=np.float64)
+        # r_max <= 0 means "the cutoff" to comdPairHistogram: refuse it here, before anything is launched
+        if (r_max is not None and not r_max > 0.0) \
+                or self.lib.comdPairHistogram(self.ptr, n_bins, 0.0 if r_max is None else float(r_max), out.ctypes.data_as(c_double_p)) != 0:
+            raise ValueError(f"pair_histogram: need 1 <= n_bins <= 4096 and 0 < r_max <= the force cutoff {self.cutoff} (got {n_bins}, {r_max})")
+        edges = np.arange(n_bins + 1, dtype=np.float64) * ((self.cutoff if r_max is None else float(r_max)) / n_bins)
+        return edges, _whole_pairs(np, out)
+
+    def rdf(self, n_bins, r_max=None):
+        """(r_centres, g): the radial distribution function g_k = counts_k / ((N/2) (N/V) (4 pi/3) ((k + 1)^3 - k^3) dr^3) of pair_histogram's bins."""
+        np = self._np
+        edges, counts = self.pair_histogram(n_bins, r_max)
+        n, dr = float(self.n_global), edges[-1] / n_bins
+        k = np.arange(n_bins, dtype=np.float64)
+        ideal = (0.5 * n) * (n / self.lib.comdVolume(self.ptr)) * (4.0 * np.pi / 3.0 * dr * dr * dr) * ((k + 1.0) ** 3 - k ** 3)
+        return 0.5 * (edges[:-1] + edges[1:]), counts / ideal
 
     @property
     def n_global(self):

@@ -21,6 +21,7 @@
 #include "eam_brick_kernels.h"
 #include "eam_atom_brick_kernels.h"
 #include "virial_kernels.h"
+#include "rdf_kernels.h"
 #include "langevin_kernels.h"
 
 static int g_rank = 0;
@@ -588,7 +589,7 @@ extern "C" void DestroyGpu(SimGpu* sim)
                     sim->boxes.boxIDLookUp, sim->boxes.boxIDLookUpReverse, sim->eam_pot.phiS.coefficients, sim->eam_pot.rhoS.coefficients,
                     sim->eam_pot.pairRows, sim->eam_pot.pairRowCount, sim->eam_pot.cellSel, sim->eam_pot.brickGroup, sim->eam_pot.brickList, sim->eam_pot.brickSel, sim->eam_pot.brickStats, sim->eam_pot.atomRows, sim->eam_pot.atomRowCount, sim->eam_pot.atomBrickSel,
                     sim->atoms.neighborList.brickRows, sim->atoms.neighborList.brickRowCount, sim->adapterScan, sim->lj_pot.waveCand, sim->lj_pot.waveCandCount, sim->lj_pot.packedR[0], sim->lj_pot.packedR[1], sim->lj_pot.packedF[0], sim->lj_pot.packedF[1],
-                    sim->lj_pot.lj_interpolation.values, sim->virialBuf };
+                    sim->lj_pot.lj_interpolation.values, sim->virialBuf, sim->pairHistBuf };
    for (void* p : ptrs) if (p) HIP_CHECK(hipFree(p));
    if (sim->statusEvent) (void)hipEventDestroy((hipEvent_t)sim->statusEvent);
    if (sim->pinned) HIP_CHECK(hipHostFree(sim->pinned));
@@ -1095,6 +1096,36 @@ extern "C" void computeVirial(SimGpu* sim, real_t* out12)
    HIP_CHECK(hipMemcpyAsync(h, out, sizeof h, hipMemcpyDeviceToHost, st));
    HIP_CHECK(hipStreamSynchronize(st));
    for (int c = 0; c < VIRIAL_N; ++c) out12[c] = (real_t)h[c];
+}
+
+// Not in the reference: the pair-distance histogram (rdf_kernels.h).  One instance for every potential and method: it reads positions and cells only
+extern "C" void computePairHistogram(SimGpu* sim, int nBins, real_t rMax, uint64_t* outCounts)
+{
+   hipStream_t st = S(sim->boundary_stream);
+   if (sim->interior_stream) HIP_CHECK(hipStreamSynchronize(S(sim->interior_stream)));      // -a 1: the interior cells' force work is done
+   if (nBins < 1 || nBins > PAIRHIST_MAX_BINS) { fprintf(stderr, "computePairHistogram: %d bins (1..%d)\n", nBins, PAIRHIST_MAX_BINS); exit(-1); }
+   if (nBins > sim->pairHistCap) {
+      if (sim->pairHistBuf) { HIP_CHECK(hipStreamSynchronize(st)); HIP_CHECK(hipFree(sim->pairHistBuf)); }
+      sim->pairHistBuf = dalloc<unsigned long long>((size_t)nBins, false);
+      sim->pairHistCap = nBins;
+   }
+   PairHistArgs v;
+   v.rx = sim->atoms.r.x; v.ry = sim->atoms.r.y; v.rz = sim->atoms.r.z;
+   v.nAtoms = sim->boxes.nAtoms; v.nbr = sim->neighbor_cells;
+   v.nLocalBoxes = sim->boxes.nLocalBoxes; v.cap = sim->maxAtoms; v.chunks = ceilDiv(sim->maxAtoms, WAVE);
+   v.nBins = nBins; v.rMax2 = rMax * rMax; v.invDr = (real_t)nBins / rMax;
+   v.counts = sim->pairHistBuf;
+   const size_t lds = (size_t)4 * nBins * sizeof(unsigned);      // one copy per wave
+   // what a workgroup can add to one 32-bit LDS counter stays below 2^32 (rdf_kernels.h); the grid does not show in a sum of integers
+   const long nWork = (long)v.nLocalBoxes * v.chunks;
+   int grid = PAIRHIST_BLOCKS;
+   while ((double)((nWork + grid - 1) / grid) * WAVE * 27.0 * v.cap >= 4.0e9) grid *= 2;
+   allowDynamicLds((const void*)PairHist_thread_atom, lds);
+   HIP_CHECK(hipMemsetAsync(sim->pairHistBuf, 0, (size_t)nBins * sizeof(unsigned long long), st));
+   hipLaunchKernelGGL(PairHist_thread_atom, dim3(grid), dim3(256), lds, st, v);
+   LAUNCH_CHECK();
+   HIP_CHECK(hipMemcpyAsync(outCounts, sim->pairHistBuf, (size_t)nBins * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
 }
 
 // ---- redistribute ---------------------------------------------------------------------------------------------------

@@ -5,7 +5,9 @@
  * MAXNEIGHBORLISTSIZE), --quiet, --ljCutoffSigmas F (the reference hard-wires 5; 2.5 meets its documented LJ cohesive energy),
  * --deviceTimers (also COMD_DEVICE_TIMERS=1: HIP-event timing of the phases in the reference's timer table),
  * --pressure (a Pressure(GPa) column in the report: pair virial + kinetic tensor, which the reference does not compute),
- * --langevin, --langevinTemp K, --langevinDamp FS, --seed N (BAOAB Langevin thermostat; the reference integrates NVE only). */
+ * --langevin, --langevinTemp K, --langevinDamp FS, --seed N (BAOAB Langevin thermostat; the reference integrates NVE only),
+ * --rdf N, --rdfMax R, --rdfFile PATH (radial distribution function g(r) from a pair histogram of N bins up to R Angstroms, sampled at every
+ * printed step and written to PATH; the reference has no structural analysis). */
 #include "comd_host.h"
 #include <getopt.h>
 #include <math.h>
@@ -38,6 +40,7 @@ Command parseCommandLine(int argc, char** argv)
    cmd.ljCutoffSigmas = 5.0;
    cmd.dt = 1.0; cmd.lat = -1.0; cmd.temperature = 600.0; cmd.initialDelta = 0.0; cmd.relativeSkinDistance = 0.1;
    cmd.langevinTemp = NAN; cmd.langevinDamp = COMD_LANGEVIN_DAMP; cmd.seed = COMD_LANGEVIN_SEED;
+   strcpy(cmd.rdfFile, "rdf.dat");
    int help = 0;
 
    const ArgDef defs[] = {
@@ -76,6 +79,9 @@ Command parseCommandLine(int argc, char** argv)
       { "langevinTemp",  0,  1, 'd', &cmd.langevinTemp,   0, "Langevin target temperature (K; default: the -T value)" },
       { "langevinDamp",  0,  1, 'd', &cmd.langevinDamp,   0, "Langevin damping time tau (fs; default 100)" },
       { "seed",          0,  1, 'u', &cmd.seed,           0, "key of the Langevin noise (Philox4x32-10)" },
+      { "rdf",           0,  1, 'i', &cmd.rdf,            0, "bins of the radial distribution function g(r), sampled at every printed step (0 = off, at most 4096)" },
+      { "rdfMax",        0,  1, 'd', &cmd.rdfMax,         0, "range of g(r) in Angstroms (default and at most: the force cutoff)" },
+      { "rdfFile",       0,  1, 's', cmd.rdfFile, sizeof cmd.rdfFile, "file g(r) is written to (default rdf.dat)" },
    };
    const int nDefs = (int)(sizeof defs / sizeof defs[0]);
 

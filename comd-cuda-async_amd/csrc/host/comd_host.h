@@ -48,6 +48,9 @@ typedef struct CommandSt {
    double langevinTemp;   /* extension: its target in K; NAN until given = the -T value */
    double langevinDamp;   /* extension: its damping time tau in fs (default 100) */
    uint64_t seed;         /* extension: the key of its Philox noise (default COMD_LANGEVIN_SEED) */
+   int rdf;               /* extension: bins of the radial distribution function sampled at every printed step, 0 = off (the reference has no structural analysis) */
+   double rdfMax;         /* extension: its range in Angstroms; <= 0 = the force cutoff */
+   char rdfFile[1024];    /* extension: where the print rank writes it (default rdf.dat) */
 } Command;
 
 #define COMD_LANGEVIN_SEED 0x436f4d44ull     /* "CoMD" */
@@ -292,6 +295,11 @@ typedef struct SimFlatSt {
    double langevinTemp, langevinDamp;   /* target (K) and damping time tau (fs) */
    uint64_t langevinSeed;           /* Philox key */
    uint64_t stepCount;              /* global step index: 0 at creation, one per step of timestep(), the same on every rank (the noise counter) */
+   int rdfBins;                     /* --rdf: comdMain samples the pair histogram at every printed step; 0 = off */
+   double rdfMax;                   /* its range in Angstroms (the force cutoff unless --rdfMax) */
+   char rdfFile[1024];
+   double* rdfSum;                  /* [rdfBins] global unordered pair counts summed over the samples */
+   int rdfSamples;
 } SimFlat;
 
 SimFlat* initSimulation(Command cmd);
@@ -313,12 +321,18 @@ void computePressure(SimFlat* s);
 /* pressure tensor (K + W) / V in eV/A^3 and its trace / 3, and the conversion to GPa */
 #define eVperA3inGPa 160.21766208
 double pressureOf(const SimFlat* s);
+/* not in the reference: the global histogram of pair distances of the current state (after a complete force evaluation), nBins uniform bins
+ * [k dr, (k + 1) dr), dr = rMax / nBins; rMax <= 0 = the force cutoff.  outCounts[k] = unordered pairs in bin k: the ranks' ordered counts
+ * (computePairHistogram) summed -- integers below 2^53, exact in doubles -- and halved (every pair is seen once from each side, so the sum is even).
+ * The same on every rank.  -1 and nothing launched for nBins < 1, nBins > COMD_RDF_MAX_BINS or rMax > the force cutoff */
+#define COMD_RDF_MAX_BINS 4096
+int comdPairHistogram(SimFlat* s, int nBins, double rMax, double* outCounts);
 void redistributeAtoms(SimFlat* sim);
 void ensureInteriorForceLaunched(SimFlat* sim);
 
 /* ---- performanceTimers.h ---- */
 enum TimerHandle { totalTimer, loopTimer, timestepTimer, positionTimer, velocityTimer, redistributeTimer, atomHaloTimer,
-                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, numberOfTimers };
+                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, numberOfTimers };
 void profileStart(enum TimerHandle handle);
 void profileStop(enum TimerHandle handle);
 double getElapsedTime(enum TimerHandle handle);
@@ -358,6 +372,8 @@ int      comdSetLangevin(SimFlat* s, double tempK, double tauFs, uint64_t seed, 
 int      comdGetLangevin(SimFlat* s, double out[2], uint64_t* seed);    /* on/off; out = {tempK, tauFs} */
 uint64_t comdStepCount(SimFlat* s);                       /* steps taken since creation */
 void     comdVirial(SimFlat* s, double out[13]);          /* computePressure, then {W[6], K[6], V}: global pair virial and kinetic tensor (eV), volume (A^3) */
+double   comdCutoff(SimFlat* s);                          /* the force cutoff in Angstroms: the largest rMax of comdPairHistogram, and its default */
+double   comdVolume(SimFlat* s);                          /* volume of the global domain in A^3 */
 void     comdGridInfo(SimFlat* s, int out[6]);            /* gridSize[3], nLocalBoxes, nTotalBoxes, maxAtoms */
 int      comdMain(int argc, char** argv);                /* the reference's main(): CoMD.c:86-187 */
 void     comdDestroy(SimFlat* s);

@@ -146,6 +146,12 @@ SimFlat* initSimulationHost(Command cmd)
       if (printRank() && !cmd.quiet) printf("LJ by table interpolation (-I): %d intervals from %f to %f Angstroms\n", sim->ljTableN, sim->ljTableX0, lj->cutoff);
    }
    if (sim->spline) eamUseSplines(sim->pot);
+   /* --rdf (not in the reference): the range defaults to the force cutoff and cannot exceed it (the 27-cell walk of the histogram kernel sees no further) */
+   if (cmd.rdf < 0 || cmd.rdf > COMD_RDF_MAX_BINS) { printf("Error: --rdf takes 0 (off) to %d bins (got %d).\n", COMD_RDF_MAX_BINS, cmd.rdf); exit(-1); }
+   if (cmd.rdf && cmd.rdfMax > sim->pot->cutoff) { printf("Error: --rdfMax must not exceed the force cutoff of %g Angstroms (got %g).\n", (double)sim->pot->cutoff, cmd.rdfMax); exit(-1); }
+   sim->rdfBins = cmd.rdf; sim->rdfMax = cmd.rdfMax > 0.0 ? cmd.rdfMax : (double)sim->pot->cutoff;
+   strcpy(sim->rdfFile, cmd.rdfFile);
+   if (sim->rdfBins) sim->rdfSum = (double*)calloc((size_t)sim->rdfBins, sizeof(double));
    real_t latticeConstant = cmd.lat;
    if (cmd.lat < 0.0) latticeConstant = sim->pot->lat;
    sanityChecks(cmd, sim->pot->cutoff, latticeConstant, sim->pot->latticeType);
@@ -248,6 +254,7 @@ void destroySimulation(SimFlat** ps)
    destroyAtoms(s->atoms);
    free(s->boundary_cells_h); free(s->interior_cells_h); free(s->boundary1_cells_h);
    free(s->ljTable);
+   free(s->rdfSum);
    free(s->species); free(s->domain); free(s);
    *ps = NULL;
 }
@@ -298,6 +305,48 @@ static void printPressureYaml(FILE* file, SimFlat* s)
    for (int c = 0; c < 6; ++c) fprintf(file, "  P%s: %.12e\n", name[c], ((double)s->K[c] + s->W[c]) / s->V * eVperA3inGPa);
    fprintf(file, "\n");
    fflush(file);
+}
+
+/* --rdf: one more sample of the global pair histogram into rdfSum */
+static void sampleRdf(SimFlat* s)
+{
+   double* counts = (double*)malloc((size_t)s->rdfBins * sizeof(double));
+   if (comdPairHistogram(s, s->rdfBins, s->rdfMax, counts) != 0) { printf("Error: --rdf %d --rdfMax %g was refused.\n", s->rdfBins, s->rdfMax); exit(-1); }
+   for (int k = 0; k < s->rdfBins; ++k) s->rdfSum[k] += counts[k];
+   s->rdfSamples++;
+   free(counts);
+}
+
+/* --rdf: g_k = counts_k / (samples (N/2) (N/V) (4 pi/3) ((k + 1)^3 - k^3) dr^3), the ideal-gas count of unordered pairs in the shell of bin k.
+ * The file: a header line, then per bin its centre, g, the running coordination number n(r) = 2 sum counts / (samples N) up to the bin's upper edge and the
+ * mean pair count per sample.  The YAML block names the file and the position of the highest peak. */
+static void writeRdf(FILE* yaml, SimFlat* s)
+{
+   if (!printRank()) return;
+   const int nBins = s->rdfBins, samples = s->rdfSamples;
+   const double N = (double)s->atoms->nGlobal, V = (double)s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2];
+   const double dr = s->rdfMax / nBins, shell = 4.0 * M_PI / 3.0 * dr * dr * dr;
+   FILE* f = fopen(s->rdfFile, "w");
+   if (!f) { printf("Error: cannot write %s\n", s->rdfFile); exit(-1); }
+   fprintf(f, "# g(r): bins %d rMax %.17g samples %d N %d V %.17g | columns: r (A), g(r), n(r), pairs per sample\n", nBins, s->rdfMax, samples, s->atoms->nGlobal, V);
+   double running = 0.0, gTop = -1.0, rTop = 0.0;
+   for (int k = 0; k < nBins; ++k) {
+      const double k0 = (double)k, k1 = (double)k + 1.0;
+      const double g = s->rdfSum[k] / ((double)samples * (0.5 * N) * (N / V) * shell * (k1 * k1 * k1 - k0 * k0 * k0));
+      running += s->rdfSum[k];
+      fprintf(f, "%.17g %.17g %.17g %.17g\n", (k0 + 0.5) * dr, g, 2.0 * running / ((double)samples * N), s->rdfSum[k] / (double)samples);
+      if (g > gTop) { gTop = g; rTop = (k0 + 0.5) * dr; }
+   }
+   fclose(f);
+   if (!yaml) return;
+   fprintf(yaml, "RDF:\n");
+   fprintf(yaml, "  bins: %d\n", nBins);
+   fprintf(yaml, "  rMax: %.12e\n", s->rdfMax);
+   fprintf(yaml, "  samples: %d\n", samples);
+   fprintf(yaml, "  file: %s\n", s->rdfFile);
+   fprintf(yaml, "  rOfHighestG: %.12e\n", rTop);
+   fprintf(yaml, "\n");
+   fflush(yaml);
 }
 
 Validate* initValidate(SimFlat* sim)
@@ -397,6 +446,7 @@ int comdMain(int argc, char** argv)
       sumAtoms(sim);
       stopTimer(commReduceTimer);
       if (sim->pressure) { startTimer(pressureTimer); computePressure(sim); stopTimer(pressureTimer); }
+      if (sim->rdfBins) { startTimer(rdfTimer); sampleRdf(sim); stopTimer(rdfTimer); }
       printThings(sim, iStep, getElapsedTime(timestepTimer));
       startTimer(timestepTimer);
       timestep(sim, printRate, sim->dt);
@@ -406,9 +456,11 @@ int comdMain(int argc, char** argv)
    profileStop(loopTimer);
    sumAtoms(sim);
    if (sim->pressure) { startTimer(pressureTimer); computePressure(sim); stopTimer(pressureTimer); }
+   if (sim->rdfBins) { startTimer(rdfTimer); sampleRdf(sim); stopTimer(rdfTimer); }
    printThings(sim, iStep, getElapsedTime(timestepTimer));
    timestampBarrier("Ending simulation\n");
    if (sim->pressure) printPressureYaml(yamlFile, sim);
+   if (sim->rdfBins) writeRdf(yamlFile, sim);
 
    validateResult(validate, sim);
    profileStop(totalTimer);
@@ -484,6 +536,9 @@ int comdLjTable(SimFlat* s, double* x0, double* invDx, double* values)
    if (values) for (int i = 0; i < s->ljTableN + 4; ++i) values[i] = s->ljTable[i];
    return s->ljTableN;
 }
+
+double comdCutoff(SimFlat* s) { return s->pot->cutoff; }
+double comdVolume(SimFlat* s) { return (double)s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2]; }
 
 void comdGridInfo(SimFlat* s, int out[6])
 {

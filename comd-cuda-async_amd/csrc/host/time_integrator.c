@@ -102,6 +102,21 @@ void computePressure(SimFlat* s)
    s->V = s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2];
 }
 
+int comdPairHistogram(SimFlat* s, int nBins, double rMax, double* outCounts)
+{
+   const double cutoff = s->pot->cutoff;
+   if (rMax <= 0.0) rMax = cutoff;
+   if (nBins < 1 || nBins > COMD_RDF_MAX_BINS || !(rMax <= cutoff)) return -1;
+   uint64_t* local = (uint64_t*)malloc((size_t)nBins * sizeof(uint64_t));
+   double* mine = (double*)malloc((size_t)nBins * sizeof(double));
+   computePairHistogram(&s->gpu, nBins, (real_t)rMax, local);
+   for (int k = 0; k < nBins; ++k) mine[k] = (double)local[k];
+   addDoubleParallel(mine, outCounts, nBins);
+   for (int k = 0; k < nBins; ++k) outCounts[k] *= 0.5;
+   free(local); free(mine);
+   return 0;
+}
+
 double pressureOf(const SimFlat* s)
 {
    return ((double)s->K[0] + s->K[1] + s->K[2] + s->W[0] + s->W[1] + s->W[2]) / (3.0 * s->V);

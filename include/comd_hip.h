@@ -236,6 +236,8 @@ typedef struct SimGpuSt {
    int          genPairlist;
    int*         d_updateLinkCellsRequired;   /* device [1], zero: the reference's list mode copies it back to ask "did an atom change cells?" (timestep.c:329) */
    double*      virialBuf;             /* device: the workgroups' partial sums for computeVirial, allocated by its first call */
+   unsigned long long* pairHistBuf;    /* device: the bins of computePairHistogram, allocated by its first call and when a call asks for more bins */
+   int          pairHistCap;           /* bins pairHistBuf holds */
 } SimGpu;
 
 /* Everything AllocateGpu needs to know about the rank's geometry and potential.
@@ -408,6 +410,16 @@ void computeEnergy(SimGpu* sim, real_t* eLocal);
  * stream computeEnergy uses, after the force work of both streams of the overlap mode; deterministic two-stage reduction; reads r, p and
  * dfEmbed only.  Blocks until the result is on the host. */
 void computeVirial(SimGpu* sim, real_t* out12);
+/* Not in the reference (CoMD has no structural analysis): this rank's histogram of pair distances, the raw material of g(r),
+ *   outCounts[k] = number of ordered pairs (i a local atom, j a local or halo atom, j != i) with k dr <= r_ij < (k + 1) dr,  dr = rMax / nBins,
+ * for k = 0 .. nBins - 1, 1 <= nBins <= 4096, in host memory.  Every unordered pair is seen once from each side (from two ranks or images when
+ * it crosses a boundary), so the sum over ranks is twice the global number of pairs per bin.  rMax must not exceed the force cutoff of the
+ * potential in use: the 27-cell walk then sees every pair, with the cells of the *_nl methods and of -L as well (the caller checks; the host's
+ * comdPairHistogram does).  Call it when the halo images are current: after a complete force evaluation (timestep, computeForce), as
+ * computeVirial.  Any method.  Launched on the stream computeEnergy uses, after the force work of both streams of the overlap mode; 32-bit
+ * counters private to each workgroup in LDS, flushed with 64-bit integer atomics into a buffer zeroed on the same stream, so the result is
+ * bit-reproducible; reads r and the cell tables only.  Blocks until the result is on the host. */
+void computePairHistogram(SimGpu* sim, int nBins, real_t rMax, uint64_t* outCounts);
 
 /* ---- redistribute: gpu_kernels.h:84-86 ------------------------------------------------------ */
 /* updateLinkCellsGpu(SimFlat*), gpu_kernels.cu:469-504: empty the halo cells, move every local atom whose
