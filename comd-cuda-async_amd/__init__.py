@@ -131,6 +131,12 @@ def lib_host():
         lib.comdVirial.argtypes = [vp, c_double_p]
         lib.comdPairHistogram.argtypes = [vp, ctypes.c_int, ctypes.c_double, c_double_p]
         lib.comdPairHistogram.restype = ctypes.c_int
+        lib.comdTrackDisplacement.argtypes = [vp, ctypes.c_int]
+        lib.comdTrackDisplacement.restype = ctypes.c_int
+        lib.comdDisplacements.argtypes = [vp, c_double_p]
+        lib.comdDisplacements.restype = ctypes.c_int
+        lib.comdMsd.argtypes = [vp, c_double_p]
+        lib.comdMsd.restype = ctypes.c_int
         lib.comdCutoff.argtypes = [vp]
         lib.comdCutoff.restype = ctypes.c_double
         lib.comdVolume.argtypes = [vp]
@@ -414,6 +420,46 @@ class Simulation:
         k = np.arange(n_bins, dtype=np.float64)
         ideal = (0.5 * n) * (n / self.lib.comdVolume(self.ptr)) * (4.0 * np.pi / 3.0 * dr * dr * dr) * ((k + 1.0) ** 3 - k ** 3)
         return 0.5 * (edges[:-1] + edges[1:]), counts / ideal
+
+    # --- dynamics (not in the reference: comd-hip --msd, --msdStart, --msdFile) ---
+    def track_displacement(self, on=True):
+        """Start tracking every atom's unwrapped displacement from the current state (already tracking: the origin moves to the current state), or,
+        with on=False, stop and free the device memory.  The drift kernels of the integrator add dt p/m of each atom they move into a 64-bit
+        fixed-point record per global atom id (units of 2^-32 Angstroms), so periodic wraps, cell changes and migration between ranks do not show.
+        Every rank of a multi-rank run makes the call.  RuntimeError when the device refuses the memory (32 bytes per global atom on every rank)."""
+        if self.host_only:
+            raise RuntimeError("track_displacement: a host-only simulation has no integrator")
+        if self.lib.comdTrackDisplacement(self.ptr, 1 if on else 0) != 0:
+            raise RuntimeError(f"track_displacement: no device memory for the displacement records of {self.n_global} atoms")
+        self._tracking = bool(on)
+
+    def _need_tracking(self, what):
+        if not getattr(self, "_tracking", False):
+            raise ValueError(f"{what}: displacements are not tracked (call track_displacement() first)")
+
+    def displacements(self):
+        """(n_global, 3) float64: the unwrapped displacement of every atom since track_displacement(), in Angstroms, keyed by gid: the ranks'
+        integer records summed, the same array on every rank."""
+        np = self._np
+        self._need_tracking("displacements")
+        out = np.zeros((self.n_global, 3), dtype=np.float64)
+        rc = self.lib.comdDisplacements(self.ptr, out.ctypes.data_as(c_double_p))
+        if rc != 0:
+            raise RuntimeError(f"displacements: refused ({rc}): a component beyond 2^53 units of 2^-32 Angstroms")
+        return out
+
+    def msd(self, remove_drift=False):
+        """(msd, (msd_x, msd_y, msd_z)) in Angstroms^2: the mean over all atoms of |d|^2 and of its three parts, d the displacement since
+        track_displacement().  remove_drift: the mean displacement (the drift of the centre of mass, which a Langevin thermostat does not hold
+        still) is taken out, msd_c = <d_c^2> - <d_c>^2.  One rank: reduced on the device; several: summed on the host from displacements()."""
+        self._need_tracking("msd")
+        out = (ctypes.c_double * 7)()
+        rc = self.lib.comdMsd(self.ptr, out)
+        if rc != 0:
+            raise RuntimeError(f"msd: refused ({rc})")
+        n = out[6]
+        parts = tuple(out[3 + c] / n - ((out[c] / n) ** 2 if remove_drift else 0.0) for c in range(3))
+        return parts[0] + parts[1] + parts[2], parts
 
     @property
     def n_global(self):

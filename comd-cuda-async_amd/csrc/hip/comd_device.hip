@@ -23,6 +23,7 @@
 #include "virial_kernels.h"
 #include "rdf_kernels.h"
 #include "langevin_kernels.h"
+#include "msd_kernels.h"
 
 static int g_rank = 0;
 
@@ -589,7 +590,7 @@ extern "C" void DestroyGpu(SimGpu* sim)
                     sim->boxes.boxIDLookUp, sim->boxes.boxIDLookUpReverse, sim->eam_pot.phiS.coefficients, sim->eam_pot.rhoS.coefficients,
                     sim->eam_pot.pairRows, sim->eam_pot.pairRowCount, sim->eam_pot.cellSel, sim->eam_pot.brickGroup, sim->eam_pot.brickList, sim->eam_pot.brickSel, sim->eam_pot.brickStats, sim->eam_pot.atomRows, sim->eam_pot.atomRowCount, sim->eam_pot.atomBrickSel,
                     sim->atoms.neighborList.brickRows, sim->atoms.neighborList.brickRowCount, sim->adapterScan, sim->lj_pot.waveCand, sim->lj_pot.waveCandCount, sim->lj_pot.packedR[0], sim->lj_pot.packedR[1], sim->lj_pot.packedF[0], sim->lj_pot.packedF[1],
-                    sim->lj_pot.lj_interpolation.values, sim->virialBuf, sim->pairHistBuf };
+                    sim->lj_pot.lj_interpolation.values, sim->virialBuf, sim->pairHistBuf, sim->dispBuf, sim->dispSumBuf };
    for (void* p : ptrs) if (p) HIP_CHECK(hipFree(p));
    if (sim->statusEvent) (void)hipEventDestroy((hipEvent_t)sim->statusEvent);
    if (sim->pinned) HIP_CHECK(hipHostFree(sim->pinned));
@@ -962,12 +963,16 @@ extern "C" void advanceVelocityGpu(SimGpu* sim, real_t dt)
    LAUNCH_CHECK();
 }
 
+// displacement tracking (msd_kernels.h): what the drift kernels add into; d == NULL while comdTrackDisplacementGpu has not switched it on
+static DispTrack dispTrackOf(const SimGpu* sim) { DispTrack t = { (long long*)sim->dispBuf, sim->dispN }; return t; }
+
 extern "C" void advancePositionGpu(SimGpu* sim, real_t dt)
 {
    const long slots = (long)sim->boxes.nLocalBoxes * sim->maxAtoms;
    hipLaunchKernelGGL(AdvancePosition, integratorGrid(sim), dim3(256), 0, S(sim->boundary_stream),
                       sim->atoms.r.x, sim->atoms.r.y, sim->atoms.r.z, sim->atoms.p.x, sim->atoms.p.y, sim->atoms.p.z,
-                      sim->atoms.iSpecies, sim->species_mass, sim->boxes.nAtoms, sim->boxes.nLocalBoxes, sim->maxAtoms, dt, integratorLaneBits(sim));
+                      sim->atoms.iSpecies, sim->species_mass, sim->boxes.nAtoms, sim->boxes.nLocalBoxes, sim->maxAtoms, dt, sim->atoms.gid, dispTrackOf(sim),
+                      integratorLaneBits(sim));
    LAUNCH_CHECK();
 }
 
@@ -992,7 +997,8 @@ extern "C" void advanceVelocityPositionGpu(SimGpu* sim, real_t dtKick, real_t dt
    hipLaunchKernelGGL(AdvanceVelocityPosition, integratorGrid(sim), dim3(256), 0, S(sim->boundary_stream),
                       sim->atoms.r.x, sim->atoms.r.y, sim->atoms.r.z, sim->atoms.p.x, sim->atoms.p.y, sim->atoms.p.z,
                       sim->atoms.f.x, sim->atoms.f.y, sim->atoms.f.z, sim->atoms.iSpecies, sim->species_mass,
-                      sim->boxes.nAtoms, sim->boxes.nLocalBoxes, sim->maxAtoms, dtKick, dtDrift, sk, integratorLaneBits(sim));
+                      sim->boxes.nAtoms, sim->boxes.nLocalBoxes, sim->maxAtoms, dtKick, dtDrift, sk, sim->atoms.gid, dispTrackOf(sim),
+                      integratorLaneBits(sim));
    LAUNCH_CHECK();
 }
 
@@ -1003,7 +1009,8 @@ extern "C" void advanceVelocityVelocityPositionGpu(SimGpu* sim, real_t dtKick1, 
    hipLaunchKernelGGL(AdvanceVelocityVelocityPosition, integratorGrid(sim), dim3(256), 0, S(sim->boundary_stream),
                       sim->atoms.r.x, sim->atoms.r.y, sim->atoms.r.z, sim->atoms.p.x, sim->atoms.p.y, sim->atoms.p.z,
                       sim->atoms.f.x, sim->atoms.f.y, sim->atoms.f.z, sim->atoms.iSpecies, sim->species_mass,
-                      sim->boxes.nAtoms, sim->boxes.nLocalBoxes, sim->maxAtoms, dtKick1, dtKick2, dtDrift, sk, integratorLaneBits(sim));
+                      sim->boxes.nAtoms, sim->boxes.nLocalBoxes, sim->maxAtoms, dtKick1, dtKick2, dtDrift, sk, sim->atoms.gid,
+                      dispTrackOf(sim), integratorLaneBits(sim));
    LAUNCH_CHECK();
 }
 
@@ -1022,7 +1029,7 @@ extern "C" void advanceVelocityPositionLangevinGpu(SimGpu* sim, real_t dtKick, r
                       sim->atoms.r.x, sim->atoms.r.y, sim->atoms.r.z, sim->atoms.p.x, sim->atoms.p.y, sim->atoms.p.z,
                       sim->atoms.f.x, sim->atoms.f.y, sim->atoms.f.z, sim->atoms.iSpecies, sim->atoms.gid, sim->species_mass,
                       sim->boxes.nAtoms, sim->boxes.nLocalBoxes, sim->maxAtoms, dtKick, dtHalfDrift, langevinOf(c1, c2, kT, seed, step), sk,
-                      integratorLaneBits(sim));
+                      dispTrackOf(sim), integratorLaneBits(sim));
    LAUNCH_CHECK();
 }
 
@@ -1034,7 +1041,7 @@ extern "C" void advanceVelocityVelocityPositionLangevinGpu(SimGpu* sim, real_t d
                       sim->atoms.r.x, sim->atoms.r.y, sim->atoms.r.z, sim->atoms.p.x, sim->atoms.p.y, sim->atoms.p.z,
                       sim->atoms.f.x, sim->atoms.f.y, sim->atoms.f.z, sim->atoms.iSpecies, sim->atoms.gid, sim->species_mass,
                       sim->boxes.nAtoms, sim->boxes.nLocalBoxes, sim->maxAtoms, dtKick1, dtKick2, dtHalfDrift, langevinOf(c1, c2, kT, seed, step),
-                      sk, integratorLaneBits(sim));
+                      sk, dispTrackOf(sim), integratorLaneBits(sim));
    LAUNCH_CHECK();
 }
 
@@ -1125,6 +1132,62 @@ extern "C" void computePairHistogram(SimGpu* sim, int nBins, real_t rMax, uint64
    hipLaunchKernelGGL(PairHist_thread_atom, dim3(grid), dim3(256), lds, st, v);
    LAUNCH_CHECK();
    HIP_CHECK(hipMemcpyAsync(outCounts, sim->pairHistBuf, (size_t)nBins * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// Not in the reference: displacement tracking for the mean-squared displacement (msd_kernels.h).  on: one zeroed 32-byte record per global atom id,
+// which the drift kernels of this simulation add into from now on (already on: zeroed again, the origin becomes "now"); off: the memory is
+// freed.  1 and nothing tracked when the device cannot give the memory.
+extern "C" int comdTrackDisplacementGpu(SimGpu* sim, int nGlobal, int on)
+{
+   hipStream_t st = S(sim->boundary_stream);
+   if (!on || nGlobal != sim->dispN) {
+      if (sim->dispBuf) {
+         HIP_CHECK(hipStreamSynchronize(st));               // the last drift kernel has written its records
+         HIP_CHECK(hipFree(sim->dispBuf)); HIP_CHECK(hipFree(sim->dispSumBuf));
+      }
+      sim->dispBuf = nullptr; sim->dispSumBuf = nullptr; sim->dispN = 0;
+      if (!on) return 0;
+   }
+   if (nGlobal < 1) return 1;
+   if (!sim->dispBuf) {
+      void *d = nullptr, *p = nullptr;
+      if (hipMalloc(&d, (size_t)nGlobal * 4 * sizeof(long long)) != hipSuccess
+          || hipMalloc(&p, (size_t)(MSD_BLOCKS + 1) * MSD_N * sizeof(double)) != hipSuccess) {
+         (void)hipGetLastError();
+         if (d) (void)hipFree(d);
+         fprintf(stderr, "comdTrackDisplacementGpu: rank %d: no device memory for %d records of 32 bytes (%.1f MB): not tracking\n",
+                 g_rank, nGlobal, nGlobal * 32.0 / 1048576.0);
+         return 1;
+      }
+      sim->dispBuf = (int64_t*)d; sim->dispSumBuf = (double*)p; sim->dispN = nGlobal;
+   }
+   HIP_CHECK(hipMemsetAsync(sim->dispBuf, 0, (size_t)nGlobal * 4 * sizeof(long long), st));      // behind the drifts already launched
+   HIP_CHECK(hipStreamSynchronize(st));
+   return 0;
+}
+
+// Not in the reference: {sum dx, dy, dz, sum dx^2, dy^2, dz^2} (Angstroms, double in both builds) over THIS rank's records
+extern "C" void computeDisplacementSums(SimGpu* sim, double* out6)
+{
+   hipStream_t st = S(sim->boundary_stream);
+   if (!sim->dispBuf) { fprintf(stderr, "computeDisplacementSums: displacements are not tracked\n"); exit(-1); }
+   int blocks = ceilDiv(sim->dispN, 256);
+   if (blocks > MSD_BLOCKS) blocks = MSD_BLOCKS;
+   double* out = sim->dispSumBuf + (size_t)MSD_BLOCKS * MSD_N;
+   hipLaunchKernelGGL(ReduceDisplacementPartial, dim3(blocks), dim3(256), 0, st, (const long long*)sim->dispBuf, sim->dispN, sim->dispSumBuf);
+   hipLaunchKernelGGL(ReduceDisplacementFinal, dim3(1), dim3(256), 0, st, sim->dispSumBuf, blocks, out);
+   LAUNCH_CHECK();
+   HIP_CHECK(hipMemcpyAsync(out6, out, MSD_N * sizeof(double), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// Not in the reference: THIS rank's raw records, [nGlobal][4] int64 {dx, dy, dz, spare} in units of 2^-32 Angstroms
+extern "C" void comdCopyDisplacementsGpu(SimGpu* sim, int64_t* out)
+{
+   hipStream_t st = S(sim->boundary_stream);
+   if (!sim->dispBuf) { fprintf(stderr, "comdCopyDisplacementsGpu: displacements are not tracked\n"); exit(-1); }
+   HIP_CHECK(hipMemcpyAsync(out, sim->dispBuf, (size_t)sim->dispN * 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
    HIP_CHECK(hipStreamSynchronize(st));
 }
 

@@ -38,15 +38,19 @@ __device__ __forceinline__ void langevinNormals(const LangevinO& o, int gid, rea
 }
 
 // A O A of one atom: r, p in registers after the kicks
+// trk (msd_kernels.h): both half drifts count, (dt / 2m) (p before O + p after O), added in real_t and quantised once -- an expression of its own, as in step_kernels.h
 __device__ __forceinline__ void langevinAOA(const LangevinO& o, int gid, real_t mass, real_t invMass, real_t dtHalf,
-                                            real_t& x, real_t& y, real_t& z, real_t& nx, real_t& ny, real_t& nz)
+                                            real_t& x, real_t& y, real_t& z, real_t& nx, real_t& ny, real_t& nz, const DispTrack& trk)
 {
+   real_t ix = R(0.0), iy = R(0.0), iz = R(0.0);
+   if (trk.d) { ix = x; iy = y; iz = z; }
    nx += dtHalf * x * invMass; ny += dtHalf * y * invMass; nz += dtHalf * z * invMass;
    real_t xi0, xi1, xi2;
    langevinNormals(o, gid, xi0, xi1, xi2);
    const real_t s = o.c2 * sqrtR(mass * o.kT);
    x = o.c1 * x + s * xi0; y = o.c1 * y + s * xi1; z = o.c1 * z + s * xi2;
    nx += dtHalf * x * invMass; ny += dtHalf * y * invMass; nz += dtHalf * z * invMass;
+   if (trk.d) { const real_t w = dtHalf * invMass; dispAdd(trk, gid, w * (ix + x), w * (iy + y), w * (iz + z)); }
 }
 
 // B A O A: the first step of a timestep() call
@@ -56,7 +60,7 @@ void AdvanceVelocityPositionLangevin(real_t* __restrict__ rx, real_t* __restrict
                                      const real_t* __restrict__ fx, const real_t* __restrict__ fy, const real_t* __restrict__ fz,
                                      const int* __restrict__ iSpecies, const int* __restrict__ gid, const real_t* __restrict__ speciesMass,
                                      const int* __restrict__ nAtoms, int nLocalBoxes, int cap, real_t dtKick, real_t dtHalfDrift, LangevinO o,
-                                     SkinCheck sk, int laneBits)
+                                     SkinCheck sk, DispTrack trk, int laneBits)
 {
    skinProgress(sk);
    COMD_CELL_SLOTS(laneBits) {
@@ -64,7 +68,7 @@ void AdvanceVelocityPositionLangevin(real_t* __restrict__ rx, real_t* __restrict
       const real_t invMass = R(1.0) / mass;
       real_t x = px[tid] + dtKick * fx[tid], y = py[tid] + dtKick * fy[tid], z = pz[tid] + dtKick * fz[tid];
       real_t nx = rx[tid], ny = ry[tid], nz = rz[tid];
-      langevinAOA(o, gid[tid], mass, invMass, dtHalfDrift, x, y, z, nx, ny, nz);
+      langevinAOA(o, gid[tid], mass, invMass, dtHalfDrift, x, y, z, nx, ny, nz, trk);
       px[tid] = x; py[tid] = y; pz[tid] = z;
       rx[tid] = nx; ry[tid] = ny; rz[tid] = nz;
       skinCheck(sk, tid, nx, ny, nz);
@@ -79,7 +83,7 @@ void AdvanceVelocityVelocityPositionLangevin(real_t* __restrict__ rx, real_t* __
                                              const real_t* __restrict__ fx, const real_t* __restrict__ fy, const real_t* __restrict__ fz,
                                              const int* __restrict__ iSpecies, const int* __restrict__ gid, const real_t* __restrict__ speciesMass,
                                              const int* __restrict__ nAtoms, int nLocalBoxes, int cap, real_t dtKick1, real_t dtKick2, real_t dtHalfDrift,
-                                             LangevinO o, SkinCheck sk, int laneBits)
+                                             LangevinO o, SkinCheck sk, DispTrack trk, int laneBits)
 {
    skinProgress(sk);
    COMD_CELL_SLOTS(laneBits) {
@@ -89,7 +93,7 @@ void AdvanceVelocityVelocityPositionLangevin(real_t* __restrict__ rx, real_t* __
       real_t x = px[tid] + dtKick1 * gx, y = py[tid] + dtKick1 * gy, z = pz[tid] + dtKick1 * gz;
       x += dtKick2 * gx; y += dtKick2 * gy; z += dtKick2 * gz;
       real_t nx = rx[tid], ny = ry[tid], nz = rz[tid];
-      langevinAOA(o, gid[tid], mass, invMass, dtHalfDrift, x, y, z, nx, ny, nz);
+      langevinAOA(o, gid[tid], mass, invMass, dtHalfDrift, x, y, z, nx, ny, nz, trk);
       px[tid] = x; py[tid] = y; pz[tid] = z;
       rx[tid] = nx; ry[tid] = ny; rz[tid] = nz;
       skinCheck(sk, tid, nx, ny, nz);

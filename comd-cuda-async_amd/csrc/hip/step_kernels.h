@@ -11,6 +11,12 @@
 //  - energy is reduced in two deterministic stages (no fp64 atomics).
 #pragma once
 #include "device_common.h"
+#include "msd_kernels.h"
+
+// Displacement tracking (msd_kernels.h DispTrack, d == NULL: off): the drift kernels add the motion of the atom they move, dt p/m, to the record of its gid.
+// The increment is its own expression, (dt / m) p, inside the tracked branch: it shares no product with the position update r + dt * p * invMass, whose
+// contraction into fused multiply-adds (and so every bit of r) is the same with and without the tracker.  The two differ by an ulp of the increment in real_t:
+// 4e-19 A in double, far below the record's unit; in single 2e-10 A, the rounding dt p/m carries anyway.
 
 // ---- integrator -------------------------------------------------------------------------------------
 // [round 4] 2^laneBits threads of a 256-thread workgroup serve one cell and loop over its atoms (slot = lane, lane + 2^laneBits, ...).  Round 3 ran a thread per
@@ -32,11 +38,12 @@ __global__ __launch_bounds__(256)
 void AdvancePosition(real_t* __restrict__ rx, real_t* __restrict__ ry, real_t* __restrict__ rz,
                      const real_t* __restrict__ px, const real_t* __restrict__ py, const real_t* __restrict__ pz,
                      const int* __restrict__ iSpecies, const real_t* __restrict__ speciesMass,
-                     const int* __restrict__ nAtoms, int nLocalBoxes, int cap, real_t dt, int laneBits)
+                     const int* __restrict__ nAtoms, int nLocalBoxes, int cap, real_t dt, const int* __restrict__ gid, DispTrack trk, int laneBits)
 {
    COMD_CELL_SLOTS(laneBits) {
       const real_t invMass = R(1.0) / speciesMass[iSpecies[tid]];  // same expression order as timestep.c:168-173
       rx[tid] += dt * px[tid] * invMass; ry[tid] += dt * py[tid] * invMass; rz[tid] += dt * pz[tid] * invMass;
+      if (trk.d) { const real_t w = dt * invMass; dispAdd(trk, gid[tid], w * px[tid], w * py[tid], w * pz[tid]); }
    }
 }
 
@@ -69,7 +76,8 @@ void AdvanceVelocityPosition(real_t* __restrict__ rx, real_t* __restrict__ ry, r
                              real_t* __restrict__ px, real_t* __restrict__ py, real_t* __restrict__ pz,
                              const real_t* __restrict__ fx, const real_t* __restrict__ fy, const real_t* __restrict__ fz,
                              const int* __restrict__ iSpecies, const real_t* __restrict__ speciesMass,
-                             const int* __restrict__ nAtoms, int nLocalBoxes, int cap, real_t dtKick, real_t dtDrift, SkinCheck sk, int laneBits)
+                             const int* __restrict__ nAtoms, int nLocalBoxes, int cap, real_t dtKick, real_t dtDrift, SkinCheck sk,
+                             const int* __restrict__ gid, DispTrack trk, int laneBits)
 {
    skinProgress(sk);
    COMD_CELL_SLOTS(laneBits) {
@@ -79,6 +87,7 @@ void AdvanceVelocityPosition(real_t* __restrict__ rx, real_t* __restrict__ ry, r
       const real_t nx = rx[tid] + dtDrift * x * invMass, ny = ry[tid] + dtDrift * y * invMass, nz = rz[tid] + dtDrift * z * invMass;
       rx[tid] = nx; ry[tid] = ny; rz[tid] = nz;
       skinCheck(sk, tid, nx, ny, nz);
+      if (trk.d) { const real_t w = dtDrift * invMass; dispAdd(trk, gid[tid], w * x, w * y, w * z); }
    }
 }
 
@@ -89,7 +98,8 @@ void AdvanceVelocityVelocityPosition(real_t* __restrict__ rx, real_t* __restrict
                                      real_t* __restrict__ px, real_t* __restrict__ py, real_t* __restrict__ pz,
                                      const real_t* __restrict__ fx, const real_t* __restrict__ fy, const real_t* __restrict__ fz,
                                      const int* __restrict__ iSpecies, const real_t* __restrict__ speciesMass,
-                                     const int* __restrict__ nAtoms, int nLocalBoxes, int cap, real_t dtKick1, real_t dtKick2, real_t dtDrift, SkinCheck sk, int laneBits)
+                                     const int* __restrict__ nAtoms, int nLocalBoxes, int cap, real_t dtKick1, real_t dtKick2, real_t dtDrift, SkinCheck sk,
+                                     const int* __restrict__ gid, DispTrack trk, int laneBits)
 {
    skinProgress(sk);
    COMD_CELL_SLOTS(laneBits) {
@@ -101,6 +111,7 @@ void AdvanceVelocityVelocityPosition(real_t* __restrict__ rx, real_t* __restrict
       const real_t nx = rx[tid] + dtDrift * x * invMass, ny = ry[tid] + dtDrift * y * invMass, nz = rz[tid] + dtDrift * z * invMass;
       rx[tid] = nx; ry[tid] = ny; rz[tid] = nz;
       skinCheck(sk, tid, nx, ny, nz);
+      if (trk.d) { const real_t w = dtDrift * invMass; dispAdd(trk, gid[tid], w * x, w * y, w * z); }
    }
 }
 

@@ -7,7 +7,9 @@
  * --pressure (a Pressure(GPa) column in the report: pair virial + kinetic tensor, which the reference does not compute),
  * --langevin, --langevinTemp K, --langevinDamp FS, --seed N (BAOAB Langevin thermostat; the reference integrates NVE only),
  * --rdf N, --rdfMax R, --rdfFile PATH (radial distribution function g(r) from a pair histogram of N bins up to R Angstroms, sampled at every
- * printed step and written to PATH; the reference has no structural analysis). */
+ * printed step and written to PATH; the reference has no structural analysis),
+ * --msd, --msdStart S, --msdFile PATH (mean-squared displacement of the unwrapped trajectories from global step S on, accumulated in the drift
+ * kernels, sampled at every printed step and written to PATH with a diffusion coefficient; the reference has no dynamical analysis). */
 #include "comd_host.h"
 #include <getopt.h>
 #include <math.h>
@@ -41,6 +43,7 @@ Command parseCommandLine(int argc, char** argv)
    cmd.dt = 1.0; cmd.lat = -1.0; cmd.temperature = 600.0; cmd.initialDelta = 0.0; cmd.relativeSkinDistance = 0.1;
    cmd.langevinTemp = NAN; cmd.langevinDamp = COMD_LANGEVIN_DAMP; cmd.seed = COMD_LANGEVIN_SEED;
    strcpy(cmd.rdfFile, "rdf.dat");
+   strcpy(cmd.msdFile, "msd.dat");
    int help = 0;
 
    const ArgDef defs[] = {
@@ -82,6 +85,9 @@ Command parseCommandLine(int argc, char** argv)
       { "rdf",           0,  1, 'i', &cmd.rdf,            0, "bins of the radial distribution function g(r), sampled at every printed step (0 = off, at most 4096)" },
       { "rdfMax",        0,  1, 'd', &cmd.rdfMax,         0, "range of g(r) in Angstroms (default and at most: the force cutoff)" },
       { "rdfFile",       0,  1, 's', cmd.rdfFile, sizeof cmd.rdfFile, "file g(r) is written to (default rdf.dat)" },
+      { "msd",           0,  0, 'i', &cmd.msd,            0, "mean-squared displacement (unwrapped, tracked in the integrator), sampled at every printed step" },
+      { "msdStart",      0,  1, 'i', &cmd.msdStart,       0, "global step the MSD origin is taken at (0..nSteps; default 0)" },
+      { "msdFile",       0,  1, 's', cmd.msdFile, sizeof cmd.msdFile, "file the MSD is written to (default msd.dat)" },
    };
    const int nDefs = (int)(sizeof defs / sizeof defs[0]);
 
@@ -156,6 +162,7 @@ void printCmdYaml(FILE* file, Command* cmd)
               "  Langevin damping: %g fs\n"
               "  Langevin seed: %llu\n",
               cmd->langevinTemp, cmd->langevinDamp, (unsigned long long)cmd->seed);
+   if (cmd->msd) fprintf(file, "  MSD from step: %d\n  MSD file: %s\n", cmd->msdStart, cmd->msdFile);
    fprintf(file, "\n");
    fflush(file);
 }

@@ -51,6 +51,9 @@ typedef struct CommandSt {
    int rdf;               /* extension: bins of the radial distribution function sampled at every printed step, 0 = off (the reference has no structural analysis) */
    double rdfMax;         /* extension: its range in Angstroms; <= 0 = the force cutoff */
    char rdfFile[1024];    /* extension: where the print rank writes it (default rdf.dat) */
+   int msd;               /* extension: mean-squared displacement from displacements tracked in the drift kernels, sampled at every printed step (the reference has no dynamical analysis) */
+   int msdStart;          /* extension: the global step its origin is taken at, 0..nSteps (default 0) */
+   char msdFile[1024];    /* extension: where the print rank writes it (default msd.dat) */
 } Command;
 
 #define COMD_LANGEVIN_SEED 0x436f4d44ull     /* "CoMD" */
@@ -300,6 +303,12 @@ typedef struct SimFlatSt {
    char rdfFile[1024];
    double* rdfSum;                  /* [rdfBins] global unordered pair counts summed over the samples */
    int rdfSamples;
+   int trackDisp;                   /* comdTrackDisplacement: the drift kernels add every atom's motion into the device records of its gid */
+   int msd, msdStart;               /* --msd: comdMain tracks from global step msdStart on and samples the MSD at every printed step */
+   char msdFile[1024];
+   double* msdRows;                 /* [msdSamples][8]: step, the seven values of comdMsd */
+   int msdSamples, msdCap;
+   double msdNow;                   /* the MSD(A^2) column of printThings: the last sample, 0 before the origin */
 } SimFlat;
 
 SimFlat* initSimulation(Command cmd);
@@ -327,12 +336,23 @@ double pressureOf(const SimFlat* s);
  * The same on every rank.  -1 and nothing launched for nBins < 1, nBins > COMD_RDF_MAX_BINS or rMax > the force cutoff */
 #define COMD_RDF_MAX_BINS 4096
 int comdPairHistogram(SimFlat* s, int nBins, double rMax, double* outCounts);
+/* not in the reference: unwrapped displacements since an origin, accumulated by the drift kernels in 64-bit fixed point per global atom id
+ * (include/comd_hip.h comdTrackDisplacementGpu).  Collective: every rank makes each call.
+ * comdTrackDisplacement: on != 0 sets (or, when already tracking, resets) the origin to the current state, 0 stops and frees; non-zero, with
+ *    nothing tracked on any rank, when a device refuses the memory.
+ * comdDisplacements: out[3 gid + {0, 1, 2}] = the global displacement of atom gid in Angstroms, the same on every rank: the ranks' integer records
+ *    summed (exact, whatever ranks the atom has been on).  -1 when not tracking, -2 when a component is beyond 2^53 units (2^21 A) on several ranks.
+ * comdMsd: out7 = {sum dx, sum dy, sum dz, sum dx^2, sum dy^2, sum dz^2, N} over all atoms.  One rank: the device reduction; several: the sums of
+ *    comdDisplacements in gid order on the host (squares of the ranks' parts do not add).  Same return values. */
+int comdTrackDisplacement(SimFlat* s, int on);
+int comdDisplacements(SimFlat* s, double* out);
+int comdMsd(SimFlat* s, double* out7);
 void redistributeAtoms(SimFlat* sim);
 void ensureInteriorForceLaunched(SimFlat* sim);
 
 /* ---- performanceTimers.h ---- */
 enum TimerHandle { totalTimer, loopTimer, timestepTimer, positionTimer, velocityTimer, redistributeTimer, atomHaloTimer,
-                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, numberOfTimers };
+                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, numberOfTimers };
 void profileStart(enum TimerHandle handle);
 void profileStop(enum TimerHandle handle);
 double getElapsedTime(enum TimerHandle handle);

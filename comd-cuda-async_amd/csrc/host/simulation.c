@@ -152,6 +152,10 @@ SimFlat* initSimulationHost(Command cmd)
    sim->rdfBins = cmd.rdf; sim->rdfMax = cmd.rdfMax > 0.0 ? cmd.rdfMax : (double)sim->pot->cutoff;
    strcpy(sim->rdfFile, cmd.rdfFile);
    if (sim->rdfBins) sim->rdfSum = (double*)calloc((size_t)sim->rdfBins, sizeof(double));
+   /* --msd (not in the reference): the origin is a global step of this run */
+   if (cmd.msdStart < 0 || cmd.msdStart > cmd.nSteps) { printf("Error: --msdStart must lie in 0..nSteps = 0..%d (got %d).\n", cmd.nSteps, cmd.msdStart); exit(-1); }
+   sim->msd = cmd.msd; sim->msdStart = cmd.msdStart;
+   strcpy(sim->msdFile, cmd.msdFile);
    real_t latticeConstant = cmd.lat;
    if (cmd.lat < 0.0) latticeConstant = sim->pot->lat;
    sanityChecks(cmd, sim->pot->cutoff, latticeConstant, sim->pot->latticeType);
@@ -255,6 +259,7 @@ void destroySimulation(SimFlat** ps)
    free(s->boundary_cells_h); free(s->interior_cells_h); free(s->boundary1_cells_h);
    free(s->ljTable);
    free(s->rdfSum);
+   free(s->msdRows);
    free(s->species); free(s->domain); free(s);
    *ps = NULL;
 }
@@ -278,8 +283,8 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
       s->firstPrint = 0;
       fprintf(screenOut,
               "#                                                                                         Performance\n"
-              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms%s\n",
-              s->pressure ? "    Pressure(GPa)" : "");
+              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms%s%s\n",
+              s->pressure ? "    Pressure(GPa)" : "", s->msd ? "         MSD(A^2)" : "");
       fflush(screenOut);
    }
    real_t time = iStep * s->dt;
@@ -291,6 +296,7 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
    fprintf(screenOut, " %6d %10.2f %18.12f %18.12f %18.12f %12.4f %10.4f %12d",
            iStep, time, eTotal, eU, eK, Temp, timePerAtom, s->atoms->nGlobal);
    if (s->pressure) fprintf(screenOut, " %16.10f", pressureOf(s) * eVperA3inGPa);
+   if (s->msd) fprintf(screenOut, " %16.10e", s->msdNow);
    fprintf(screenOut, "\n");
 }
 
@@ -345,6 +351,66 @@ static void writeRdf(FILE* yaml, SimFlat* s)
    fprintf(yaml, "  samples: %d\n", samples);
    fprintf(yaml, "  file: %s\n", s->rdfFile);
    fprintf(yaml, "  rOfHighestG: %.12e\n", rTop);
+   fprintf(yaml, "\n");
+   fflush(yaml);
+}
+
+/* --msd: the origin: tracking on (or, were it on already, zeroed again) */
+static void startMsd(SimFlat* s)
+{
+   if (comdTrackDisplacement(s, 1) != 0) { printf("Error: --msd: no device memory for the displacement records of %d atoms.\n", s->atoms->nGlobal); exit(-1); }
+}
+
+/* --msd: one more row {step, sum d (3), sum d^2 (3), N} */
+static void sampleMsd(SimFlat* s, int iStep)
+{
+   if (s->msdSamples == s->msdCap) { s->msdCap = s->msdCap ? 2 * s->msdCap : 64; s->msdRows = (double*)realloc(s->msdRows, (size_t)s->msdCap * 8 * sizeof(double)); }
+   double* row = s->msdRows + 8 * (size_t)s->msdSamples++;
+   row[0] = (double)iStep;
+   if (comdMsd(s, row + 1) != 0) { printf("Error: --msd: the displacements could not be summed.\n"); exit(-1); }
+   s->msdNow = (row[4] + row[5] + row[6]) / row[7];
+}
+
+/* --msd: the file: a header line, then per sample the time since the origin in fs, MSD = sum |d|^2 / N, its x, y, z parts and the MSD with the drift of the
+ * centre of mass removed, sum |d|^2 / N - |sum d / N|^2 (a Langevin thermostat does not conserve momentum: the centre of mass walks).  The YAML block names
+ * the file and gives D = slope / 6 of a least-squares line through the drift-removed MSD of the samples in the second half of the tracked interval. */
+static void writeMsd(FILE* yaml, SimFlat* s)
+{
+   if (!printRank()) return;
+   const int samples = s->msdSamples;
+   FILE* f = fopen(s->msdFile, "w");
+   if (!f) { printf("Error: cannot write %s\n", s->msdFile); exit(-1); }
+   fprintf(f, "# MSD: N %d dt %.17g originStep %d samples %d | columns: t - t0 (fs), MSD (A^2), MSD_x, MSD_y, MSD_z, MSD without the centre-of-mass drift\n",
+           s->atoms->nGlobal, s->dt, s->msdStart, samples);
+   double tLast = 0.0, msdLast = 0.0, freeLast = 0.0;
+   double st = 0.0, sy = 0.0, stt = 0.0, sty = 0.0; int m = 0;
+   if (samples > 0) tLast = (s->msdRows[8 * (size_t)(samples - 1)] - s->msdStart) * s->dt;
+   for (int k = 0; k < samples; ++k) {
+      const double* row = s->msdRows + 8 * (size_t)k;
+      const double N = row[7], t = (row[0] - s->msdStart) * s->dt;
+      const double mx = row[4] / N, my = row[5] / N, mz = row[6] / N;
+      const double cx = row[1] / N, cy = row[2] / N, cz = row[3] / N;
+      msdLast = mx + my + mz; freeLast = msdLast - (cx * cx + cy * cy + cz * cz);
+      fprintf(f, "%.17g %.17g %.17g %.17g %.17g %.17g\n", t, msdLast, mx, my, mz, freeLast);
+      if (t >= 0.5 * tLast) { st += t; sy += freeLast; stt += t * t; sty += t * freeLast; m++; }
+   }
+   fclose(f);
+   if (!yaml) return;
+   fprintf(yaml, "MSD:\n");
+   fprintf(yaml, "  originStep: %d\n", s->msdStart);
+   fprintf(yaml, "  samples: %d\n", samples);
+   fprintf(yaml, "  finalMSD: %.12e\n", msdLast);
+   fprintf(yaml, "  finalMSDNoDrift: %.12e\n", freeLast);
+   fprintf(yaml, "  Units: Angstroms^2\n");
+   fprintf(yaml, "  file: %s\n", s->msdFile);
+   const double det = m * stt - st * st;
+   if (m >= 3 && det > 0.0) {
+      const double D = (m * sty - st * sy) / det / 6.0;
+      fprintf(yaml, "  D: %.12e\n", D);
+      fprintf(yaml, "  DUnits: Angstroms^2/fs\n");
+      fprintf(yaml, "  D_cm2_per_s: %.12e\n", 0.1 * D);
+      fprintf(yaml, "  fitSamples: %d\n", m);
+   } else fprintf(yaml, "  D: n/a\n");
    fprintf(yaml, "\n");
    fflush(yaml);
 }
@@ -447,9 +513,13 @@ int comdMain(int argc, char** argv)
       stopTimer(commReduceTimer);
       if (sim->pressure) { startTimer(pressureTimer); computePressure(sim); stopTimer(pressureTimer); }
       if (sim->rdfBins) { startTimer(rdfTimer); sampleRdf(sim); stopTimer(rdfTimer); }
+      if (sim->msd && iStep >= sim->msdStart) { startTimer(msdTimer); if (iStep == sim->msdStart) startMsd(sim); sampleMsd(sim, iStep); stopTimer(msdTimer); }
       printThings(sim, iStep, getElapsedTime(timestepTimer));
+      /* --msdStart between two printed steps: the interval is taken as two timestep() calls (which give the bits of one) with the origin in between */
+      const int toOrigin = sim->msd && sim->msdStart > iStep && sim->msdStart < iStep + printRate ? sim->msdStart - iStep : 0;
       startTimer(timestepTimer);
-      timestep(sim, printRate, sim->dt);
+      if (toOrigin) { timestep(sim, toOrigin, sim->dt); startMsd(sim); }
+      timestep(sim, printRate - toOrigin, sim->dt);
       stopTimer(timestepTimer);
       iStep += printRate;
    }
@@ -457,10 +527,12 @@ int comdMain(int argc, char** argv)
    sumAtoms(sim);
    if (sim->pressure) { startTimer(pressureTimer); computePressure(sim); stopTimer(pressureTimer); }
    if (sim->rdfBins) { startTimer(rdfTimer); sampleRdf(sim); stopTimer(rdfTimer); }
+   if (sim->msd && iStep >= sim->msdStart) { startTimer(msdTimer); if (iStep == sim->msdStart) startMsd(sim); sampleMsd(sim, iStep); stopTimer(msdTimer); }
    printThings(sim, iStep, getElapsedTime(timestepTimer));
    timestampBarrier("Ending simulation\n");
    if (sim->pressure) printPressureYaml(yamlFile, sim);
    if (sim->rdfBins) writeRdf(yamlFile, sim);
+   if (sim->msd) writeMsd(yamlFile, sim);
 
    validateResult(validate, sim);
    profileStop(totalTimer);

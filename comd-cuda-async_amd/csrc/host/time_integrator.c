@@ -117,6 +117,68 @@ int comdPairHistogram(SimFlat* s, int nBins, double rMax, double* outCounts)
    return 0;
 }
 
+/* ---- displacement tracking (not in the reference; comd_host.h) ---- */
+int comdTrackDisplacement(SimFlat* s, int on)
+{
+   int fail = comdTrackDisplacementGpu(&s->gpu, s->atoms->nGlobal, on), anyFail = 0;
+   maxIntParallel(&fail, &anyFail, 1);
+   if (anyFail && !fail) comdTrackDisplacementGpu(&s->gpu, s->atoms->nGlobal, 0);      /* all ranks or none */
+   s->trackDisp = on != 0 && !anyFail;
+   return anyFail;
+}
+
+#define COMD_DISP_UNIT (1.0 / 4294967296.0)      /* Angstroms per unit of the device records */
+
+int comdDisplacements(SimFlat* s, double* out)
+{
+   if (!s->trackDisp) return -1;
+   const size_t n = (size_t)s->atoms->nGlobal;
+   int64_t* raw = (int64_t*)malloc(4 * n * sizeof(int64_t));
+   comdCopyDisplacementsGpu(&s->gpu, raw);
+   if (getNRanks() == 1) {
+      for (size_t g = 0; g < n; ++g) for (int c = 0; c < 3; ++c) out[3 * g + c] = (double)raw[4 * g + c] * COMD_DISP_UNIT;
+      free(raw);
+      return 0;
+   }
+   /* the ranks' parts as doubles (exact below 2^53), summed in chunks whose count fits addDoubleParallel's int */
+   const int64_t top = (int64_t)1 << 53;
+   double* mine = (double*)malloc(3 * n * sizeof(double));
+   int bad = 0, anyBad = 0;
+   for (size_t g = 0; g < n; ++g)
+      for (int c = 0; c < 3; ++c) {
+         const int64_t v = raw[4 * g + c];
+         if (v >= top || v <= -top) bad = 1;
+         mine[3 * g + c] = (double)v;
+      }
+   free(raw);
+   maxIntParallel(&bad, &anyBad, 1);
+   if (!anyBad) {
+      const size_t chunk = (size_t)1 << 28;
+      startTimer(commReduceTimer);
+      for (size_t o = 0; o < 3 * n; o += chunk) addDoubleParallel(mine + o, out + o, (int)(3 * n - o < chunk ? 3 * n - o : chunk));
+      stopTimer(commReduceTimer);
+      for (size_t k = 0; k < 3 * n; ++k) out[k] *= COMD_DISP_UNIT;
+   }
+   free(mine);
+   return anyBad ? -2 : 0;
+}
+
+int comdMsd(SimFlat* s, double* out7)
+{
+   if (!s->trackDisp) return -1;
+   const size_t n = (size_t)s->atoms->nGlobal;
+   out7[6] = (double)n;
+   if (getNRanks() == 1) { computeDisplacementSums(&s->gpu, out7); return 0; }
+   double* d = (double*)malloc(3 * n * sizeof(double));
+   const int rc = comdDisplacements(s, d);
+   for (int c = 0; c < 6; ++c) out7[c] = 0.0;
+   if (rc == 0)
+      for (size_t g = 0; g < n; ++g)
+         for (int c = 0; c < 3; ++c) { const double v = d[3 * g + c]; out7[c] += v; out7[3 + c] += v * v; }
+   free(d);
+   return rc;
+}
+
 double pressureOf(const SimFlat* s)
 {
    return ((double)s->K[0] + s->K[1] + s->K[2] + s->W[0] + s->W[1] + s->W[2]) / (3.0 * s->V);

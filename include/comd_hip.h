@@ -238,6 +238,9 @@ typedef struct SimGpuSt {
    double*      virialBuf;             /* device: the workgroups' partial sums for computeVirial, allocated by its first call */
    unsigned long long* pairHistBuf;    /* device: the bins of computePairHistogram, allocated by its first call and when a call asks for more bins */
    int          pairHistCap;           /* bins pairHistBuf holds */
+   int64_t*     dispBuf;               /* device [dispN][4]: displacement records by gid (comdTrackDisplacementGpu), NULL = not tracking */
+   double*      dispSumBuf;            /* device: the workgroups' partial sums for computeDisplacementSums, allocated with dispBuf */
+   int          dispN;                 /* records dispBuf holds = nGlobal */
 } SimGpu;
 
 /* Everything AllocateGpu needs to know about the rank's geometry and potential.
@@ -420,6 +423,18 @@ void computeVirial(SimGpu* sim, real_t* out12);
  * counters private to each workgroup in LDS, flushed with 64-bit integer atomics into a buffer zeroed on the same stream, so the result is
  * bit-reproducible; reads r and the cell tables only.  Blocks until the result is on the host. */
 void computePairHistogram(SimGpu* sim, int nBins, real_t rMax, uint64_t* outCounts);
+/* Not in the reference: unwrapped displacements since an origin, for the mean-squared displacement (hip/msd_kernels.h).  on != 0: allocate and zero
+ * one 32-byte record {dx, dy, dz, spare} per global atom id, signed 64-bit fixed point in units of 2^-32 Angstroms; from then on the drift kernels
+ * of this simulation (advancePositionGpu and the fused forms, plain and Langevin) add dt p/m of every local atom into the record of its gid.  Already
+ * on: the records are zeroed again, the origin becomes "now".  on == 0: the memory is freed and the kernels run with a null tracker, as they do
+ * by default.  Returns non-zero, with a message and nothing tracked, when the device cannot give the memory. */
+int comdTrackDisplacementGpu(SimGpu* sim, int nGlobal, int on);
+/* Not in the reference: out6 = {sum dx, sum dy, sum dz, sum dx^2, sum dy^2, sum dz^2} in Angstroms over THIS rank's records (an atom that has been
+ * on several ranks has a part of its displacement on each: squares of parts do not add, so the sums mean something on one rank only -- with
+ * more the host sums the raw records first).  Double in both precision builds; deterministic two-stage reduction on the stream computeEnergy uses. */
+void computeDisplacementSums(SimGpu* sim, double* out6);
+/* Not in the reference: copy THIS rank's raw records to the host, out[4 * gid + {0, 1, 2}] = dx, dy, dz in units of 2^-32 Angstroms (4 * nGlobal words) */
+void comdCopyDisplacementsGpu(SimGpu* sim, int64_t* out);
 
 /* ---- redistribute: gpu_kernels.h:84-86 ------------------------------------------------------ */
 /* updateLinkCellsGpu(SimFlat*), gpu_kernels.cu:469-504: empty the halo cells, move every local atom whose

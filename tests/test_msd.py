@@ -1,0 +1,465 @@
+"""Mean-squared displacement from displacements tracked in the drift kernels (comd-hip --msd, Simulation.track_displacement / displacements / msd;
+hip/msd_kernels.h).  The reference has no counterpart and there is no oracle: the references here are analytic results (free flight, the
+deterministic 0 K Langevin decay) and numpy restatements built from gather()ed positions.
+
+Error bounds (derived, not measured).  A drift call quantises its increment once, to 2^-32 A, round to nearest: at most 2^-33 A per component
+and call, 2^-32 A per step to be safe (the issue counts a Langevin step's two half drifts separately).  Where the reference is built from
+gathered positions, each drift has also rounded the stored position to the real_t grid, by at most half an ulp of the box edge L.  So
+
+    tol(n, L) = n (2^-32 + 2 eps L),   eps = 2.2e-16 (double) or 1.2e-7 (COMD_PRECISION=single)
+
+which for n = 40, L = 29 A is 9e-9 A (double) or 3e-4 A (single); one lost step at 600 K is about 3e-3 A rms per component, a missed wrap is L.
+"""
+import json
+import os
+import re
+import shutil
+import subprocess
+import sys
+import textwrap
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HERE = os.path.dirname(os.path.abspath(__file__))
+CSRC = os.path.join(ROOT, "comd-cuda-async_amd", "csrc")
+SINGLE = os.environ.get("COMD_PRECISION", "double") == "single"
+TOL = json.load(open(os.path.join(HERE, "golden", "reference_values.json")))["tolerances_single" if SINGLE else "tolerances"]
+
+LAT = 3.615
+EPS = 1.2e-7 if SINGLE else 2.2e-16
+Q = 2.0 ** -32                                     # Angstroms per unit of the device records
+MISHIN = ["-e", "-t", "setfl", "-p", "Cu01.eam.alloy"]
+GAS = ["-x", 6, "-y", 6, "-z", 6, "-l", 20]         # nearest neighbours at 14.1 A, beyond the 5 sigma = 11.6 A cutoff
+GAS_L = 120.0
+HOT = GAS + ["-T", 150000]
+
+
+def tol(n, box):
+    return n * (Q + 2.0 * EPS * box)
+
+
+def _cube(n):
+    return ["-x", n, "-y", n, "-z", n, "-l", repr(LAT)]
+
+
+def _wrap(d, box):
+    return d - np.rint(d / box) * box
+
+
+def _mass(p, ek):
+    """the (single) species mass from the momenta and the kinetic energy the device reduced: sum p^2 / 2 eK"""
+    return float((p * p).sum() / (2.0 * ek))
+
+
+PRELUDE = f"import sys, json\nsys.path.insert(0, {ROOT!r})\nimport __graft_entry__ as ge\npkg = ge.load_package()\n"
+
+
+def _child(code, env=None, timeout=600):
+    return subprocess.run([sys.executable, "-c", PRELUDE + textwrap.dedent(code)], cwd=ROOT, capture_output=True, text=True, timeout=timeout,
+                          env=dict(os.environ, **(env or {})))
+
+
+# ---------------------------------------------------------------- CPU: flags, exports, ISA
+def test_msd_flags_are_listed_and_accepted_host_only():
+    proc = _child("pkg.Simulation(['-x', 8, '-y', 8, '-z', 8, '--msd', '--msdStart', 40, '--msdFile', 'x.dat'], host_only=True).close(); print('made')")
+    assert proc.returncode == 0 and "made" in proc.stdout and "invalid switch" not in proc.stdout, proc.stdout[-2000:] + proc.stderr[-2000:]
+    proc = _child("pkg.Simulation(['--help'], host_only=True)")
+    for flag in ("msd", "msdStart", "msdFile"):
+        assert re.search(rf"^\s+--{flag}\s", proc.stdout, flags=re.M), (flag, proc.stdout[-3000:])
+    for bad in (-1, 101):                             # nSteps defaults to 100
+        proc = _child(f"pkg.Simulation(['-x', 8, '-y', 8, '-z', 8, '--msd', '--msdStart', {bad}], host_only=True); print('made')")
+        assert proc.returncode != 0 and "made" not in proc.stdout and "--msdStart must lie in 0..nSteps" in proc.stdout, proc.stdout[-2000:]
+    proc = _child("pkg.Simulation(['-x', 8, '-y', 8, '-z', 8, '-N', 300, '--msd', '--msdStart', 300], host_only=True).close(); print('made')")
+    assert proc.returncode == 0 and "made" in proc.stdout, proc.stdout[-2000:] + proc.stderr[-2000:]
+
+
+def test_untracked_calls_raise_before_anything_is_launched(pkg):
+    """displacements() and msd() of a simulation that is not tracking raise ValueError; a host-only simulation has no device to launch on."""
+    sim = pkg.Simulation(_cube(8), host_only=True)
+    try:
+        with pytest.raises(ValueError):
+            sim.displacements()
+        with pytest.raises(ValueError):
+            sim.msd()
+    finally:
+        sim.close()
+
+
+@pytest.mark.parametrize("sfx", ["", "_sp"])
+def test_displacement_entries_are_exported_and_declared(sfx):
+    def exported(name):
+        out = subprocess.run(["nm", "-D", "--defined-only", os.path.join(CSRC, name)], capture_output=True, text=True).stdout
+        return {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert {"comdTrackDisplacementGpu", "computeDisplacementSums", "comdCopyDisplacementsGpu"} <= exported(f"libcomd_hip{sfx}.so")
+    assert {"comdTrackDisplacement", "comdDisplacements", "comdMsd"} <= exported(f"libcomd_host{sfx}.so")
+    header = open(os.path.join(ROOT, "include", "comd_hip.h")).read()
+    assert re.search(r"^int comdTrackDisplacementGpu\(SimGpu\* sim, int nGlobal, int on\);", header, flags=re.M)
+    assert re.search(r"^void computeDisplacementSums\(SimGpu\* sim, double\* out6\);", header, flags=re.M)
+    assert re.search(r"^void comdCopyDisplacementsGpu\(SimGpu\* sim, int64_t\* out\);", header, flags=re.M)
+
+
+DRIFT_KERNELS = {"AdvancePosition", "AdvanceVelocityPosition", "AdvanceVelocityVelocityPosition", "AdvanceVelocityPositionLangevin",
+                 "AdvanceVelocityVelocityPositionLangevin"}
+REDUCTION_KERNELS = {"ReduceDisplacementPartial", "ReduceDisplacementFinal"}
+
+
+@pytest.mark.parametrize("precision", ["double", "single"])
+def test_drift_and_reduction_kernels_use_no_scratch(tmp_path, precision):
+    """The five kernels that drift (langevinAOA's two half drifts are inside the two Langevin kernels: six drifts) and the two stages of the reduction"""
+    if shutil.which("hipcc") is None:
+        pytest.fail("hipcc not on PATH")
+    src = os.path.join(CSRC, "hip", "comd_device.hip")
+    out = tmp_path / "dev.s"
+    proc = subprocess.run(["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-Wno-comment", "-I" + os.path.join(ROOT, "include"),
+                           "-I" + os.path.dirname(src), "-S", "--cuda-device-only", "-o", str(out), src]
+                          + (["-DCOMD_SINGLE"] if precision == "single" else []), capture_output=True, text=True)
+    assert proc.returncode == 0, proc.stderr[-2000:]
+    blocks = {}
+    for mangled, block in re.findall(r"^\s*\.amdhsa_kernel (_Z\d+\w+)\n(.*?)\.end_amdhsa_kernel", out.read_text(), flags=re.S | re.M):
+        m = re.match(r"_Z(\d+)", mangled)
+        blocks[mangled[m.end():m.end() + int(m.group(1))]] = block
+    assert DRIFT_KERNELS | REDUCTION_KERNELS <= set(blocks), sorted(blocks)
+    for name in sorted(DRIFT_KERNELS | REDUCTION_KERNELS):
+        assert re.search(r"\.amdhsa_private_segment_fixed_size 0\n", blocks[name]), name
+
+
+# ---------------------------------------------------------------- GPU 1, 2: free flight
+def _check_msd(sim, d):
+    """msd() against mean |d|^2 of displacements(): 1e-12 relative; the parts add up to the total"""
+    total, parts = sim.msd()
+    want = (d * d).sum(axis=0) / d.shape[0]
+    print("msd", total, want.sum(), parts)
+    assert abs(total - want.sum()) <= 1e-12 * want.sum()
+    assert np.all(np.abs(np.array(parts) - want) <= 1e-12 * want.sum())
+    assert abs(sum(parts) - total) <= 1e-14 * total
+
+
+@pytest.mark.gpu
+def test_free_flight_is_n_dt_p_over_m(gpu):
+    """-l 20: every force is exactly 0 (asserted), so NVE is r_n = r_0 + n dt p_0 / m and the displacement after n steps is n dt p_0 / m:
+    within n 2^-32 A plus 1e-12 relative in the double build; the single build rounds dt p / m itself (3 roundings of 6e-8 relative on
+    0.003 A a step, far inside tol(n, L), which is the bound there)."""
+    n = 100
+    with gpu.Simulation(GAS + ["-T", 600]) as sim:
+        p0 = sim.gather(1).copy()
+        m = _mass(p0, sim.energy()[1])
+        sim.track_displacement()
+        assert not sim.displacements().any()
+        sim.step(n)
+        f = sim.gather(2)
+        assert not f.any() and sim.energy()[0] == 0.0, (np.abs(f).max(), sim.energy())
+        assert np.array_equal(sim.gather(1), p0)
+        d = sim.displacements()
+        want = n * 1.0 * p0 / m
+        err = np.abs(d - want)
+        bound = tol(n, GAS_L) if SINGLE else n * Q + 1e-12 * np.abs(want)
+        print("free flight: max err", err.max(), "bound", np.min(bound), "max |d|", np.abs(d).max())
+        assert d.shape == (sim.n_global, 3) and d.dtype == np.float64
+        assert np.all(err <= bound)
+        _check_msd(sim, d)
+
+
+@pytest.mark.gpu
+def test_langevin_at_zero_kelvin_is_the_geometric_sum(gpu):
+    """set_langevin(0 K, tau): the noise term is c2 sqrt(m 0) xi = 0 exactly and the forces are 0, so p_k = c1^k p_0 and step k drifts by
+    (dt / 2m) (p_k + c1 p_k): d_n = (dt / 2m)(1 + c1) p_0 sum_{k<n} c1^k.  n = 1 is the kernel that opens a step() call, the others the
+    fused one between steps; both of langevinAOA's half drifts count."""
+    tau = 40.0
+    c1 = float(np.float32(np.exp(-1.0 / tau))) if SINGLE else float(np.exp(-1.0 / tau))
+    with gpu.Simulation(GAS + ["-T", 600]) as sim:
+        p0 = sim.gather(1).copy()
+        m = _mass(p0, sim.energy()[1])
+        sim.set_langevin(0.0, tau)
+        sim.track_displacement()
+        for n in (1, 10, 50):
+            sim.step(n - sim.step_count)
+            assert not sim.gather(2).any()
+            d = sim.displacements()
+            want = (1.0 / (2.0 * m)) * (1.0 + c1) * p0 * sum(c1 ** k for k in range(n))
+            err = np.abs(d - want)
+            bound = tol(n, GAS_L) if SINGLE else n * Q + 1e-12 * np.abs(want)
+            print("langevin 0 K: n", n, "max err", err.max(), "max |d|", np.abs(d).max())
+            assert np.all(err <= bound), n
+        _check_msd(sim, d)
+
+
+@pytest.mark.gpu
+def test_unfused_drift_entry_is_tracked(gpu):
+    """advancePositionGpu, the reference's unfused drift (timestep() runs the fused forms), feeds the tracker like the others: three drifts
+    of dt = 0.5 fs move every atom, and its record, by 1.5 p / m."""
+    import ctypes
+    with gpu.Simulation(GAS + ["-T", 600]) as sim:
+        r0, p0 = sim.gather(0).copy(), sim.gather(1).copy()
+        m = _mass(p0, sim.energy()[1])
+        sim.track_displacement()
+        hip = gpu.lib_hip()
+        for _ in range(3):
+            hip.advancePositionGpu(ctypes.c_void_p(sim.lib.comdSimGpu(sim.ptr)), gpu.c_real(0.5))
+        d = sim.displacements()
+        want = 1.5 * p0 / m
+        print("unfused drift: max err", np.abs(d - want).max(), "against the positions", np.abs((sim.gather(0) - r0) - d).max())
+        assert np.all(np.abs(d - want) <= (tol(3, GAS_L) if SINGLE else 3 * Q + 1e-12 * np.abs(want)))
+        assert np.abs((sim.gather(0) - r0) - d).max() <= tol(3, GAS_L)
+
+
+# ---------------------------------------------------------------- GPU 3: wraps, cell changes, slot churn
+def _incremental(sim, steps, box, chunk=1):
+    """sum over the steps of the minimum-image increment of the gathered positions -> (displacement, first positions, last positions, faces
+    crossed per atom).  Every increment must be far below box / 2 for the minimum image to be the motion: asserted."""
+    r_first = sim.gather(0).copy()
+    prev, total, crossed = r_first, np.zeros_like(r_first), np.zeros(r_first.shape[0], dtype=np.int64)
+    for _ in range(steps // chunk):
+        sim.step(chunk)
+        r = sim.gather(0).copy()
+        raw = r - prev
+        inc = _wrap(raw, box)
+        assert np.abs(inc).max() < 0.25 * box
+        crossed += (np.rint(raw / box) != 0).any(axis=1)
+        total += inc
+        prev = r
+    return total, r_first, prev, crossed
+
+
+@pytest.fixture(scope="module")
+def hot_gas_200(gpu):
+    """the hot gas taken as 200 x step(1): (displacements(), incremental reference, first and last positions, faces crossed, link-cell grid)"""
+    with gpu.Simulation(HOT) as sim:
+        sim.track_displacement()
+        ref, r_first, r_last, crossed = _incremental(sim, 200, GAS_L)
+        d = sim.displacements()
+        _check_msd(sim, d)
+        return d, ref, r_first, r_last, crossed, sim.grid
+
+
+@pytest.mark.gpu
+def test_wraps_cell_changes_and_slot_churn(hot_gas_200):
+    """LJ 5 sigma gas at 150000 K: in 200 steps atoms cross periodic faces (where the stored position jumps by L), change link cell (and with
+    it slot, and the thread that drifts them) and collide.  The reference is incremental -- the sum over the steps of the minimum-image
+    increment of the gathered positions -- because it stays valid however far an atom travels, while the end-point minimum image is only the
+    displacement as long as |d| < L / 2; for this run (max |d| of about 33 A against L / 2 = 60 A, asserted) the two agree, which is asserted
+    too.  The test asserts that the reference itself saw what it is meant to cover: >= 8 % of the atoms crossed a face, >= half changed cell
+    (a free-flight Monte Carlo of this lattice and temperature gives 15 % and 91 %)."""
+    d, ref, r_first, r_last, crossed, grid = hot_gas_200
+    cell = GAS_L / np.array(grid, dtype=np.float64)
+    changed = (np.floor(np.mod(r_first, GAS_L) / cell) != np.floor(np.mod(r_last, GAS_L) / cell)).any(axis=1)
+    print("hot gas: crossed", (crossed > 0).mean(), "changed cell", changed.mean(), "max |d|", np.abs(ref).max(), "max err", np.abs(d - ref).max(),
+          "tol", tol(200, GAS_L))
+    assert (crossed > 0).mean() >= 0.08
+    assert changed.mean() >= 0.5
+    assert np.abs(ref).max() < 0.5 * GAS_L
+    assert np.abs(_wrap(r_last - r_first, GAS_L) - ref).max() <= tol(200, GAS_L)
+    assert np.abs(d - ref).max() <= tol(200, GAS_L)
+
+
+@pytest.mark.gpu
+def test_one_call_of_200_steps_gives_the_200_single_steps(gpu, hot_gas_200):
+    """step(200) runs the fused kick-kick-drift kernel between steps where 200 x step(1) runs the opening kernel every time: the same
+    trajectory bit for bit, so the same displacements up to the quantisation of either side, 200 x 2^-32 A."""
+    with gpu.Simulation(HOT) as sim:
+        sim.track_displacement()
+        sim.step(200)
+        d = sim.displacements()
+    print("step(200) against 200 x step(1): max diff", np.abs(d - hot_gas_200[0]).max())
+    assert np.abs(d - hot_gas_200[0]).max() <= 200 * Q
+
+
+# ---------------------------------------------------------------- GPU 4: interacting solids
+SOLIDS = [("lj", [], "thread_atom", None), ("lj", [], "cta_cell", None), ("lj", [], "thread_atom_nl", None), ("adams", ["-e"], "cta_cell", (300.0, 20.0, 0x9E3779B97F4A7C15)),
+          ("adams", ["-e"], "thread_atom_nl", None), ("mishin", MISHIN, "thread_atom", None)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,pot,method,langevin", SOLIDS, ids=[f"{s[0]}-{s[2]}{'-langevin' if s[3] else ''}" for s in SOLIDS])
+def test_interacting_solids(gpu, name, pot, method, langevin):
+    """8^3, -r 0.1, 40 steps against the incremental reference of the hot-gas test, within tol(40, L)"""
+    n, steps = 8, 40
+    box = n * LAT
+    with gpu.Simulation(_cube(n) + ["-r", 0.1, "-m", method] + pot) as sim:
+        if langevin:
+            sim.set_langevin(*langevin)
+        sim.track_displacement()
+        ref, _, _, _ = _incremental(sim, steps, box)
+        d = sim.displacements()
+        print(name, method, "max |d|", np.abs(ref).max(), "max err", np.abs(d - ref).max(), "tol", tol(steps, box))
+        assert np.abs(ref).max() > 0.05                      # the atoms did move: thermal motion over 40 fs
+        assert np.abs(d - ref).max() <= tol(steps, box)
+        _check_msd(sim, d)
+
+
+@pytest.mark.gpu
+def test_hilbert_numbering_gives_the_same_integers(gpu):
+    """-H renumbers the link cells, not the atoms: the same trajectory, the same increments, the same records"""
+    got = []
+    for extra in ([], ["-H"]):
+        with gpu.Simulation(_cube(8) + ["-r", 0.1, "-m", "thread_atom"] + extra) as sim:
+            sim.track_displacement()
+            sim.step(40)
+            got.append(sim.displacements())
+    assert np.abs(got[0]).max() > 0.05
+    assert np.array_equal(got[0], got[1])
+
+
+# ---------------------------------------------------------------- GPU 5: nothing else changes
+@pytest.mark.gpu
+@pytest.mark.parametrize("pot", [[], ["-e"]], ids=["lj", "eam"])
+def test_tracking_changes_nothing_else(gpu, pot):
+    got = []
+    for track in (False, True):
+        with gpu.Simulation(_cube(8) + ["-r", 0.1] + pot) as sim:
+            if track:
+                sim.track_displacement()
+            sim.step(20)
+            got.append((sim.gather(0).copy(), sim.gather(1).copy(), sim.gather(2).copy(), sim.energy()))
+    for a, b in zip(got[0][:3], got[1][:3]):
+        assert np.array_equal(a, b)
+    assert got[0][3] == got[1][3]
+
+
+# ---------------------------------------------------------------- GPU 6: origin and lifetime
+@pytest.mark.gpu
+def test_origin_and_lifetime(gpu):
+    n, k = 8, 10
+    box = n * LAT
+    with gpu.Simulation(_cube(n) + ["-r", 0.1]) as sim:
+        with pytest.raises(ValueError):
+            sim.msd()
+        with pytest.raises(ValueError):
+            sim.displacements()
+        sim.track_displacement()
+        sim.step(k)
+        assert sim.displacements().any()
+        sim.track_displacement()                                # again: the origin is now
+        assert not sim.displacements().any() and sim.msd()[0] == 0.0
+        ref, _, _, _ = _incremental(sim, k, box)
+        d = sim.displacements()
+        assert np.abs(d - ref).max() <= tol(k, box)
+        sim.track_displacement(on=False)
+        with pytest.raises(ValueError):
+            sim.msd()
+        with pytest.raises(ValueError):
+            sim.displacements()
+        sim.step(2)                                             # the kernels run with a null tracker again
+        sim.track_displacement()
+        sim.step(2)
+        assert sim.displacements().any()
+    sim = gpu.Simulation(_cube(n) + ["-r", 0.1])                # destroyed while tracking
+    sim.track_displacement()
+    sim.step(2)
+    sim.close()
+
+
+# ---------------------------------------------------------------- GPU 7: two ranks
+def _ranks(grid, args, steps, tmp_path, timeout=300):
+    import socket
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = str(s.getsockname()[1])
+    world = grid[0] * grid[1] * grid[2]
+    env = dict(os.environ, OMP_NUM_THREADS="2")
+    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "msd_worker.py"), str(r), str(world), port, *map(str, grid),
+                               json.dumps(args), str(steps), str(tmp_path / f"rank{r}.npz")],
+                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env)
+             for r in range(world)]
+    outs = []
+    for p in procs:
+        try:
+            outs.append(p.communicate(timeout=timeout)[0])
+        except subprocess.TimeoutExpired:
+            for q in procs:
+                q.kill()
+            raise
+    for r, (p, out) in enumerate(zip(procs, outs)):
+        assert p.returncode == 0, f"rank {r} failed:\n{out[-3000:]}"
+    return [np.load(tmp_path / f"rank{r}.npz") for r in range(world)]
+
+
+@pytest.mark.gpu
+def test_two_ranks_give_the_one_rank_displacements(gpu, tmp_path):
+    """2 ranks (2x1x1) sharing the device over gloo, the hot gas for 100 steps.  First the summed positions against the one-rank run, with the
+    tolerance expression test_langevin.py::test_ranks_give_the_one_rank_trajectory applies to r: a failure there says the trajectories
+    diverged, one after it that the displacement is wrong.  Then displacements() of every rank against the one-rank array within that
+    tolerance plus 100 x 2^-32 A; msd() the same on both ranks and 1e-12 relative from mean |d|^2; at least one atom changed rank."""
+    steps = 100
+    with gpu.Simulation(HOT) as sim:
+        sim.track_displacement()
+        sim.step(steps)
+        r0, d0 = sim.gather(0).copy(), sim.displacements()
+    parts = _ranks((2, 1, 1), HOT, steps, tmp_path)
+    r = sum(s["r"] for s in parts)
+    assert np.all(sum(s["own1"].astype(int) for s in parts) == 1) and np.all(sum(s["own0"].astype(int) for s in parts) == 1)
+    tol_r = 100 * TOL["force_rel_to_max"]
+    print("two ranks: positions differ by", np.abs(_wrap(r - r0, GAS_L)).max(), "bound", tol_r * np.abs(r0).max())
+    assert np.abs(_wrap(r - r0, GAS_L)).max() <= tol_r * np.abs(r0).max()
+    for s in parts:
+        print("two ranks: displacements differ by", np.abs(s["d"] - d0).max())
+        assert np.abs(s["d"] - d0).max() <= tol_r * np.abs(r0).max() + steps * Q
+    assert np.array_equal(parts[0]["d"], parts[1]["d"])
+    assert np.array_equal(parts[0]["msd"], parts[1]["msd"])
+    want = (parts[0]["d"] ** 2).sum() / d0.shape[0]
+    assert abs(parts[0]["msd"][0] - want) <= 1e-12 * want
+    assert abs(parts[0]["msd"][1:].sum() - parts[0]["msd"][0]) <= 1e-14 * want
+    moved = (parts[0]["own0"] != parts[0]["own1"]).sum()
+    print("two ranks: atoms that changed rank", moved)
+    assert moved >= 1
+
+
+# ---------------------------------------------------------------- GPU 8: single precision
+@pytest.mark.gpu
+def test_single_precision_free_flight_and_wraps():
+    """The free-flight and hot-gas tests in the float build (COMD_PRECISION=single, lib*_sp.so) with the single-precision tol: the increment is
+    converted to double before it is scaled, the records and the sums stay 64-bit."""
+    env = dict(os.environ, COMD_PRECISION="single")
+    cmd = [sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider", os.path.join(HERE, "test_msd.py"),
+           "-k", "test_free_flight_is_n_dt_p_over_m or test_wraps_cell_changes_and_slot_churn or test_one_call_of_200_steps"]
+    proc = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert proc.returncode == 0, proc.stdout[-3000:] + proc.stderr[-2000:]
+    assert "3 passed" in proc.stdout, proc.stdout[-1000:]
+
+
+# ---------------------------------------------------------------- GPU 9: the command line
+def _comd_hip(tmp_path, extra):
+    proc = subprocess.run([os.path.join(CSRC, "comd-hip"), "-x", "8", "-y", "8", "-z", "8", "-N", "200", "-n", "20", "-d", os.path.join(ROOT, "pots")]
+                          + extra, capture_output=True, text=True, cwd=tmp_path, timeout=300)
+    assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-2000:]
+    yaml = [f for f in os.listdir(tmp_path) if f.startswith("CoMD-hip") and f.endswith(".yaml")]
+    assert len(yaml) == 1
+    text = (tmp_path / yaml[0]).read_text()
+    os.remove(tmp_path / yaml[0])
+    return proc.stdout, text
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("extra", [[], ["--langevin", "--langevinDamp", "50"]], ids=["nve", "langevin"])
+def test_comd_hip_msd(gpu, tmp_path, extra):
+    out, yaml = _comd_hip(tmp_path, ["--msd", "--msdStart", "40"] + extra)
+    assert re.search(r"^#\s+Loop .*# Atoms\s+MSD\(A\^2\)$", out, flags=re.M), out[:3000]
+    rows = [(int(s), float(v)) for s, v in re.findall(r"^\s+(\d+)\s+\d+\.\d+(?:\s+\S+){5}\s+\d+\s+(\S+)$", out, flags=re.M)]
+    assert [s for s, _ in rows] == list(range(0, 220, 20)), out[:3000]
+    assert all(v == 0.0 for s, v in rows if s <= 40)
+    assert rows[3][1] > 0.0 and all(np.isfinite(v) for _, v in rows)
+    assert re.search(r"^msd\s+9\s", out, flags=re.M)          # the timer row: one call per sample
+    lines = (tmp_path / "msd.dat").read_text().splitlines()
+    head = re.match(r"# MSD: N (\d+) dt (\S+) originStep (\d+) samples (\d+) ", lines[0])
+    assert head and [int(head.group(1)), float(head.group(2)), int(head.group(3)), int(head.group(4))] == [2048, 1.0, 40, 9]
+    table = np.array([[float(v) for v in line.split()] for line in lines[1:]])
+    assert table.shape == (9, 6)
+    assert np.array_equal(table[:, 0], np.arange(0.0, 180.0, 20.0)) and not table[0, 1:].any()
+    assert np.allclose(table[:, 2:5].sum(axis=1), table[:, 1], rtol=1e-14, atol=0.0)
+    assert np.all(table[:, 5] <= table[:, 1] * (1 + 1e-15)) and np.all(table[1:, 5] > 0.0)
+    assert [float(f"{v:.10e}") for v in table[:, 1]] == [v for s, v in rows if s >= 40]
+    block = re.search(r"^MSD:\n((?:  .*\n)+)", yaml, flags=re.M)
+    assert block, yaml[-3000:]
+    keys = dict(re.findall(r"^  (\w+): (.*)$", block.group(1), flags=re.M))
+    assert keys["originStep"] == "40" and keys["samples"] == "9" and keys["file"] == "msd.dat"
+    assert float(keys["finalMSD"]) == pytest.approx(table[-1, 1], rel=1e-11) and float(keys["finalMSDNoDrift"]) == pytest.approx(table[-1, 5], rel=1e-11)
+    assert np.isfinite(float(keys["D"])) and float(keys["D_cm2_per_s"]) == pytest.approx(0.1 * float(keys["D"]), rel=1e-11)
+    # D restated: least squares through the drift-removed MSD of the second half of the tracked interval (t >= 80 fs: 5 samples)
+    half = table[table[:, 0] >= 0.5 * table[-1, 0]]
+    assert int(keys["fitSamples"]) == len(half) == 5
+    assert float(keys["D"]) == pytest.approx(np.polyfit(half[:, 0], half[:, 5], 1)[0] / 6.0, rel=1e-8, abs=1e-18)
+    os.remove(tmp_path / "msd.dat")
+    out0, yaml0 = _comd_hip(tmp_path, extra)
+    assert "MSD" not in out0 and "MSD" not in yaml0 and not re.search(r"^msd\s", out0, flags=re.M)
+    assert not (tmp_path / "msd.dat").exists()
