@@ -363,6 +363,22 @@ class Simulation:
         return {"lj_candidate_lists_active": bool(a[0]), "eam_brick_image_records": a[1], "neighbor_list_format": a[2], "eam_brick_cells": a[3] & 255, "eam_brick_lists_made": a[3] >> 8,
                 "eam_bricks_in_thread_per_atom_fallback": b[0], "eam_bricks_per_launch": b[1]}
 
+    _LJ_CTA_FORMS = {0: None, 1: "boxes", 2: "slabs", 3: "pairlist"}
+    _EAM_KERNELS = {0: None, 1: "brick", 2: "atom_brick", 3: "cta_cell_round2", 4: "listed_rows", 5: "nl_lds", 6: "thread_atom_round2", 7: "nl_global"}
+    _EAM_COVERS = {0: "all_cells", 1: "whole_bricks", 2: "cell_by_cell"}
+
+    def force_leg_report(self):
+        """What the LAST force evaluation of this simulation ran (comd_hip.h comdForceLegReport): the wrappers' records of their launches and counts taken from the
+        device arrays they fill.  Waits for the device; launches and clears nothing.  eam_bricks_streamed_total counts since creation: take the difference of two reports."""
+        out = (ctypes.c_int * 32)()
+        lib_hip().comdForceLegReport(ctypes.c_void_p(self.lib.comdSimGpu(self.ptr)), out)
+        return {"lj_waves_per_cell": out[0], "lj_list_row_capacity": out[1], "lj_lists_active": bool(out[2]), "lj_waves_listed": out[3], "lj_waves_walking": out[4],
+                "lj_candidates_min": out[5], "lj_candidates_max": out[6], "lj_cta_form": self._LJ_CTA_FORMS[out[7]],
+                "eam_kernel": self._EAM_KERNELS[out[8]], "eam_brick_shape": (out[9], out[10]), "eam_image_records": out[11], "eam_bricks": out[12],
+                "eam_pass1_workgroups": out[13], "eam_bricks_streamed_total": out[14], "eam_row_capacity": out[15], "eam_pass3_read_rows": bool(out[16]),
+                "eam_cover": self._EAM_COVERS[out[17]], "eam_byte_offset_limit": out[18], "eam_tables_in_lds": bool(out[19]), "eam_spline": bool(out[20]),
+                "eam_clamps_kept": bool(out[21]), "eam_stencil_records": out[22], "neighbor_list_format": out[23]}
+
     # --- results ---
     def energy(self):
         """(ePotential, eKinetic, nGlobal) totals in eV."""

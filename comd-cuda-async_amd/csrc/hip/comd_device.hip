@@ -117,6 +117,12 @@ static ComdTuning readTuning()
 }
 // AllocateGpu fills SimGpu.tuning; a SimGpu that reaches a launch wrapper without it gets its record here
 static const ComdTuning& tuningOf(SimGpu* sim) { if (!sim->tuning) sim->tuning = new ComdTuning(readTuning()); return *(const ComdTuning*)sim->tuning; }
+// ---- what the last force launches ran (comdForceLegReport): written down by the launch wrappers, per simulation, SimGpu.legs ----
+struct ForceLegs {
+   int ljWaves, ljListCap, ljLists, ljCtaForm;
+   int eamKernel, eamBy, eamBz, eamImage, eamBricks, eamPass1Grid, eamRows, eamPass3ReadsRows, eamCover, eamRunMax, eamTablesInLds, eamSpline, eamClampsKept, eamStencil;
+};
+static ForceLegs& legsOf(SimGpu* sim) { if (!sim->legs) sim->legs = new ForceLegs(); return *(ForceLegs*)sim->legs; }
 // The density estimates behind the sizing of rows, lists and LDS images: the perfect FCC lattice, 4 atoms per lat^3 (GpuConfig.latticeConstant; 0: copper)
 static double latticeConstantOf(const SimGpu* sim) { return sim->latticeConstant > 0.0 ? sim->latticeConstant : 3.615; }
 static const double SPHERE_VOLUME = 4.18879020478639;      // of radius 1
@@ -579,6 +585,7 @@ extern "C" void DestroyGpu(SimGpu* sim)
       delete t;
    }
    delete (ComdTuning*)sim->tuning;
+   delete (ForceLegs*)sim->legs;
    void* ptrs[] = { sim->boxes.nAtoms, sim->atoms.r.x, sim->atoms.r.y, sim->atoms.r.z, sim->atoms.p.x, sim->atoms.p.y, sim->atoms.p.z,
                     sim->atoms.f.x, sim->atoms.f.y, sim->atoms.f.z, sim->atoms.e, sim->atoms.iSpecies, sim->atoms.gid,
                     sim->neighbor_cells, sim->species_mass, sim->eam_pot.phi.values, sim->eam_pot.rho.values, sim->eam_pot.f.values,
@@ -828,6 +835,7 @@ static void launchLjThreadAtom(SimGpu* sim, const LjArgs& a, int num_cells, int*
    const unsigned nBlocks = L.nBlocks;
    const bool prune = L.prune;
    const LjWaveLists& wl = L.wl;
+   { ForceLegs& legs = legsOf(sim); legs.ljWaves = w; legs.ljLists = prune; legs.ljListCap = prune ? wl.candCap : 0; }
    ForceTimer timer(sim, S(stream));                     // the force kernel proper (bench.py's roofline line; rocprof must agree with it)
    if (table) {
       const TableView tv = ljTableView(sim);
@@ -901,6 +909,7 @@ static void ljForce(SimGpu* sim, int num_cells, int* cells_list, int method, com
       pl.plCut2 = (sim->lj_pot.cutoff + n->skinDistance) * (sim->lj_pot.cutoff + n->skinDistance);
 #define LAUNCH_CTA(PLV) do { if (sim->needEnergy) hipLaunchKernelGGL((LJ_Force_cta_cell<PLV, true>), dim3(num_cells), dim3(threads), lds, S(stream), a, sim->status, pl); \
                             else              hipLaunchKernelGGL((LJ_Force_cta_cell<PLV, false>), dim3(num_cells), dim3(threads), lds, S(stream), a, sim->status, pl); } while (0)
+      legsOf(sim).ljCtaForm = n->slabFormat == 3 ? 3 : tuningOf(sim).ljCtaSlabs ? 2 : 1;
       if (n->slabFormat != 3 && !tuningOf(sim).ljCtaSlabs) {
          // the default form: every wave stages its own box-pruned candidates (COMD_LJ_CTA_SLABS=1: the slab kernel, for A/B runs)
          real_t rc2Box, grow;
@@ -939,6 +948,42 @@ extern "C" void comdForcePathInfo(SimGpu* sim, int out[4])
    out[1] = sim->eam_pot.brickImageCap ? sim->eam_pot.brickImageCap : sim->eam_pot.atomBrickImageCap;
    out[2] = sim->atoms.neighborList.slabFormat;
    out[3] = (sim->eam_pot.brickBy ? sim->eam_pot.brickBy * sim->eam_pot.brickBz : sim->eam_pot.atomBrickBy * sim->eam_pot.atomBrickBz) + 256 * sim->eam_pot.brickListMakes;      // (cells per brick in the low byte, times the brick lists were made above)
+}
+
+// what the last force evaluation ran (comd_hip.h has the entries): host records of the launch wrappers, and counts taken from waveCandCount / brickStats as they stand
+extern "C" void comdForceLegReport(SimGpu* sim, int out[COMD_LEG_REPORT_N])
+{
+   for (int k = 0; k < COMD_LEG_REPORT_N; ++k) out[k] = 0;
+   HIP_CHECK(hipDeviceSynchronize());
+   const ForceLegs& g = legsOf(sim);
+   const LjPotentialGpu* lj = &sim->lj_pot;
+   out[0] = g.ljWaves; out[1] = g.ljListCap; out[2] = g.ljLists; out[7] = g.ljCtaForm;
+   if (g.ljWaves > 0) {
+      // a wave per 64-atom chunk of a local cell; LJ_WaveCandidates leaves {own-cell, all} candidates (all == -1: walk) for chunk < min(waves per cell, waveCandWaves)
+      const int nCells = sim->boxes.nLocalBoxes, wavesMax = lj->waveCandWaves;
+      std::vector<int> counts((size_t)nCells), cand;
+      HIP_CHECK(hipMemcpy(counts.data(), sim->boxes.nAtoms, counts.size() * sizeof(int), hipMemcpyDeviceToHost));
+      if (g.ljLists && lj->waveCandCount) {
+         cand.resize((size_t)nCells * wavesMax * 2);
+         HIP_CHECK(hipMemcpy(cand.data(), lj->waveCandCount, cand.size() * sizeof(int), hipMemcpyDeviceToHost));
+      }
+      int listed = 0, walked = 0, lo = 0, hi = 0;
+      for (int c = 0; c < nCells; ++c) {
+         const int chunks = (counts[c] + 63) / 64;
+         for (int k = 0; k < chunks; ++k) {
+            const int n = (!cand.empty() && k < g.ljWaves && k < wavesMax) ? cand[((size_t)c * wavesMax + k) * 2 + 1] : -1;
+            if (n < 0) { ++walked; continue; }
+            if (!listed || n < lo) lo = n;
+            if (!listed || n > hi) hi = n;
+            ++listed;
+         }
+      }
+      out[3] = listed; out[4] = walked; out[5] = lo; out[6] = hi;
+   }
+   out[8] = g.eamKernel; out[9] = g.eamBy; out[10] = g.eamBz; out[11] = g.eamImage; out[12] = g.eamBricks; out[13] = g.eamPass1Grid;
+   if (sim->eam_pot.brickStats) HIP_CHECK(hipMemcpy(&out[14], sim->eam_pot.brickStats + 2, sizeof(int), hipMemcpyDeviceToHost));
+   out[15] = g.eamRows; out[16] = g.eamPass3ReadsRows; out[17] = g.eamCover; out[18] = g.eamRunMax; out[19] = g.eamTablesInLds; out[20] = g.eamSpline;
+   out[21] = g.eamClampsKept; out[22] = g.eamStencil; out[23] = sim->atoms.neighborList.slabFormat;
 }
 
 extern "C" void updateNeighborsGpu(SimGpu*, int*) {}
@@ -1508,7 +1553,7 @@ static void buildNeighborListImpl(SimGpu* sim, int method, int boundaryFlag)
          sim->eam_pot.brickListsValid = 1;
       }
       EamArgs a = makeEamArgs(sim, sim->boxes.nLocalBoxes, nullptr);
-      if (!sim->eam_pot.brickStats) sim->eam_pot.brickStats = dalloc<int>(2);
+      if (!sim->eam_pot.brickStats) sim->eam_pot.brickStats = dalloc<int>(3);
       HIP_CHECK(hipMemsetAsync(sim->eam_pot.brickStats, 0, 2 * sizeof(int), st));
       launchEamBrick<0>(sim, a, sim->boxes.nLocalBoxes, nullptr, st, EamTablePlan(a.phi, a.rho, 0), true, THREAD_ATOM_NL);
       LAUNCH_CHECK();

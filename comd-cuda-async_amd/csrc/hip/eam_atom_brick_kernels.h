@@ -44,6 +44,11 @@ static inline size_t eamAtomBrickLdsBytes(int step, size_t tableDoubles, int ima
 }
 
 // (the scans and the per-run wave minimum run on the DPP path: waveInclusiveScan, waveMin of eam_brick_kernels.h)
+// Pass 3 evaluates an atom's pairs in one of three forms (trips from the rows in registers, trips from the rows in the LDS, the direct walk), and the forces must not
+// depend on which: tests hold the hand-over to the last bit.  Under the default contraction mode the optimiser decides per call site which products are fused into the
+// adds that follow, and in the float build the copies of evalTrip came out differently (half of all atoms a few ulps apart).  contract(on) fuses what one expression
+// writes as a * b + c and nothing across statements: every copy is the same arithmetic.
+#pragma clang fp contract(on)
 template <int STEP, bool LDS_TABLES, bool SPLINE, bool CLAMP>
 __global__ __launch_bounds__(EAM_ATOM_BRICK_THREADS, 2)
 void EAM_Force_atom_brick(EamArgs a, EamBrickArgs b)
@@ -202,7 +207,7 @@ void EAM_Force_atom_brick(EamArgs a, EamBrickArgs b)
    const int imageTotal = uniform(sMisc[4]);
    const bool fits = imageTotal <= b.imageCap;
    if (!fits) {      // a block larger than the LDS image: streaming form, a wave per cell, same tables
-      if (STEP == 1 && b.stats && tid == 0) atomicAdd(&b.stats[1], 1);
+      if (STEP == 1 && b.stats && tid == 0) { atomicAdd(&b.stats[1], 1); atomicAdd(&b.stats[2], 1); }
       for (int pick = wave; pick < nSel; pick += nWaves) {
          const int cl = sList[pick], hc = 1 + 3 * ((cl % b.by + 1) + HY * (cl / b.by + 1));
          if (STEP == 1 && b.brickSel && lane == 0) b.brickSel[sBox[hc]] = 0ull;      // no rows for this cell
@@ -444,3 +449,4 @@ void EAM_Force_atom_brick(EamArgs a, EamBrickArgs b)
       }
    }
 }
+#pragma clang fp contract(fast)      // (the default of the other kernel files)

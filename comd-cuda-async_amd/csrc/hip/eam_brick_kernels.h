@@ -77,7 +77,7 @@ struct EamBrickArgs {
    int debug;                             // experiments (COMD_EAM_ABLATE): 1 no build sweeps, 2 no pair evaluation
    int listRounds, listQuads;             // rounds of roundAtoms atoms a cell's capacity makes; 16-byte quads per lane and round (2 without lists, <= 3 with)
    real_t rBuild2;                        // STEP 0: (cutoff + skin)^2
-   int* stats;                            // [0] longest list (STEP 0), [1] bricks whose block outgrew the image, counted by STEP 0 / pass 1 (NULL: not counted)
+   int* stats;                            // [0] longest list (STEP 0), [1] bricks whose block outgrew the image, counted by STEP 0 / pass 1, [2] the same, never cleared (NULL: not counted)
    unsigned long long* brickSel;          // not listed: [local cells] the selection of its brick pass 1 wrote the cell's rows under; pass 3 must stage for the same (status[3] |= 4)
 };
 
@@ -313,7 +313,7 @@ void EAM_Force_cta_brick(EamArgs a, EamBrickArgs b)
          sp[REC * imageTotal] = FAR_AWAY; sp[REC * imageTotal + 1] = FAR_AWAY; sp[REC * imageTotal + 2] = FAR_AWAY;
          if (STEP == 3) sd[imageTotal] = R(0.0);
       }
-   } else if (STEP != 3 && b.stats && tid == 0) atomicAdd(&b.stats[1], 1);      // bricks that take the thread-per-atom form (comdEamBrickStats)
+   } else if (STEP != 3 && b.stats && tid == 0) { atomicAdd(&b.stats[1], 1); atomicAdd(&b.stats[2], 1); }      // bricks that take the thread-per-atom form (comdEamBrickStats; [2]: never cleared)
    __syncthreads();
    if (b.debug & 4) return;
 

@@ -266,7 +266,7 @@ static void eamBrickGroupLists(SimGpu* sim, const EamBrickArgs& b, hipStream_t s
 // What the brick launchers share behind their shape and rows: the statistics, the switches, and which bricks or cells of `cells_list` the launch covers.  Returns the grid.
 static int eamBrickCover(SimGpu* sim, EamBrickArgs* b, int num_cells, int* cells_list, hipStream_t st, bool listed, int method)
 {
-   if (!sim->eam_pot.brickStats) sim->eam_pot.brickStats = dalloc<int>(2);
+   if (!sim->eam_pot.brickStats) sim->eam_pot.brickStats = dalloc<int>(3);
    b->stats = sim->eam_pot.brickStats; b->fuseEmbed = sim->fuseEmbed; b->status = sim->status; b->debug = tuningOf(sim).eamAblate;
    const int group = eamBrickGroupOf(sim, cells_list, num_cells, method);
    if (listed) {           // the lists of the last list build (eamBrickBuildLists): all bricks, or the whole bricks of the boundary / interior launch
@@ -278,6 +278,8 @@ static int eamBrickCover(SimGpu* sim, EamBrickArgs* b, int num_cells, int* cells
       // every cell of a listed brick is selected: no marks to look at (the embedding pass, a kernel over cells, uses brickGroup)
       b->brickList = sim->eam_pot.brickList + (group == 1 ? 0 : sim->eam_pot.brickListStride);
    } else if (cells_list && !group) eamSelectCells(sim, cells_list, num_cells, st, b);
+   ForceLegs& legs = legsOf(sim);
+   legs.eamCover = group ? 1 : cells_list ? 2 : 0; legs.eamBy = b->by; legs.eamBz = b->bz; legs.eamBricks = eamBrickCount(*b); legs.eamRunMax = (b->debug & 16) ? 64 : 256;
    return group ? sim->eam_pot.brickCount[group - 1] : listed ? sim->eam_pot.brickCountAll : eamBrickCount(*b);
 }
 
@@ -361,6 +363,7 @@ static void launchEamAtomBrick(SimGpu* sim, const EamArgs& a, int num_cells, int
    b.listQuads = ((STEP == 3 && b.rowsG) ? 0 : 1) | (rowCap << 8);
    const size_t lds = eamAtomBrickLdsBytes(STEP, plan.tableDoubles(STEP), b.imageCap, b.rows, b.listRounds, (b.listQuads & 1) != 0) + (size_t)t.eamAtomLdsPad;      // (COMD_EAM_ATOM_LDS_PAD: experiments)
    if (lds > 160 * 1024) { fprintf(stderr, "eamForce: thread_atom needs %zu bytes of LDS for this box\n", lds); exit(-1); }
+   { ForceLegs& legs = legsOf(sim); legs.eamImage = b.imageCap; legs.eamRows = b.rows; if (STEP == 1) legs.eamPass1Grid = grid; else legs.eamPass3ReadsRows = b.rowsG != nullptr; }
    if (grid <= 0) return;
    // threads: the waves that take atoms, and enough to ask for the 16 first slots of every block cell in EAM_BRICK_STAGE rounds
    const int nThreads = (b.listRounds > 256 || 3 * (b.by + 2) * (b.bz + 2) * 16 > EAM_BRICK_STAGE * 256) ? EAM_ATOM_BRICK_THREADS : 256;
@@ -409,6 +412,7 @@ static void launchEamBrick(SimGpu* sim, const EamArgs& a, int num_cells, int* ce
    if (listed && 3 * (b.by + 2) * (b.bz + 2) * 32 > EAM_BRICK_STAGE_LISTED * 64 * waves) { fprintf(stderr, "eamForce: a brick of 1 x %d x %d cells has more cells around it than a listed launch stages\n", b.by, b.bz); exit(-1); }
    const size_t lds = eamBrickLdsBytes(STEP, listed, plan.tableDoubles(STEP), b.imageCap, b.rows, waves);
    if (lds > 160 * 1024) { fprintf(stderr, "eamForce: cta_cell needs %zu bytes of LDS for this box\n", lds); exit(-1); }
+   { ForceLegs& legs = legsOf(sim); legs.eamImage = b.imageCap; legs.eamRows = b.rows; if (STEP != 3) legs.eamPass1Grid = grid; else legs.eamPass3ReadsRows = 1; }
    if (grid <= 0) return;
    const bool tablesInLds = plan.tablesInLds(STEP), clampFree = eamClampFree(sim, a, plan.spline);
 #define COMD_LAUNCH_EAM_BRICK(STP, TAB, SPL, LST, CLP) launchLds(EAM_Force_cta_brick<STP, TAB, SPL, LST, CLP>, grid, 64 * waves, lds, st, a, b)
@@ -482,6 +486,7 @@ static void launchEamCtaCell(SimGpu* sim, const EamArgs& a, int num_cells, hipSt
    const size_t lds = ldsBytes(STEP, stencil);
    if (lds > 160 * 1024) { fprintf(stderr, "eamForce: cta_cell needs %zu bytes of LDS for this box\n", lds); exit(-1); }
    const int grid = ceilDiv(num_cells, waves * 8);        // each wave walks ~8 consecutive cells
+   { ForceLegs& legs = legsOf(sim); legs.eamStencil = stencil; legs.eamRows = rows; if (STEP == 3) legs.eamPass3ReadsRows = 1; }
 #define COMD_LAUNCH_EAM_CTA(TAB, SPL) launchLds(EAM_Force_cta_cell<STEP, TAB, SPL>, grid, 64 * waves, lds, st, a, stencil, rows, sim->eam_pot.pairRows, sim->eam_pot.pairRowCount, sim->fuseEmbed, sim->status)
    if (plan.spline)                 COMD_LAUNCH_EAM_CTA(false, true);
    else if (plan.tablesInLds(STEP)) COMD_LAUNCH_EAM_CTA(true, false);
@@ -501,16 +506,20 @@ static void launchEamPair(SimGpu* sim, int num_cells, int* cells_list, int metho
    if (spline && (!a.phiS.coefficients || !a.rhoS.coefficients)) { fprintf(stderr, "eamForce: spline != 0 but no spline tables were given to AllocateGpu\n"); exit(-1); }
    const bool lists = method == THREAD_ATOM_NL || method == WARP_ATOM_NL, atomBrick = eamAtomBrickPath(sim, method);
    if (STEP == 1 && !atomBrick) sim->eam_pot.atomRowsValid = 0;      // (another method's pass 1: the rows EAM_Force_atom_brick left are not this evaluation's)
-   if (!lists && method != CTA_CELL && !atomBrick) launchEamThreadAtom<STEP>(sim, a, num_cells, st, plan);
-   else if (atomBrick)                             launchEamAtomBrick<STEP>(sim, a, num_cells, cells_list, st, plan);
+   // what this launch runs, for comdForceLegReport (the brick launchers add their shape, image and rows)
+   ForceLegs& legs = legsOf(sim);
+   legs.eamCover = cells_list ? 2 : 0; legs.eamSpline = plan.spline; legs.eamClampsKept = !eamClampFree(sim, a, plan.spline);
+   if (STEP == 1) { legs.eamTablesInLds = plan.tablesInLds(1); legs.eamPass3ReadsRows = 0; legs.eamBy = legs.eamBz = legs.eamImage = legs.eamBricks = legs.eamPass1Grid = legs.eamRows = legs.eamStencil = 0; legs.eamRunMax = 0; }
+   if (!lists && method != CTA_CELL && !atomBrick) { legs.eamKernel = 6; launchEamThreadAtom<STEP>(sim, a, num_cells, st, plan); }
+   else if (atomBrick)                             { legs.eamKernel = 2; launchEamAtomBrick<STEP>(sim, a, num_cells, cells_list, st, plan); }
    else if (eamListedBrick(sim, method)) {
       if (sim->atoms.neighborList.nBuilds == 0) { fprintf(stderr, "the *_nl methods need buildNeighborListGpu before the first force call\n"); exit(-1); }
-      launchEamBrick<STEP>(sim, a, num_cells, cells_list, st, plan, true, method);
+      legs.eamKernel = 4; launchEamBrick<STEP>(sim, a, num_cells, cells_list, st, plan, true, method);
    }
-   else if (lists && sim->atoms.neighborList.slabFormat == 2) launchEamNlLds<STEP>(sim, a, num_cells, st, plan);
-   else if (lists)                                 launchEamThreadAtomNl<STEP>(sim, a, num_cells, st, plan);
-   else if (eamBrickPath(sim, method))             launchEamBrick<STEP>(sim, a, num_cells, cells_list, st, plan, false, method);
-   else                                            launchEamCtaCell<STEP>(sim, a, num_cells, st, plan);
+   else if (lists && sim->atoms.neighborList.slabFormat == 2) { legs.eamKernel = 5; launchEamNlLds<STEP>(sim, a, num_cells, st, plan); }
+   else if (lists)                                 { legs.eamKernel = 7; launchEamThreadAtomNl<STEP>(sim, a, num_cells, st, plan); }
+   else if (eamBrickPath(sim, method))             { legs.eamKernel = 1; launchEamBrick<STEP>(sim, a, num_cells, cells_list, st, plan, false, method); }
+   else                                            { legs.eamKernel = 3; launchEamCtaCell<STEP>(sim, a, num_cells, st, plan); }
    LAUNCH_CHECK();
 }
 

@@ -111,7 +111,8 @@ typedef struct EamPotentialGpuSt {
    /* [round 4] per cell, the selection (64-bit mask of the brick's cells) its brick was staged for when pass 1 wrote the cell's rows; pass 3 of the same force evaluation must be launched over
     * the same partition of the cells -- the 16-bit numbers in pairRows index an image whose composition depends on it -- and raises status[3] bit 2 otherwise */
    unsigned long long* brickSel;       /* device [nLocalBoxes] */
-   int*    brickStats;                 /* device [2]: {longest Verlet row of the last list build, bricks that took the thread-per-atom form since the last comdEamBrickStats} */
+   int*    brickStats;                 /* device [3]: {longest Verlet row of the last list build, bricks that took the thread-per-atom form since the last comdEamBrickStats,
+                                        * the same count never cleared (comdForceLegReport)} */
    int     brickBy, brickBz;           /* host: the brick shape of this simulation (fixed by the first launch: rows index the image of that shape) */
    /* [round 4] method thread_atom (EAM_Force_atom_brick, hip/eam_atom_brick_kernels.h): thread per atom inside a brick workgroup; a shape and an image of its own */
    int     atomBrickBy, atomBrickBz;   /* host: brick shape (0: chosen by the first launch) */
@@ -241,6 +242,7 @@ typedef struct SimGpuSt {
    int64_t*     dispBuf;               /* device [dispN][4]: displacement records by gid (comdTrackDisplacementGpu), NULL = not tracking */
    double*      dispSumBuf;            /* device: the workgroups' partial sums for computeDisplacementSums, allocated with dispBuf */
    int          dispN;                 /* records dispBuf holds = nGlobal */
+   void*        legs;                  /* private to the device library: what the last force launches of this simulation ran (hip/comd_device.hip ForceLegs, comdForceLegReport) */
 } SimGpu;
 
 /* Everything AllocateGpu needs to know about the rank's geometry and potential.
@@ -372,6 +374,22 @@ void comdEamBrickResize(SimGpu* sim);
 /* what the force wrappers decided for this simulation: {LJ thread_atom candidate lists in use (0: the plain 27-cell walk -- lists did not fit the device memory),
  * records of the EAM brick image, Verlet-list format (NeighborListGpu.slabFormat), cells per EAM brick + 256 x the times the brick lists of the list method were made} */
 void comdForcePathInfo(SimGpu* sim, int out[4]);
+/* What the LAST force evaluation of this simulation ran, for tests that must know a forced leg was taken: written down by the launch wrappers as they launch (host
+ * state) and counted from the small device arrays they fill anyway.  Waits for the device, launches nothing, clears nothing.  out[] (unused entries are 0):
+ *  [0] LJ thread_atom: waves per cell of the launch   [1] entries a candidate row holds   [2] candidate lists used by the launch (0: the 27-cell walk)
+ *  [3] waves (64-atom chunks of the local cells) that read a list   [4] waves that walked the stencil   [5], [6] fewest / most candidates of a listed wave
+ *  [7] LJ cta_cell form: 1 box-pruned, 2 slabs, 3 pairlist bits (-L)
+ *  [8] EAM pair kernel: 1 brick (cta_cell), 2 thread per atom on the brick image (thread_atom), 3 round 2's cta_cell kernel, 4 brick kernel on Verlet rows,
+ *      5 round 3's list kernel (COMD_EAM_NL=lds), 6 round 2's thread_atom kernel, 7 lists of global slots
+ *  [9], [10] brick shape by, bz   [11] records of the brick's LDS image   [12] bricks that cover all local cells   [13] workgroups of the last pass-1 launch
+ *  [14] bricks whose block outgrew the image (streaming / thread-per-atom form), counted by every pass 1 since AllocateGpu and never cleared: the difference
+ *       of two reports is the count of the evaluations in between   [15] entries of a row (thread_atom: of a thread)   [16] pass 3 read the rows of pass 1
+ *  [17] what the launch covered: 0 all local cells, 1 the whole bricks of the boundary or interior group, 2 a cell list taken cell by cell
+ *  [18] longest stencil run a thread_atom row addresses with byte offsets (256; 64 under COMD_EAM_ABLATE=16)   [19] phi / rho tables staged in the LDS (pass 1)
+ *  [20] spline tables (-P)   [21] the table clamps of interpolate() kept   [22] records of the LDS slice of round 2's cta_cell kernel
+ *  [23] Verlet-list format (NeighborListGpu.slabFormat) */
+#define COMD_LEG_REPORT_N 32
+void comdForceLegReport(SimGpu* sim, int out[COMD_LEG_REPORT_N]);
 /* updateNeighborsGpu[Async], gpu_kernels.cu:251-279: the reference materialises 27*MAXATOMS neighbour
  * offsets per cell for its cta_cell/warp_atom EAM kernels; ours gather from the cell table directly,
  * so these are no-ops kept for link compatibility. */

@@ -10,6 +10,8 @@ import os
 import numpy as np
 import pytest
 
+import test_kernel_legs as legs          # the facts a leg asserts from Simulation.force_leg_report() and from the run's own occupancies
+
 pytestmark = pytest.mark.gpu
 
 G = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "reference_values.json")))
@@ -22,6 +24,10 @@ METHODS = ["thread_atom", "cta_cell"]
 def _args(n, eam=0, delta=0.0, method="thread_atom", extra=()):
     nx, ny, nz = (n, n, n) if isinstance(n, int) else n
     return ["-x", nx, "-y", ny, "-z", nz, "-r", delta, "-m", method] + (["-e"] if eam else []) + list(extra)
+
+
+def _box(n, flags=()):
+    return {"n": (n, n, n) if isinstance(n, int) else n, "flags": list(flags)}
 
 
 def _per_atom(sim):
@@ -91,6 +97,7 @@ def test_lj_cells_larger_than_the_launch_estimate(gpu, orc, monkeypatch):
         fo = o.gather(orc.F)
         assert np.abs(sim.gather(2) - fo).max() <= 1e-10 * np.abs(fo).max()
         assert np.abs(sim.gather(3) - o.gather(orc.U)).max() <= TOL["per_atom_energy_abs"]
+        legs.lj_one_wave(legs.observe(sim, _box(10)))      # one wave per cell, cells of more than 64 atoms
 
 
 @pytest.mark.parametrize("env", [{}, {"COMD_LJ_CTA_SLABS": "1"}])
@@ -107,20 +114,32 @@ def test_lj_cta_cell_both_forms(gpu, orc, monkeypatch, env):
         fo = o.gather(orc.F)
         assert np.abs(sim.gather(2) - fo).max() <= TOL["force_rel_to_max"] * np.abs(fo).max()
         assert np.abs(sim.gather(3) - o.gather(orc.U)).max() <= TOL["per_atom_energy_abs"]
+        legs.lj_cta_form("slabs" if env else "boxes")(legs.observe(sim, _box((12, 10, 11))))
 
 
-@pytest.mark.parametrize("env", [{"COMD_EAM_IMAGE": "128"}, {"COMD_EAM_IMAGE": "1000"}, {"COMD_EAM_BRICK": "2,2"}, {"COMD_EAM_BRICK": "3,5"},
-                                 {"COMD_EAM_CTA": "cell", "COMD_EAM_STENCIL": "128"}, {"COMD_EAM_CTA": "cell", "COMD_EAM_STENCIL": "368"}, {"COMD_EAM_CTA": "cell"}])
-def test_eam_cells_whose_stencil_outgrows_the_lds_slice(gpu, orc, monkeypatch, env):
+STENCIL_LEGS = [({"COMD_EAM_IMAGE": "128"}, legs.eam_kernel("brick", extra=legs.brick_all_streamed)),
+                ({"COMD_EAM_IMAGE": "800"}, legs.eam_kernel("brick", extra=legs.brick_some_streamed(800))),
+                ({"COMD_EAM_BRICK": "2,2"}, legs.eam_kernel("brick", extra=legs.brick_shape(2, 2))),
+                ({"COMD_EAM_BRICK": "3,5"}, legs.eam_kernel("brick", extra=legs.brick_shape(3, 5))),
+                ({"COMD_EAM_CTA": "cell", "COMD_EAM_STENCIL": "128"}, legs.eam_kernel("cta_cell_round2", extra=legs.stencil_slice(128, "all"))),
+                ({"COMD_EAM_CTA": "cell", "COMD_EAM_STENCIL": "320"}, legs.eam_kernel("cta_cell_round2", extra=legs.stencil_slice(320, "some"))),
+                ({"COMD_EAM_CTA": "cell"}, legs.eam_kernel("cta_cell_round2", extra=legs.stencil_slice(0, "none")))]
+
+
+@pytest.mark.parametrize("env,fact", STENCIL_LEGS, ids=[f"env{k}" for k in range(len(STENCIL_LEGS))])
+def test_eam_cells_whose_stencil_outgrows_the_lds_slice(gpu, orc, monkeypatch, env, fact):
     """cta_cell stages the cells around a brick in an LDS image sized from the fullest block the first launch finds; a brick whose block holds more
     atoms than the image is walked thread-per-atom by the same workgroup, in pass 1 AND pass 3 (no rows are handed over for it).  COMD_EAM_IMAGE
-    forces an image that every brick (128) or part of the bricks (1000; the blocks of this box hold 860-1170 atoms) outgrow; COMD_EAM_BRICK
-    other brick shapes, one that does not divide the grid; COMD_EAM_CTA=cell round 2's kernel (a wave stages every cell's stencil for itself), with
-    its own slice-overflow legs."""
+    forces an image that every brick (128) or part of the bricks (800) outgrow; COMD_EAM_BRICK other brick shapes, one that does not divide the grid;
+    COMD_EAM_CTA=cell round 2's kernel (a wave stages every cell's stencil for itself), with its own slice-overflow legs (128: every cell, 320: part of
+    them).  The two "part of" legs run on 12 x 11 x 13: the cells of 12^3 are 1.5 lattice cells wide, every block of it holds 972 atoms and every
+    stencil 364 or 365, so no image and no slice (multiples of 8) splits them; on 12 x 11 x 13 the blocks hold 680-700 or 840-920 atoms and the stencils
+    288 to 359.  Every leg asserts what it took from the report of one more evaluation."""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    with gpu.Simulation(_args(12, 1, 0.1, "cta_cell")) as sim:
-        o = orc.Oracle(12, eam=1, delta=0.1, cap=max(sim.max_atoms, 64))
+    n = (12, 11, 13) if env.get("COMD_EAM_IMAGE") == "800" or env.get("COMD_EAM_STENCIL") == "320" else 12
+    with gpu.Simulation(_args(n, 1, 0.1, "cta_cell")) as sim:
+        o = orc.Oracle(n, eam=1, delta=0.1, cap=max(sim.max_atoms, 64))
         sim.step(3)
         o.step(3)
         fo = o.gather(orc.F)
@@ -128,10 +147,16 @@ def test_eam_cells_whose_stencil_outgrows_the_lds_slice(gpu, orc, monkeypatch, e
         assert np.abs(sim.gather(3) - o.gather(orc.U)).max() <= TOL["per_atom_energy_abs"]
         assert np.abs(sim.gather(4) - o.gather(orc.RHOBAR)).max() < TOL["eam_density_abs"]
         assert np.abs(sim.gather(5) - o.gather(orc.DFEMBED)).max() < TOL["eam_dfembed_abs"]
+        fact(legs.observe(sim, _box(n)))
 
 
-@pytest.mark.parametrize("env", [{"COMD_LJ_PRUNE": "0"}, {"COMD_LJ_LIST_CAP": "64"}, {"COMD_LJ_LIST_CAP": "2200"}, {"COMD_LJ_LIST_BUDGET_MB": "1"}, {}])
-def test_lj_wave_candidate_lists_and_their_fallbacks(gpu, orc, monkeypatch, env):
+LIST_CAP_MIXED = 2200
+LIST_LEGS = [({"COMD_LJ_PRUNE": "0"}, legs.lj_lists_inactive), ({"COMD_LJ_LIST_CAP": "64"}, legs.lj_rows_too_short),
+             ({"COMD_LJ_LIST_CAP": str(LIST_CAP_MIXED)}, legs.lj_rows_mixed(LIST_CAP_MIXED)), ({"COMD_LJ_LIST_BUDGET_MB": "1"}, legs.lj_lists_inactive), ({}, legs.lj_lists_all)]
+
+
+@pytest.mark.parametrize("env,fact", LIST_LEGS, ids=[f"env{k}" for k in range(len(LIST_LEGS))])
+def test_lj_wave_candidate_lists_and_their_fallbacks(gpu, orc, monkeypatch, env, fact):
     """thread_atom tests only the stencil atoms within the cutoff of each wave's bounding box (LJ_WaveCandidates).  The four legs: lists
     off (the plain 27-cell walk), rows too short for any wave (every wave falls back to the walk), rows that fit the tail waves' lists but
     not the full waves' (both paths inside one launch), and the default.  All four must give the oracle's forces."""
@@ -144,10 +169,15 @@ def test_lj_wave_candidate_lists_and_their_fallbacks(gpu, orc, monkeypatch, env)
         f, fo = sim.gather(2), o.gather(orc.F)
         assert np.abs(f - fo).max() <= TOL["force_rel_to_max"] * np.abs(fo).max()
         assert np.abs(sim.gather(3) - o.gather(orc.U)).max() <= TOL["per_atom_energy_abs"]
+        fact(legs.observe(sim, _box((12, 10, 11))))
 
 
-@pytest.mark.parametrize("env", [{}, {"COMD_EAM_GROUPS": "0"}, {"COMD_EAM_BRICK": "2,3"}])
-def test_eam_overlap_mode_takes_whole_bricks(gpu, orc, monkeypatch, env):
+OVERLAP_LEGS = [({}, legs.eam_kernel("brick", "whole_bricks")), ({"COMD_EAM_GROUPS": "0"}, legs.eam_kernel("brick", "cell_by_cell")),
+                ({"COMD_EAM_BRICK": "2,3"}, legs.eam_kernel("brick", "whole_bricks", extra=legs.atom_shape(2, 3)))]
+
+
+@pytest.mark.parametrize("env,fact", OVERLAP_LEGS, ids=[f"env{k}" for k in range(len(OVERLAP_LEGS))])
+def test_eam_overlap_mode_takes_whole_bricks(gpu, orc, monkeypatch, env, fact):
     """-a 1 launches every EAM pass once over the boundary cells and once over the interior cells.  cta_cell makes that split at brick
     granularity (every cell of a brick that holds a boundary cell goes with the boundary launch: no brick is staged twice per pass;
     eam_launch.h eamBrickGroupOf).  Forces, energies, densities and dF/drho after three steps must be the oracle's -- with the groups,
@@ -163,23 +193,33 @@ def test_eam_overlap_mode_takes_whole_bricks(gpu, orc, monkeypatch, env):
         assert np.abs(sim.gather(3) - o.gather(orc.U)).max() <= TOL["per_atom_energy_abs"]
         assert np.abs(sim.gather(4) - o.gather(orc.RHOBAR)).max() < TOL["eam_density_abs"]
         assert np.abs(sim.gather(5) - o.gather(orc.DFEMBED)).max() < TOL["eam_dfembed_abs"]
+        fact(legs.observe(sim, _box((14, 12, 13))))
+
+
+ATOM_IMAGE_MIXED = 1100
+# (env, the fact of the leg, its fact under -a 1 when that differs)
+ATOM_LEGS = [({}, legs.hand_over(True)), ({"COMD_EAM_ATOM_HANDOVER": "0"}, legs.hand_over(False)), ({"COMD_EAM_IMAGE": "128"}, legs.brick_all_streamed),
+             ({"COMD_EAM_IMAGE": str(ATOM_IMAGE_MIXED)}, legs.brick_some_streamed(ATOM_IMAGE_MIXED)), ({"COMD_EAM_ATOM_BRICK": "2,3"}, legs.atom_shape(2, 3)),
+             ({"COMD_EAM_ATOM_BRICK": "4,5"}, legs.atom_shape(4, 5)), ({"COMD_EAM_ATOM_ROWS": "16"}, legs.rows_capacity(16, 1.0, 1.0)),
+             ({"COMD_EAM_ATOM_ROWS": "48"}, legs.rows_capacity(48, 0.1, 0.9)), ({"COMD_EAM_THREAD_ATOM": "cell"}, None), ({"COMD_EAM_GROUPS": "0"}, None),
+             ({"COMD_EAM_ABLATE": "16"}, legs.offset_limit_64)]
 
 
 @pytest.mark.parametrize("overlap", [0, 1])
-@pytest.mark.parametrize("env", [{}, {"COMD_EAM_ATOM_HANDOVER": "0"}, {"COMD_EAM_IMAGE": "128"}, {"COMD_EAM_IMAGE": "1500"}, {"COMD_EAM_ATOM_BRICK": "2,3"},
-                                 {"COMD_EAM_ATOM_BRICK": "4,5"}, {"COMD_EAM_ATOM_ROWS": "16"}, {"COMD_EAM_ATOM_ROWS": "48"}, {"COMD_EAM_THREAD_ATOM": "cell"}, {"COMD_EAM_GROUPS": "0"}, {"COMD_EAM_ABLATE": "16"}])
-def test_eam_thread_atom_on_the_brick_image(gpu, orc, monkeypatch, env, overlap):
+@pytest.mark.parametrize("env,fact", ATOM_LEGS, ids=[f"env{k}" for k in range(len(ATOM_LEGS))])
+def test_eam_thread_atom_on_the_brick_image(gpu, orc, monkeypatch, env, fact, overlap):
     """-m thread_atom -e: a thread per atom inside a brick workgroup (eam_atom_brick_kernels.h).  Legs: the default; pass 3 testing again instead of reading
-    the rows of pass 1; an image every brick (128 records) or part of the bricks (1500) outgrow -- those take the streaming form, in both passes; brick shapes
+    the rows of pass 1; an image every brick (128 records) or part of the bricks (1100) outgrow -- those take the streaming form, in both passes; brick shapes
     that do not divide the grid / fill all four waves; rows shorter than the neighbour count of every atom (16: each walks its stencil a second time) or of
-    some atoms (48); stencil runs too long for byte offsets (COMD_EAM_ABLATE=16 lowers the limit from 256 records to 64: every atom walks without a row, in both
+    some atoms (48, on the lattice compressed to -l 3.5: a third of its atoms have 49 to 53 neighbours; at 3.615 A fewer than one atom in a thousand has); stencil runs too long for byte offsets (COMD_EAM_ABLATE=16 lowers the limit from 256 records to 64: every atom walks without a row, in both
     passes); round 2's kernel; the lists of -a 1 taken cell by cell (COMD_EAM_GROUPS=0: bricks that hold cells of both lists are staged under two
     selections, the hand-over must notice) instead of as whole bricks.  Each without and with -a 1 (every pass once over the boundary and once over the
-    interior cells).  Forces, energies, densities, dF/drho against the oracle."""
+    interior cells).  Forces, energies, densities, dF/drho against the oracle, and the leg's fact from the report of one more evaluation."""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    with gpu.Simulation(_args((14, 12, 13), 1, 0.2, "thread_atom", extra=("-a", overlap))) as sim:
-        o = orc.Oracle((14, 12, 13), eam=1, delta=0.2, cap=max(sim.max_atoms, 64))
+    lat = ["-l", 3.5] if "COMD_EAM_ATOM_ROWS" in env and env["COMD_EAM_ATOM_ROWS"] == "48" else []
+    with gpu.Simulation(_args((14, 12, 13), 1, 0.2, "thread_atom", extra=["-a", overlap] + lat)) as sim:
+        o = orc.Oracle((14, 12, 13), eam=1, delta=0.2, cap=max(sim.max_atoms, 64), **({"lat": 3.5} if lat else {}))
         sim.step(3)
         o.step(3)
         fo = o.gather(orc.F)
@@ -187,6 +227,9 @@ def test_eam_thread_atom_on_the_brick_image(gpu, orc, monkeypatch, env, overlap)
         assert np.abs(sim.gather(3) - o.gather(orc.U)).max() <= TOL["per_atom_energy_abs"]
         assert np.abs(sim.gather(4) - o.gather(orc.RHOBAR)).max() < TOL["eam_density_abs"]
         assert np.abs(sim.gather(5) - o.gather(orc.DFEMBED)).max() < TOL["eam_dfembed_abs"]
+        round2, cell_by_cell = env.get("COMD_EAM_THREAD_ATOM") == "cell", overlap and (env.get("COMD_EAM_GROUPS") == "0" or env.get("COMD_EAM_THREAD_ATOM") == "cell")
+        legs.eam_kernel("thread_atom_round2" if round2 else "atom_brick", "cell_by_cell" if cell_by_cell else "whole_bricks" if overlap else "all_cells", extra=fact)(
+            legs.observe(sim, _box((14, 12, 13), lat)))
 
 
 def test_eam_thread_atom_hand_over_changes_no_bit(gpu, monkeypatch):

@@ -260,12 +260,12 @@ def test_trajectories_agree_across_paths(gpu):
 
 @pytest.mark.gpu
 def test_single_precision_build():
-    """One leg of the force test in the float build (lib*_sp.so), at the float tolerances."""
+    """The force test (all five legs, both boxes) and both Verlet-list formats in the float build (lib*_sp.so), at the float tolerances."""
     env = dict(os.environ, COMD_PRECISION="single")
     cmd = [sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider", "tests/test_lj_interpolation.py",
-           "-k", "test_one_evaluation_matches_the_restatement and thread_atom-lists"]
+           "-k", "test_one_evaluation_matches_the_restatement or test_both_verlet_list_formats"]
     proc = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
-    assert proc.returncode == 0 and "2 passed" in proc.stdout, proc.stdout[-3000:] + proc.stderr[-2000:]
+    assert proc.returncode == 0 and "12 passed" in proc.stdout, proc.stdout[-3000:] + proc.stderr[-2000:]
 
 
 FORCE_CALL = """

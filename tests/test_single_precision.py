@@ -5,11 +5,16 @@ with COMD_PRECISION=single: the product loads lib*_sp.so, the checker loads orac
 real_t = float) and the tolerances are tests/golden/reference_values.json "tolerances_single" (their derivation is written there).
 Index work -- lattice, momenta, cell membership, gid order, halo images -- stays bit-exact in either precision.
 """
+import json
 import os
+import re
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+
+from test_kernel_legs import FAMILY_LEG_COUNT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "comd-cuda-async_amd", "csrc")
@@ -56,6 +61,45 @@ def test_single_precision_gpu_parity():
          "or test_halo_cells_are_periodic_images or test_neighbor_list_global_slot_format")
     out = _run(["tests/test_gpu_parity.py"], k, "gpu", 1500)
     assert "passed" in out and "failed" not in out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("family", ["lj", "eam_cta", "eam_atom", "lists", "tables", "pairloss"])
+def test_single_precision_kernel_legs(family):
+    """Every forced leg of tests/test_kernel_legs.py in the float build, a family per child process.  Float changes which leg a run takes (every LDS size is
+    n * sizeof(real_t)), so each leg asserts its fact there as well; the count of passed tests must be the family's leg count from the same table: none skipped."""
+    out = _run(["tests/test_kernel_legs.py"], family, "gpu", 300)
+    passed = re.search(r"(\d+) passed", out)
+    assert passed and int(passed.group(1)) == FAMILY_LEG_COUNT[family] and "skipped" not in out and "failed" not in out, out[-1500:]
+
+
+SPLINE_CASE = r"""
+import sys
+import numpy as np
+sys.path.insert(0, %r)
+import oracle_binding as ob
+o = ob.Oracle((8, 7, 9), eam=1, delta=0.1, spline=True)
+np.savez(sys.argv[1], f=o.gather(ob.F), u=o.gather(ob.U), rho=o.gather(ob.RHOBAR), df=o.gather(ob.DFEMBED), e=o.energy()[0] / o.n_global)
+"""
+
+
+def test_single_precision_spline_tolerances_are_four_times_the_checkers_distance(tmp_path):
+    """tests/golden/reference_values.json "tolerances_single_spline" states its rule: 4x the distance of the float checker from the double checker on EAM 8 x 7 x 9, -r 0.1,
+    -P.  Both checkers are run here (a child process each: one precision per process) and every recorded value must lie within [4x, 8x] of the distance found."""
+    got = {}
+    for precision in ("double", "single"):
+        path = str(tmp_path / f"{precision}.npz")
+        proc = subprocess.run([sys.executable, "-c", SPLINE_CASE % os.path.join(ROOT, "tests"), path], cwd=ROOT, env=dict(os.environ, COMD_PRECISION=precision),
+                              capture_output=True, text=True, timeout=300)
+        assert proc.returncode == 0, proc.stderr[-1500:]
+        got[precision] = np.load(path)
+    d, s = got["double"], got["single"]
+    distance = {"force_rel_to_max": np.abs(d["f"] - s["f"]).max() / np.abs(d["f"]).max(), "per_atom_energy_abs": np.abs(d["u"] - s["u"]).max(),
+                "eam_density_abs": np.abs(d["rho"] - s["rho"]).max(), "eam_dfembed_abs": np.abs(d["df"] - s["df"]).max(), "energy_per_atom_step0": abs(float(d["e"]) - float(s["e"]))}
+    recorded = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_values.json")))["tolerances_single_spline"]
+    assert set(recorded) - {"_about"} == set(distance)
+    for key, dist in distance.items():
+        assert 4.0 * dist <= recorded[key] <= 8.0 * dist, (key, float(dist), recorded[key])
 
 
 @pytest.mark.gpu
