@@ -377,7 +377,9 @@ class Simulation:
                 "eam_kernel": self._EAM_KERNELS[out[8]], "eam_brick_shape": (out[9], out[10]), "eam_image_records": out[11], "eam_bricks": out[12],
                 "eam_pass1_workgroups": out[13], "eam_bricks_streamed_total": out[14], "eam_row_capacity": out[15], "eam_pass3_read_rows": bool(out[16]),
                 "eam_cover": self._EAM_COVERS[out[17]], "eam_byte_offset_limit": out[18], "eam_tables_in_lds": bool(out[19]), "eam_spline": bool(out[20]),
-                "eam_clamps_kept": bool(out[21]), "eam_stencil_records": out[22], "neighbor_list_format": out[23]}
+                "eam_clamps_kept": bool(out[21]), "eam_stencil_records": out[22], "neighbor_list_format": out[23], "lj_prefetch": bool(out[24]),
+                "lj_full_waves_listed": out[25], "lj_full_rows_not_multiple_of_64": out[26], "lj_full_rows_own_part_not_multiple_of_8": out[27],
+                "lj_full_rows_min": out[28], "lj_prefetch_distance": out[29]}
 
     # --- results ---
     def energy(self):

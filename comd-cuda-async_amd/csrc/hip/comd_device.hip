@@ -60,6 +60,7 @@ struct ComdTuning {
    bool   eamNlLds;            // COMD_EAM_NL=lds               round 3's EAM list kernel (a wave stages every cell's stencil), not rows of the brick kernel  off
    int    ljWaves;             // COMD_LJ_WAVES=k (> 0)         at most k waves per cell in LJ_Force_thread_atom (tests: the extra-chunk path)              cap/64
    bool   ljPrune;             // COMD_LJ_PRUNE=0               LJ thread_atom walks all 27 cells, no candidate lists                                       lists
+   bool   ljPrefetch;          // COMD_LJ_PREFETCH=0            LJ thread_atom reads its candidate lists without the vector-side L2 prefetch (A/B runs)     prefetch
    int    ljListCap;           // COMD_LJ_LIST_CAP=n (> 0)      candidate rows of n entries, rounded up to 8 (tests: rows too short fall back to the walk)  70 % of a stencil
    double ljListBudgetMb;      // COMD_LJ_LIST_BUDGET_MB=x      memory the LJ candidate lists may take (tests: the fallback to the plain walk)              what is free
    bool   ljCtaSlabs;          // COMD_LJ_CTA_SLABS=1           LJ cta_cell in its slab form                                                                box-pruned form
@@ -93,6 +94,7 @@ static ComdTuning readTuning()
    t.eamNlLds = is("COMD_EAM_NL", "lds");
    t.ljWaves = num("COMD_LJ_WAVES") > 0 ? num("COMD_LJ_WAVES") : 0;
    t.ljPrune = !isZero("COMD_LJ_PRUNE");
+   t.ljPrefetch = !isZero("COMD_LJ_PREFETCH");
    t.ljListCap = num("COMD_LJ_LIST_CAP") > 0 ? (num("COMD_LJ_LIST_CAP") + 7) & ~7 : 0;
    t.ljListBudgetMb = env("COMD_LJ_LIST_BUDGET_MB") ? atof(env("COMD_LJ_LIST_BUDGET_MB")) : INFINITY;
    t.ljCtaSlabs = num("COMD_LJ_CTA_SLABS") != 0;
@@ -119,7 +121,7 @@ static ComdTuning readTuning()
 static const ComdTuning& tuningOf(SimGpu* sim) { if (!sim->tuning) sim->tuning = new ComdTuning(readTuning()); return *(const ComdTuning*)sim->tuning; }
 // ---- what the last force launches ran (comdForceLegReport): written down by the launch wrappers, per simulation, SimGpu.legs ----
 struct ForceLegs {
-   int ljWaves, ljListCap, ljLists, ljCtaForm;
+   int ljWaves, ljListCap, ljLists, ljCtaForm, ljPrefetch;
    int eamKernel, eamBy, eamBz, eamImage, eamBricks, eamPass1Grid, eamRows, eamPass3ReadsRows, eamCover, eamRunMax, eamTablesInLds, eamSpline, eamClampsKept, eamStencil;
 };
 static ForceLegs& legsOf(SimGpu* sim) { if (!sim->legs) sim->legs = new ForceLegs(); return *(ForceLegs*)sim->legs; }
@@ -835,7 +837,8 @@ static void launchLjThreadAtom(SimGpu* sim, const LjArgs& a, int num_cells, int*
    const unsigned nBlocks = L.nBlocks;
    const bool prune = L.prune;
    const LjWaveLists& wl = L.wl;
-   { ForceLegs& legs = legsOf(sim); legs.ljWaves = w; legs.ljLists = prune; legs.ljListCap = prune ? wl.candCap : 0; }
+   const bool prefetch = prune && !table && tuningOf(sim).ljPrefetch;      // (the -I kernel has a list loop of its own, without the prefetch)
+   { ForceLegs& legs = legsOf(sim); legs.ljWaves = w; legs.ljLists = prune; legs.ljListCap = prune ? wl.candCap : 0; legs.ljPrefetch = prefetch; }
    ForceTimer timer(sim, S(stream));                     // the force kernel proper (bench.py's roofline line; rocprof must agree with it)
    if (table) {
       const TableView tv = ljTableView(sim);
@@ -843,12 +846,12 @@ static void launchLjThreadAtom(SimGpu* sim, const LjArgs& a, int num_cells, int*
       if (prune) { if (sim->needEnergy) LAUNCH_TABLE(true, true);  else LAUNCH_TABLE(false, true); }
       else       { if (sim->needEnergy) LAUNCH_TABLE(true, false); else LAUNCH_TABLE(false, false); }
 #undef LAUNCH_TABLE
-   } else if (prune) {
-      if (sim->needEnergy) hipLaunchKernelGGL((LJ_Force_thread_atom<true, true>), dim3(nBlocks), dim3(64 * wavesPerBlock), 0, S(stream), a, w, wl);
-      else              hipLaunchKernelGGL((LJ_Force_thread_atom<false, true>), dim3(nBlocks), dim3(64 * wavesPerBlock), 0, S(stream), a, w, wl);
    } else {
-      if (sim->needEnergy) hipLaunchKernelGGL((LJ_Force_thread_atom<true, false>), dim3(nBlocks), dim3(64 * wavesPerBlock), 0, S(stream), a, w, wl);
-      else              hipLaunchKernelGGL((LJ_Force_thread_atom<false, false>), dim3(nBlocks), dim3(64 * wavesPerBlock), 0, S(stream), a, w, wl);
+#define LAUNCH_LJ(K) hipLaunchKernelGGL((K), dim3(nBlocks), dim3(64 * wavesPerBlock), 0, S(stream), a, w, wl)
+      if (prefetch)   { if (sim->needEnergy) LAUNCH_LJ((LJ_Force_thread_atom<true, true>));   else LAUNCH_LJ((LJ_Force_thread_atom<false, true>)); }
+      else if (prune) { if (sim->needEnergy) LAUNCH_LJ(LJ_Force_thread_atom_plain<true>);     else LAUNCH_LJ(LJ_Force_thread_atom_plain<false>); }
+      else            { if (sim->needEnergy) LAUNCH_LJ((LJ_Force_thread_atom<true, false>));  else LAUNCH_LJ((LJ_Force_thread_atom<false, false>)); }
+#undef LAUNCH_LJ
    }
    LAUNCH_CHECK();
 }
@@ -968,6 +971,7 @@ extern "C" void comdForceLegReport(SimGpu* sim, int out[COMD_LEG_REPORT_N])
          HIP_CHECK(hipMemcpy(cand.data(), lj->waveCandCount, cand.size() * sizeof(int), hipMemcpyDeviceToHost));
       }
       int listed = 0, walked = 0, lo = 0, hi = 0;
+      int full = 0, fullOdd = 0, fullOddSelf = 0, fullLo = 0;       // the listed waves of more than 32 atoms: the ones that run ljListLoop
       for (int c = 0; c < nCells; ++c) {
          const int chunks = (counts[c] + 63) / 64;
          for (int k = 0; k < chunks; ++k) {
@@ -976,14 +980,21 @@ extern "C" void comdForceLegReport(SimGpu* sim, int out[COMD_LEG_REPORT_N])
             if (!listed || n < lo) lo = n;
             if (!listed || n > hi) hi = n;
             ++listed;
+            if (counts[c] - 64 * k > 32) {
+               if (!full || n < fullLo) fullLo = n;
+               ++full;
+               if (n % 64) ++fullOdd;
+               if (cand[((size_t)c * wavesMax + k) * 2] % 8) ++fullOddSelf;
+            }
          }
       }
       out[3] = listed; out[4] = walked; out[5] = lo; out[6] = hi;
+      out[25] = full; out[26] = fullOdd; out[27] = fullOddSelf; out[28] = fullLo; out[29] = LJ_PREFETCH_D;
    }
    out[8] = g.eamKernel; out[9] = g.eamBy; out[10] = g.eamBz; out[11] = g.eamImage; out[12] = g.eamBricks; out[13] = g.eamPass1Grid;
    if (sim->eam_pot.brickStats) HIP_CHECK(hipMemcpy(&out[14], sim->eam_pot.brickStats + 2, sizeof(int), hipMemcpyDeviceToHost));
    out[15] = g.eamRows; out[16] = g.eamPass3ReadsRows; out[17] = g.eamCover; out[18] = g.eamRunMax; out[19] = g.eamTablesInLds; out[20] = g.eamSpline;
-   out[21] = g.eamClampsKept; out[22] = g.eamStencil; out[23] = sim->atoms.neighborList.slabFormat;
+   out[21] = g.eamClampsKept; out[22] = g.eamStencil; out[23] = sim->atoms.neighborList.slabFormat; out[24] = g.ljPrefetch;
 }
 
 extern "C" void updateNeighborsGpu(SimGpu*, int*) {}

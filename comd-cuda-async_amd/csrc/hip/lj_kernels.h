@@ -103,14 +103,40 @@ template <bool SELF, bool ENERGY>
 __device__ __forceinline__ void ljListTest(const LjArgs& a, const LjPos4& q, real_t xi, real_t yi, real_t zi, real_t& fx, real_t& fy, real_t& fz, real_t& e)
 {
    real_t dx = xi - q.x, dy = yi - q.y, dz = zi - q.z;
-   real_t r2 = dx*dx + dy*dy + dz*dz;
+   // r^2 = dx dx + dy dy + dz dz with its roundings written out.  Left to -ffp-contract=fast, hipcc fused it one way in the float kernel without the
+   // prefetch ((dx dx + dy dy) rounded, then fma with dz) and another way in the one with it (fma(dx, dx, dy dy) + dz dz): forces that differed by 2e-5 eV/A
+   // after three steps.  These are the shapes it had always chosen for this loop, one per precision, so no result moves.
+   real_t r2;
+   {
+#pragma clang fp contract(off)
+#ifdef COMD_SINGLE
+      r2 = fmaR(dz, dz, dx*dx + dy*dy);
+#else
+      r2 = fmaR(dz, dz, fmaR(dx, dx, dy*dy));
+#endif
+   }
    bool hit = SELF ? (r2 <= q.rc2 && r2 > R(0.0)) : (r2 <= q.rc2);        // (the record's own copy of rc^2: see LjPos4)
    if (hit) ljPair<ENERGY>(dx, dy, dz, r2, a, fx, fy, fz, e);
 }
 
-template <bool SELF, bool ENERGY>
-__device__ __forceinline__ void ljListLoop(const LjArgs& a, const LjPos4* __restrict__ pos, const unsigned* __restrict__ L, int p, int pEnd,
-                                           real_t xi, real_t yi, real_t zi, real_t& fx, real_t& fy, real_t& fz, real_t& e)
+// L2 prefetch of the list loop (PREFETCH): the scalar loads of a batch wait for the slowest of them, and a row is read exactly once (cold by
+// construction) while the 84 MB of records stand against 4 MB of L2 per XCD, so most batches pay the latency of the memory behind L2.
+// Once per period of 64 candidates the LANES therefore run ahead of the scalar stream: lane l loads the entry LJ_PREFETCH_D + l candidates
+// ahead (one global_load_dword: the row's lines on their way into L2), and one period later uses that entry to touch its record with one dword
+// load, LJ_PREFETCH_D - 64 ... LJ_PREFETCH_D - 1 candidates before the scalar stream asks for it.  Nothing waits for a load of the same period:
+// the entry is used, and the touched word folded into the lane's sink, one period (eight batches) after it was asked for.  The sink ends in a
+// store that never executes (LJ_Force_thread_atom), which is all that keeps the loads alive; they are ordinary loads the compiler tracks.
+// In flight per wave: at most LJ_PREFETCH_D records of 32 B and as many entries of 4 B, 2.3 KB.  An XCD holds 32 CUs x <= 30 waves = 960 waves:
+// 2.2 MB of its 4 MB of L2 even if every wave touched lines of its own -- and they do not: the three waves of a cell and the cells around them read the
+// same stencil records, and four records share a 128-byte line.  Measured at LJ 80^3 (ms per step, three runs each, the parent at 3.07):
+// D = 64: 2.89, 2.89, 2.87   128: 2.92, 2.91, 2.89   192: 2.96, 2.95, 2.93   256: 2.97, 2.96, 2.95 -- the shortest distance the scheme has is the best.
+#ifndef LJ_PREFETCH_D
+#define LJ_PREFETCH_D 64                      // candidates the entry loads run ahead (a multiple of 64, at least 64: the touches follow one period behind)
+#endif
+
+template <bool SELF, bool ENERGY, bool PREFETCH>
+__device__ __forceinline__ void ljListLoop(const LjArgs& a, const LjPos4* __restrict__ pos, const unsigned* __restrict__ L, int p, int pEnd, int nAll, int lane,
+                                           real_t xi, real_t yi, real_t zi, real_t& fx, real_t& fy, real_t& fz, real_t& e, unsigned& sink)
 {
    // The list is wave-uniform: eight offsets per s_load_dwordx8, one s_load_dwordx8 per candidate record.  The offsets of batch b + 1 are
    // fetched together with the records of batch b, so a batch costs one exposed scalar-load latency, not two dependent ones.
@@ -121,6 +147,19 @@ __device__ __forceinline__ void ljListLoop(const LjArgs& a, const LjPos4* __rest
       unsigned id[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) id[u] = L[p + u];
+      // per-lane prefetch state: the entry asked for one period ago, the record word touched one period ago.  Every index is clamped to the
+      // row's last entry (nAll - 1 >= 7 here): the tail of a row is uninitialised, and an entry below nAll is an offset inside pos.
+      // The first period's touch is made here, in front of the loop, and waits for its entry: the one load latency of the prefetch that is exposed.
+      // (It also drains the loads of xi, yi, zi.  With those still counted as pending inside the loop, hipcc's s_waitcnt for them -- vmcnt(1) in every
+      // batch -- waited for the touch just issued.)
+      const int lim = nAll - 1 - lane;                       // lane + min(i, lim) = min(i + lane, nAll - 1)
+      unsigned ent = 0u, touched = 0u;
+      if (PREFETCH) {
+         const int i0 = p + (LJ_PREFETCH_D - 64), i1 = p + LJ_PREFETCH_D;
+         ent = L[lane + (i0 < lim ? i0 : lim)];
+         touched = *(const unsigned*)((const char*)pos + ent);
+         ent = L[lane + (i1 < lim ? i1 : lim)];
+      }
       for (int b = 0; b < n8; ++b, p += 8) {
          LjPos4 q[8];
          unsigned idn[8];
@@ -133,7 +172,14 @@ __device__ __forceinline__ void ljListLoop(const LjArgs& a, const LjPos4* __rest
          for (int u = 0; u < 8; ++u) ljListTest<SELF, ENERGY>(a, q[u], xi, yi, zi, fx, fy, fz, e);
 #pragma unroll
          for (int u = 0; u < 8; ++u) id[u] = idn[u];
+         if (PREFETCH && (b & 7) == 7) {                     // a period ends: fold what it asked for, ask for the next
+            sink |= touched;
+            touched = *(const unsigned*)((const char*)pos + ent);
+            const int i = p + 8 + LJ_PREFETCH_D;
+            ent = L[lane + (i < lim ? i : lim)];
+         }
       }
+      if (PREFETCH) sink |= touched;
    }
    for (; p < pEnd; ++p) ljListTest<SELF, ENERGY>(a, atByte(pos, L[p]), xi, yi, zi, fx, fy, fz, e);
 }
@@ -373,9 +419,12 @@ __device__ __forceinline__ void ljChunkListed(const LjArgs& a, const LjPos4* __r
 // last seen by the host (SimGpu.max_atoms_cell) -- 3 waves for 5-sigma LJ Cu instead of cap/64 = 4, so no wave is born dead.
 // A cell that outgrew that estimate is still complete: its waves take the extra chunks through the generic path.
 // LISTED: the full waves read the candidates LJ_WaveCandidates left for them instead of walking the 27 cells.
-template <bool ENERGY, bool LISTED>
-__global__ __launch_bounds__(256)
-void LJ_Force_thread_atom(LjArgs a, int wavesPerCell, LjWaveLists w)
+// PREFETCH: the vector-side L2 prefetch of ljListLoop (COMD_LJ_PREFETCH=0 launches LJ_Force_thread_atom_plain, the kernel without it).
+// SGPRs: 106 in double (hipcc: 7 waves per SIMD), as before the prefetch.  The list loop holds seven records (56 SGPRs), eight entries and ~25 of loop and
+// wave state; with the six the hardware adds that is the 96 an eighth wave allows at best, and hipcc bounded to it (__launch_bounds__(256, 7 or 8)) spills
+// 40-120 SGPRs, reloaded inside the list loop.  DESIGN.md section 6 has the attempts.
+template <bool ENERGY, bool LISTED, bool PREFETCH>
+__device__ __forceinline__ void ljForceThreadAtom(const LjArgs& a, const int wavesPerCell, const LjWaveLists& w)
 {
    const int lane = threadIdx.x & 63;
    // one workgroup per cell when wavesPerCell <= 4 (blockDim = 64 * wavesPerCell); otherwise 4-wave workgroups laid flat over (cell, chunk)
@@ -407,9 +456,10 @@ void LJ_Force_thread_atom(LjArgs a, int wavesPerCell, LjWaveLists w)
       real_t fx = R(0.0), fy = R(0.0), fz = R(0.0), e = R(0.0);
       // (a software-pipelined variant -- scalar loads of batch b+1 issued before batch b is evaluated, 4 neighbours per batch to fit
       // two batches in SGPRs -- measured 9 % slower: 4.30 vs 3.95 ms; the 8-wide batches below rely on the other waves for latency cover)
+      unsigned sink = 0u;                                    // the prefetch loads of ljListLoop end here
       if (LISTED && nAll >= 0) {
-         ljListLoop<true, ENERGY>(a, w.pos, L, 0, nSelf, xi, yi, zi, fx, fy, fz, e);
-         ljListLoop<false, ENERGY>(a, w.pos, L, nSelf, nAll, xi, yi, zi, fx, fy, fz, e);
+         ljListLoop<true, ENERGY, PREFETCH>(a, w.pos, L, 0, nSelf, nAll, lane, xi, yi, zi, fx, fy, fz, e, sink);
+         ljListLoop<false, ENERGY, PREFETCH>(a, w.pos, L, nSelf, nAll, nAll, lane, xi, yi, zi, fx, fy, fz, e, sink);
       } else {
          ljCellLoop<true, ENERGY>(a, iBox, xi, yi, zi, fx, fy, fz, e);
          for (int k = 1; k < 27; ++k) ljCellLoop<false, ENERGY>(a, uniform(nb[k]), xi, yi, zi, fx, fy, fz, e);
@@ -419,12 +469,23 @@ void LJ_Force_thread_atom(LjArgs a, int wavesPerCell, LjWaveLists w)
          a.fx[iOff] = fx * fs; a.fy[iOff] = fy * fs; a.fz[iOff] = fz * fs;
          if (ENERGY) a.e[iOff] = e * R(2.0) * a.eps;          // 4 eps * 1/2 per pair
       }
+      // where the prefetch ends: no cell has a negative capacity, so this store never executes, and it stands behind the force stores
+      if (LISTED && PREFETCH && a.cap < 0) a.fx[iOff] = (real_t)sink;
    }
    // NOTE: no store may precede the scalar-path loads above on any path through this kernel, or the compiler gives up proving the
    // position arrays unclobbered and silently replaces the s_load_dwordx16 stream by per-lane global_load (measured: 4.7 -> 6.2 ms).
    // Everything below runs after the wave's first chunk is stored.  Check `grep -c s_load_dwordx16` in the ISA after edits here.
    for (int c = chunk + wavesPerCell; c * 64 < ni; c += wavesPerCell) ljChunkGeneric<ENERGY>(a, iBox, ni, c, lane);
 }
+
+// the kernel as launched: with lists it prefetches; LJ_Force_thread_atom_plain is the listed kernel without the prefetch (COMD_LJ_PREFETCH=0)
+template <bool ENERGY, bool LISTED>
+__global__ __launch_bounds__(256)
+void LJ_Force_thread_atom(LjArgs a, int wavesPerCell, LjWaveLists w) { ljForceThreadAtom<ENERGY, LISTED, LISTED>(a, wavesPerCell, w); }
+
+template <bool ENERGY>
+__global__ __launch_bounds__(256)
+void LJ_Force_thread_atom_plain(LjArgs a, int wavesPerCell, LjWaveLists w) { ljForceThreadAtom<ENERGY, true, false>(a, wavesPerCell, w); }
 
 // ---------------------------------------------------------------------------------------------------
 // CTA per link cell (the reference's LJ_Force_cta_cell shape, gpu_lj_cta_cell.h:29-122): one workgroup per cell, one thread

@@ -387,7 +387,10 @@ void comdForcePathInfo(SimGpu* sim, int out[4]);
  *  [17] what the launch covered: 0 all local cells, 1 the whole bricks of the boundary or interior group, 2 a cell list taken cell by cell
  *  [18] longest stencil run a thread_atom row addresses with byte offsets (256; 64 under COMD_EAM_ABLATE=16)   [19] phi / rho tables staged in the LDS (pass 1)
  *  [20] spline tables (-P)   [21] the table clamps of interpolate() kept   [22] records of the LDS slice of round 2's cta_cell kernel
- *  [23] Verlet-list format (NeighborListGpu.slabFormat) */
+ *  [23] Verlet-list format (NeighborListGpu.slabFormat)   [24] LJ thread_atom: the launch ran the list kernel with the L2 prefetch (0 under COMD_LJ_PREFETCH=0,
+ *       without lists, and for the -I kernel)
+ *  [25] listed waves of more than 32 atoms (the ones that run the list loop)   [26] of them, rows whose length is no multiple of 64
+ *  [27] of them, rows whose own-cell part is no multiple of 8 (the rest of the row starts off the batch grid)   [28] the shortest of their rows   [29] the prefetch distance (LJ_PREFETCH_D) */
 #define COMD_LEG_REPORT_N 32
 void comdForceLegReport(SimGpu* sim, int out[COMD_LEG_REPORT_N]);
 /* updateNeighborsGpu[Async], gpu_kernels.cu:251-279: the reference materialises 27*MAXATOMS neighbour
