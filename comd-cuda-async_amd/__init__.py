@@ -137,6 +137,12 @@ def lib_host():
         lib.comdDisplacements.restype = ctypes.c_int
         lib.comdMsd.argtypes = [vp, c_double_p]
         lib.comdMsd.restype = ctypes.c_int
+        lib.comdCentroSymmetry.argtypes = [vp, ctypes.c_double, c_double_p, c_double_p]
+        lib.comdCentroSymmetry.restype = ctypes.c_int
+        lib.comdDefaultCoordRadius.argtypes = [vp]
+        lib.comdDefaultCoordRadius.restype = ctypes.c_double
+        lib.comdLatticeConstant.argtypes = [vp]
+        lib.comdLatticeConstant.restype = ctypes.c_double
         lib.comdCutoff.argtypes = [vp]
         lib.comdCutoff.restype = ctypes.c_double
         lib.comdVolume.argtypes = [vp]
@@ -438,6 +444,44 @@ class Simulation:
         k = np.arange(n_bins, dtype=np.float64)
         ideal = (0.5 * n) * (n / self.lib.comdVolume(self.ptr)) * (4.0 * np.pi / 3.0 * dr * dr * dr) * ((k + 1.0) ** 3 - k ** 3)
         return 0.5 * (edges[:-1] + edges[1:]), counts / ideal
+
+    # --- defects (not in the reference: comd-hip --csp, --cspThreshold, --cspCoord, --cspFile, --cspDump) ---
+    @property
+    def lattice_constant(self):
+        """The lattice constant the crystal was made with (-l, or the potential's), in Angstroms."""
+        return self.lib.comdLatticeConstant(self.ptr)
+
+    def centro_symmetry(self, r_coord=None):
+        """(csp float64[n_global], coordination int32[n_global]) of the current state, keyed by gid.  csp: the centro-symmetry parameter in
+        Angstroms^2, the sum in ascending order of the 6 smallest |R_a + R_b|^2 over the 66 pairs of the offset vectors of the atom's 12 nearest
+        neighbours -- 0 on a perfect FCC site, 24 |d|^2 for an atom displaced alone by d, lat^2 / 2 in a stacking fault, +inf with fewer than 12
+        neighbours inside the force cutoff.  coordination: the neighbours closer than r_coord Angstroms (None: halfway between the first and second
+        FCC shells, (1/sqrt 2 + 1) lat / 2, or the force cutoff where that is smaller; at most the force cutoff).  Computed on the device by
+        computeCentroSymmetry, summed over the ranks (every rank gets the global arrays); valid whenever pair_histogram() is."""
+        np = self._np
+        if self.host_only:
+            raise RuntimeError("centro_symmetry: a host-only simulation has no device state")
+        # r_coord <= 0 means "the default" to comdCentroSymmetry: refuse it here, before anything is launched
+        if r_coord is not None and not (0.0 < float(r_coord) <= self.cutoff):
+            raise ValueError(f"centro_symmetry: need 0 < r_coord <= the force cutoff {self.cutoff} (got {r_coord})")
+        n = self.n_global
+        csp, coord = np.zeros(max(n, 1), dtype=np.float64), np.zeros(max(n, 1), dtype=np.float64)
+        if self.lib.comdCentroSymmetry(self.ptr, 0.0 if r_coord is None else float(r_coord), csp.ctypes.data_as(c_double_p), coord.ctypes.data_as(c_double_p)) != 0:
+            raise ValueError(f"centro_symmetry: r_coord {r_coord} was refused (the force cutoff is {self.cutoff})")
+        return csp[:n], coord[:n].astype(np.int32)
+
+    def defects(self, threshold=None, r_coord=None):
+        """Ascending int64 gids of the atoms whose centro-symmetry parameter exceeds `threshold` Angstroms^2 (None: lat^2 / 4, half the value of an
+        atom in a stacking fault); atoms with fewer than 12 neighbours (+inf) count."""
+        np = self._np
+        if self.host_only:
+            raise RuntimeError("defects: a host-only simulation has no device state")
+        if threshold is not None and not float(threshold) > 0.0:
+            raise ValueError(f"defects: need threshold > 0 (got {threshold})")
+        if threshold is None:
+            threshold = 0.25 * self.lattice_constant ** 2
+        csp, _ = self.centro_symmetry(r_coord)
+        return np.nonzero(csp > float(threshold))[0].astype(np.int64)
 
     # --- dynamics (not in the reference: comd-hip --msd, --msdStart, --msdFile) ---
     def track_displacement(self, on=True):

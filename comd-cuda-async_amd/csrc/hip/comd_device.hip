@@ -22,6 +22,7 @@
 #include "eam_atom_brick_kernels.h"
 #include "virial_kernels.h"
 #include "rdf_kernels.h"
+#include "csp_kernels.h"
 #include "langevin_kernels.h"
 #include "msd_kernels.h"
 
@@ -599,7 +600,7 @@ extern "C" void DestroyGpu(SimGpu* sim)
                     sim->boxes.boxIDLookUp, sim->boxes.boxIDLookUpReverse, sim->eam_pot.phiS.coefficients, sim->eam_pot.rhoS.coefficients,
                     sim->eam_pot.pairRows, sim->eam_pot.pairRowCount, sim->eam_pot.cellSel, sim->eam_pot.brickGroup, sim->eam_pot.brickList, sim->eam_pot.brickSel, sim->eam_pot.brickStats, sim->eam_pot.atomRows, sim->eam_pot.atomRowCount, sim->eam_pot.atomBrickSel,
                     sim->atoms.neighborList.brickRows, sim->atoms.neighborList.brickRowCount, sim->adapterScan, sim->lj_pot.waveCand, sim->lj_pot.waveCandCount, sim->lj_pot.packedR[0], sim->lj_pot.packedR[1], sim->lj_pot.packedF[0], sim->lj_pot.packedF[1],
-                    sim->lj_pot.lj_interpolation.values, sim->virialBuf, sim->pairHistBuf, sim->dispBuf, sim->dispSumBuf };
+                    sim->lj_pot.lj_interpolation.values, sim->virialBuf, sim->pairHistBuf, sim->dispBuf, sim->dispSumBuf, sim->cspBuf, sim->cspCoordBuf };
    for (void* p : ptrs) if (p) HIP_CHECK(hipFree(p));
    if (sim->statusEvent) (void)hipEventDestroy((hipEvent_t)sim->statusEvent);
    if (sim->pinned) HIP_CHECK(hipHostFree(sim->pinned));
@@ -1188,6 +1189,33 @@ extern "C" void computePairHistogram(SimGpu* sim, int nBins, real_t rMax, uint64
    hipLaunchKernelGGL(PairHist_thread_atom, dim3(grid), dim3(256), lds, st, v);
    LAUNCH_CHECK();
    HIP_CHECK(hipMemcpyAsync(outCounts, sim->pairHistBuf, (size_t)nBins * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// Not in the reference: the centro-symmetry parameter and the coordination number of every local atom (csp_kernels.h).  One instance for every
+// potential and method: it reads positions and cells only.  The two per-slot buffers are allocated by the first call.
+extern "C" void computeCentroSymmetry(SimGpu* sim, real_t rCoord, real_t* outCspBySlot, int* outCoordBySlot)
+{
+   hipStream_t st = S(sim->boundary_stream);
+   if (sim->interior_stream) HIP_CHECK(hipStreamSynchronize(S(sim->interior_stream)));      // -a 1: the interior cells' force work is done
+   const real_t cutoff = sim->do_eam ? sim->eam_pot.cutoff : sim->lj_pot.cutoff;
+   if (!(rCoord > R(0.0)) || rCoord > cutoff) { fprintf(stderr, "computeCentroSymmetry: rCoord %g outside (0, cutoff = %g]\n", (double)rCoord, (double)cutoff); exit(-1); }
+   if ((double)sim->boxes.nTotalBoxes * sim->maxAtoms >= 2147483648.0) { fprintf(stderr, "computeCentroSymmetry: more than 2^31 slots\n"); exit(-1); }
+   const size_t nSlots = (size_t)sim->boxes.nLocalBoxes * sim->maxAtoms;
+   if (!sim->cspBuf) {
+      sim->cspBuf = dalloc<real_t>(nSlots);
+      sim->cspCoordBuf = dalloc<int>(nSlots);
+   }
+   CentroSymArgs v;
+   v.rx = sim->atoms.r.x; v.ry = sim->atoms.r.y; v.rz = sim->atoms.r.z;
+   v.nAtoms = sim->boxes.nAtoms; v.nbr = sim->neighbor_cells;
+   v.nLocalBoxes = sim->boxes.nLocalBoxes; v.cap = sim->maxAtoms; v.chunks = ceilDiv(sim->maxAtoms, WAVE);
+   v.rc2 = cutoff * cutoff; v.rCoord2 = rCoord * rCoord;
+   v.csp = sim->cspBuf; v.coord = sim->cspCoordBuf;
+   hipLaunchKernelGGL(CentroSym_thread_atom, dim3(CSP_BLOCKS), dim3(256), 0, st, v);
+   LAUNCH_CHECK();
+   HIP_CHECK(hipMemcpyAsync(outCspBySlot, sim->cspBuf, nSlots * sizeof(real_t), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipMemcpyAsync(outCoordBySlot, sim->cspCoordBuf, nSlots * sizeof(int), hipMemcpyDeviceToHost, st));
    HIP_CHECK(hipStreamSynchronize(st));
 }
 

@@ -1,0 +1,178 @@
+// csp_kernels.h -- per-atom defect analysis for gfx950: the centro-symmetry parameter and the coordination number (computeCentroSymmetry,
+// comd_hip.h).  The reference has no counterpart.
+//
+// For every local atom i, with the neighbours j != i (local or halo image) at |r_j - r_i| < the force cutoff:
+//   coord_i = number of neighbours with |r_ij| < rCoord                                  (rCoord <= cutoff, the host checks)
+//   csp_i   = sum of the 6 smallest of the 66 values |R_a + R_b|^2, a < b, added in ascending order, R_1..R_12 = r_j - r_i of the 12 nearest
+//             neighbours (Kelchner, Plimpton, Hamilton 1998); +inf for an atom with fewer than 12 neighbours inside the cutoff.
+// A tie between the 12th and the 13th nearest distance goes to the neighbour met first in walk order (stencil cell by stencil cell, slot by
+// slot; with a replicated chunk, see below, the copy with the lower number wins).
+//
+// Mapping: the one of PairHist_thread_atom (rdf_kernels.h), whose header also says why the 27-cell walk sees every pair within the cutoff when
+// the cells are sized for cutoff + skin and not re-binned.  One wave = one 64-slot chunk of a local cell, lane = atom i, the candidates j
+// wave-uniform through the scalar load stream, 8 per batch.
+//
+// The 12 nearest: every lane keeps {r^2, slot} of its 12 best candidates sorted by r^2 in registers.  A candidate closer than the lane's 12th
+// (which starts at cutoff^2, so this is the cutoff test too) is carried through the 12 positions with compare / select at compile-time indices: it
+// settles where it belongs and pushes the rest down, the last one out.  No array is indexed at run time, so nothing goes to scratch.  The
+// chain runs only when some lane of the wave takes a candidate; a lane's threshold falls quickly, so most candidates are refused by the one compare.
+// Slots are kept, not offset vectors (12 VGPRs instead of 72 in the double build): the positions are read again at the end.  The halo
+// cells hold shifted images, so r_j - r_i is the offset vector as it stands, without a minimum image.
+//
+// Small chunks: a chunk of at most 32 atoms -- every EAM cell, LJ at 2.5 sigma, the tail chunk of an LJ cell -- would use 10 to 50 % of the lanes.  It
+// is replicated as PairHist does it: reps copies of its atoms, copy q walks the stencil cells q, q + reps, ... with per-lane loads, and the
+// partial sets are merged by a butterfly over the copies (each lane reads the 12 entries of the lane `span` away through ds_bpermute and offers
+// them to its own set; the coordination counts add).  Packing several cells into a wave instead would keep the loads scalar only for the lanes of one
+// cell at a time and needs a per-lane cell table; replication reuses the walk the histogram and the virial already have, and the merge costs
+// 12 offers per doubling against the 27 / reps cells of candidates it saves.  The 66-pair stage at the end is NOT shared among the copies: only copy 0
+// keeps its result, so on an EAM cell it runs on about 14 of 64 lanes.  The reason: a lane that took a share of the 66 pairs of its own would index
+// X[a], X[b] at run time (scratch), and predicating shares on compile-time indices leaves every lane issuing all 66 anyway.  Measured at 80^3 the EAM
+// kernel takes 4.3 ms against 10.2 ms for LJ 5 sigma: this stage and the merge are what does not shrink with the candidates.
+//
+// The kernel reads r, nAtoms and nbr and writes nothing but its own two per-slot buffers; no atomics: bit-reproducible.
+#pragma once
+#include "device_common.h"
+
+#define CSP_BLOCKS 2048
+#define CSP_NN 12                      // neighbours of the parameter: the first FCC shell
+
+struct CentroSymArgs {
+   const real_t* __restrict__ rx; const real_t* __restrict__ ry; const real_t* __restrict__ rz;
+   const int* __restrict__ nAtoms;
+   const int* __restrict__ nbr;        // [nLocal*27], self first
+   int nLocalBoxes, cap, chunks;       // chunks = 64-slot chunks per cell
+   real_t rc2, rCoord2;                // cutoff^2, rCoord^2
+   real_t* __restrict__ csp;           // [nLocalBoxes*cap]
+   int* __restrict__ coord;            // [nLocalBoxes*cap]
+};
+
+// offer {c, ci} to the ascending set: it settles at its place, what was there moves on, the last one drops out.  On equal keys the entry that is in stays.
+template <int N>
+__device__ __forceinline__ void cspOffer(real_t (&d)[N], int (&id)[N], real_t c, int ci)
+{
+#pragma unroll
+   for (int k = 0; k < N; ++k) {
+      const bool lt = c < d[k];
+      const real_t lo = lt ? c : d[k], hi = lt ? d[k] : c;
+      const int loI = lt ? ci : id[k], hiI = lt ? id[k] : ci;
+      d[k] = lo; id[k] = loI; c = hi; ci = hiI;
+   }
+}
+
+// the same for keys alone
+template <int N>
+__device__ __forceinline__ void cspOfferKey(real_t (&d)[N], real_t c)
+{
+#pragma unroll
+   for (int k = 0; k < N; ++k) {
+      const bool lt = c < d[k];
+      const real_t lo = lt ? c : d[k], hi = lt ? d[k] : c;
+      d[k] = lo; c = hi;
+   }
+}
+
+__global__ __launch_bounds__(256, 4)
+void CentroSym_thread_atom(CentroSymArgs v)
+{
+   const int lane = laneId(), wave = (int)threadIdx.x >> 6;
+   const real_t inf = R(__builtin_huge_val());
+
+   const long nWork = (long)v.nLocalBoxes * v.chunks;
+   const long per = (nWork + gridDim.x - 1) / gridDim.x;
+   const long w0 = (long)xcdRemap(blockIdx.x, gridDim.x) * per;
+   const long w1 = w0 + per < nWork ? w0 + per : nWork;
+   for (long w = w0 + wave; w < w1; w += 4) {
+      const int iBox = uniform((int)(w / v.chunks));
+      const int first = uniform((int)(w - (long)iBox * v.chunks)) * WAVE;
+      const int ni = uniform(v.nAtoms[iBox]);
+      if (first >= ni) continue;
+      // a chunk of m <= 32 atoms is replicated: reps copies of its atoms, copy q walks the stencil cells q, q + reps, ... (as PairHist_thread_atom)
+      const int m = ni - first < WAVE ? ni - first : WAVE;
+      int reps = 1;
+      while (reps < 16 && 2 * reps * m <= WAVE) reps *= 2;
+      const int span = WAVE / reps, q = lane / span;
+      const int ia = first + (lane & (span - 1));
+      const bool active = ia < first + m;
+      const int me = iBox * v.cap + (active ? ia : first);
+      const real_t xi = v.rx[me], yi = v.ry[me], zi = v.rz[me];
+
+      real_t d[CSP_NN]; int id[CSP_NN];
+#pragma unroll
+      for (int k = 0; k < CSP_NN; ++k) { d[k] = active ? v.rc2 : R(0.0); id[k] = -1; }      // an idle lane takes nothing
+      int coord = 0;
+      auto test = [&](real_t xj, real_t yj, real_t zj, int slot) {
+         const real_t dx = xj - xi, dy = yj - yi, dz = zj - zi;
+         const real_t r2 = dx*dx + dy*dy + dz*dz;
+         const bool other = slot != me;
+         coord += (other && r2 < v.rCoord2) ? 1 : 0;
+         if (other && r2 < d[CSP_NN - 1]) cspOffer<CSP_NN>(d, id, r2, slot);
+      };
+      const int* __restrict__ nb = v.nbr + (size_t)iBox * 27;
+      if (reps > 1) {
+         for (int k = q; k < 27; k += reps) {
+            const int jBox = nb[k];
+            const int nj = v.nAtoms[jBox];
+            const int base = jBox * v.cap;
+            for (int j = 0; j < nj; ++j) test(v.rx[base + j], v.ry[base + j], v.rz[base + j], base + j);
+         }
+         // the copies' sets into one: after the doubling over s every lane holds the 12 nearest of the copies lane ^ s, lane ^ 2s, ... as well
+         for (int s = span; s < WAVE; s <<= 1) {
+            const int addr = (lane ^ s) << 2;
+            real_t pd[CSP_NN]; int pi[CSP_NN];
+#pragma unroll
+            for (int k = 0; k < CSP_NN; ++k) { pd[k] = bpermuteAddrR(d[k], addr); pi[k] = __builtin_amdgcn_ds_bpermute(addr, id[k]); }
+            coord += __builtin_amdgcn_ds_bpermute(addr, coord);
+            // the lower copy's entries win ties in both lanes of a pair: the upper copy's set is rebuilt from the lower one's
+            const bool upper = (lane & s) != 0;
+#pragma unroll
+            for (int k = 0; k < CSP_NN; ++k) {
+               const real_t td = d[k]; const int ti = id[k];
+               d[k] = upper ? pd[k] : td; id[k] = upper ? pi[k] : ti;
+               pd[k] = upper ? td : pd[k]; pi[k] = upper ? ti : pi[k];
+            }
+#pragma unroll
+            for (int k = 0; k < CSP_NN; ++k)
+               if (pi[k] >= 0 && pd[k] < d[CSP_NN - 1]) cspOffer<CSP_NN>(d, id, pd[k], pi[k]);
+         }
+      } else for (int k = 0; k < 27; ++k) {
+         const int jBox = uniform(nb[k]);
+         const int nj = uniform(v.nAtoms[jBox]);
+         const int base = jBox * v.cap;
+         const real_t* __restrict__ qx = v.rx + base;
+         const real_t* __restrict__ qy = v.ry + base;
+         const real_t* __restrict__ qz = v.rz + base;
+         int j = 0;
+         for (; j + 8 <= nj; j += 8) {
+            real_t xs[8], ys[8], zs[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { xs[u] = qx[j + u]; ys[u] = qy[j + u]; zs[u] = qz[j + u]; }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) test(xs[u], ys[u], zs[u], base + j + u);
+         }
+         for (; j < nj; ++j) test(qx[j], qy[j], qz[j], base + j);
+      }
+
+      if (active && q == 0) {
+         const bool full = id[CSP_NN - 1] >= 0;
+         real_t X[CSP_NN], Y[CSP_NN], Z[CSP_NN];
+#pragma unroll
+         for (int k = 0; k < CSP_NN; ++k) {
+            const int s = full ? id[k] : me;
+            X[k] = v.rx[s] - xi; Y[k] = v.ry[s] - yi; Z[k] = v.rz[s] - zi;
+         }
+         real_t t[6];
+#pragma unroll
+         for (int k = 0; k < 6; ++k) t[k] = inf;
+#pragma unroll
+         for (int a = 0; a < CSP_NN; ++a)
+#pragma unroll
+            for (int b = a + 1; b < CSP_NN; ++b) {
+               const real_t sx = X[a] + X[b], sy = Y[a] + Y[b], sz = Z[a] + Z[b];
+               cspOfferKey<6>(t, sx*sx + sy*sy + sz*sz);
+            }
+         const real_t sum = ((((t[0] + t[1]) + t[2]) + t[3]) + t[4]) + t[5];
+         v.csp[me] = full ? sum : inf;
+         v.coord[me] = coord;
+      }
+   }
+}

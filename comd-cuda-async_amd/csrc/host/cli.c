@@ -9,7 +9,10 @@
  * --rdf N, --rdfMax R, --rdfFile PATH (radial distribution function g(r) from a pair histogram of N bins up to R Angstroms, sampled at every
  * printed step and written to PATH; the reference has no structural analysis),
  * --msd, --msdStart S, --msdFile PATH (mean-squared displacement of the unwrapped trajectories from global step S on, accumulated in the drift
- * kernels, sampled at every printed step and written to PATH with a diffusion coefficient; the reference has no dynamical analysis). */
+ * kernels, sampled at every printed step and written to PATH with a diffusion coefficient; the reference has no dynamical analysis),
+ * --csp, --cspThreshold X, --cspCoord R, --cspFile PATH, --cspDump PATH (per-atom defect analysis: the centro-symmetry parameter of every atom's 12
+ * nearest neighbours and its coordination number within R Angstroms, sampled at every printed step; a Defects column counts the atoms above X
+ * Angstroms^2, PATH gets a line per sample and the dump the defect atoms of the last step as extended XYZ). */
 #include "comd_host.h"
 #include <getopt.h>
 #include <math.h>
@@ -44,6 +47,7 @@ Command parseCommandLine(int argc, char** argv)
    cmd.langevinTemp = NAN; cmd.langevinDamp = COMD_LANGEVIN_DAMP; cmd.seed = COMD_LANGEVIN_SEED;
    strcpy(cmd.rdfFile, "rdf.dat");
    strcpy(cmd.msdFile, "msd.dat");
+   strcpy(cmd.cspFile, "csp.dat");
    int help = 0;
 
    const ArgDef defs[] = {
@@ -88,6 +92,11 @@ Command parseCommandLine(int argc, char** argv)
       { "msd",           0,  0, 'i', &cmd.msd,            0, "mean-squared displacement (unwrapped, tracked in the integrator), sampled at every printed step" },
       { "msdStart",      0,  1, 'i', &cmd.msdStart,       0, "global step the MSD origin is taken at (0..nSteps; default 0)" },
       { "msdFile",       0,  1, 's', cmd.msdFile, sizeof cmd.msdFile, "file the MSD is written to (default msd.dat)" },
+      { "csp",           0,  0, 'i', &cmd.csp,            0, "centro-symmetry parameter and coordination number of every atom, sampled at every printed step (a Defects column)" },
+      { "cspThreshold",  0,  1, 'd', &cmd.cspThreshold,   0, "an atom is a defect above this centro-symmetry parameter (Angstroms^2; default lat^2 / 4)" },
+      { "cspCoord",      0,  1, 'd', &cmd.cspCoord,       0, "radius of the coordination count in Angstroms (default (1/sqrt 2 + 1) lat / 2; at most the force cutoff)" },
+      { "cspFile",       0,  1, 's', cmd.cspFile, sizeof cmd.cspFile, "file the samples are written to (default csp.dat)" },
+      { "cspDump",       0,  1, 's', cmd.cspDump, sizeof cmd.cspDump, "extended-XYZ file of the defect atoms of the last step (default: none)" },
    };
    const int nDefs = (int)(sizeof defs / sizeof defs[0]);
 
@@ -111,7 +120,10 @@ Command parseCommandLine(int argc, char** argv)
       if (!d->hasArg) { *(int*)d->ptr = 1; continue; }
       switch (d->type) {
          case 'i': *(int*)d->ptr = atoi(optarg); break;
-         case 'd': *(double*)d->ptr = atof(optarg); break;
+         case 'd': *(double*)d->ptr = atof(optarg);
+                   if (d->ptr == &cmd.cspThreshold) cmd.cspThresholdSet = 1;
+                   if (d->ptr == &cmd.cspCoord) cmd.cspCoordSet = 1;
+                   break;
          case 'u': *(uint64_t*)d->ptr = strtoull(optarg, NULL, 0); break;
          case 's': strncpy((char*)d->ptr, optarg, (size_t)d->size - 1); ((char*)d->ptr)[d->size - 1] = '\0'; break;
       }
@@ -162,6 +174,7 @@ void printCmdYaml(FILE* file, Command* cmd)
               "  Langevin damping: %g fs\n"
               "  Langevin seed: %llu\n",
               cmd->langevinTemp, cmd->langevinDamp, (unsigned long long)cmd->seed);
+   if (cmd->csp) fprintf(file, "  CSP file: %s\n", cmd->cspFile);
    if (cmd->msd) fprintf(file, "  MSD from step: %d\n  MSD file: %s\n", cmd->msdStart, cmd->msdFile);
    fprintf(file, "\n");
    fflush(file);

@@ -54,6 +54,12 @@ typedef struct CommandSt {
    int msd;               /* extension: mean-squared displacement from displacements tracked in the drift kernels, sampled at every printed step (the reference has no dynamical analysis) */
    int msdStart;          /* extension: the global step its origin is taken at, 0..nSteps (default 0) */
    char msdFile[1024];    /* extension: where the print rank writes it (default msd.dat) */
+   int csp;               /* extension: centro-symmetry parameter and coordination number of every atom, sampled at every printed step (the reference has no structural analysis) */
+   double cspThreshold;   /* extension: an atom is a defect when its parameter exceeds this, in Angstroms^2; 0 = lat^2 / 4 */
+   double cspCoord;       /* extension: radius of the coordination count in Angstroms; 0 = halfway between the first two FCC shells */
+   char cspFile[1024];    /* extension: where the print rank writes the samples (default csp.dat) */
+   char cspDump[1024];    /* extension: extended-XYZ file of the defect atoms of the last step; empty = none */
+   int cspThresholdSet, cspCoordSet;   /* the two values were given (a given 0 is refused, an absent one means the default) */
 } Command;
 
 #define COMD_LANGEVIN_SEED 0x436f4d44ull     /* "CoMD" */
@@ -309,6 +315,16 @@ typedef struct SimFlatSt {
    double* msdRows;                 /* [msdSamples][8]: step, the seven values of comdMsd */
    int msdSamples, msdCap;
    double msdNow;                   /* the MSD(A^2) column of printThings: the last sample, 0 before the origin */
+   double lat;                      /* the lattice constant the crystal was made with (-l, or the potential's) */
+   int csp;                         /* --csp: comdMain samples the centro-symmetry parameter at every printed step */
+   double cspThreshold, cspCoord;   /* defect threshold (A^2) and coordination radius (A), defaults resolved */
+   char cspFile[1024], cspDump[1024];
+   double* cspRows;                 /* [cspSamples][7]: step, defects, atoms with fewer than 12 neighbours, mean and max of the finite csp, mean coordination, atoms with coordination != 12 */
+   int cspSamples, cspCap;
+   double* cspLast;                 /* [2 nGlobal]: csp and coordination by gid of the last sample (--cspDump) */
+   void* cspStage;                  /* comdCentroSymmetry: host staging for the by-slot results, the gids and the occupancies, kept between calls */
+   size_t cspStageBytes;
+   int cspDefectsNow;               /* the Defects column of printThings: the last sample */
 } SimFlat;
 
 SimFlat* initSimulation(Command cmd);
@@ -347,12 +363,19 @@ int comdPairHistogram(SimFlat* s, int nBins, double rMax, double* outCounts);
 int comdTrackDisplacement(SimFlat* s, int on);
 int comdDisplacements(SimFlat* s, double* out);
 int comdMsd(SimFlat* s, double* out7);
+/* not in the reference: the centro-symmetry parameter (Angstroms^2, +inf with fewer than 12 neighbours inside the force cutoff) and the coordination
+ * number (neighbours closer than rCoord) of every atom of the current state (after a complete force evaluation, as comdPairHistogram), keyed by gid:
+ * cspByGid[g], coordByGid[g], nGlobal doubles each.  Each rank fills the entries of its local atoms from computeCentroSymmetry, the others stay 0, and the
+ * arrays are summed over the ranks: the same on every rank.  Collective.  rCoord <= 0 = the default, halfway between the first and second FCC shells,
+ * (1/sqrt 2 + 1) lat / 2, or the force cutoff where that is smaller.  -1 and nothing launched for rCoord > the force cutoff. */
+int comdCentroSymmetry(SimFlat* s, double rCoord, double* cspByGid, double* coordByGid);
+double comdDefaultCoordRadius(SimFlat* s);              /* that default */
 void redistributeAtoms(SimFlat* sim);
 void ensureInteriorForceLaunched(SimFlat* sim);
 
 /* ---- performanceTimers.h ---- */
 enum TimerHandle { totalTimer, loopTimer, timestepTimer, positionTimer, velocityTimer, redistributeTimer, atomHaloTimer,
-                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, numberOfTimers };
+                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, cspTimer, numberOfTimers };
 void profileStart(enum TimerHandle handle);
 void profileStop(enum TimerHandle handle);
 double getElapsedTime(enum TimerHandle handle);
@@ -393,6 +416,7 @@ int      comdGetLangevin(SimFlat* s, double out[2], uint64_t* seed);    /* on/of
 uint64_t comdStepCount(SimFlat* s);                       /* steps taken since creation */
 void     comdVirial(SimFlat* s, double out[13]);          /* computePressure, then {W[6], K[6], V}: global pair virial and kinetic tensor (eV), volume (A^3) */
 double   comdCutoff(SimFlat* s);                          /* the force cutoff in Angstroms: the largest rMax of comdPairHistogram, and its default */
+double   comdLatticeConstant(SimFlat* s);                 /* the lattice constant the crystal was made with, in Angstroms: lat^2 / 4 is the default defect threshold */
 double   comdVolume(SimFlat* s);                          /* volume of the global domain in A^3 */
 void     comdGridInfo(SimFlat* s, int out[6]);            /* gridSize[3], nLocalBoxes, nTotalBoxes, maxAtoms */
 int      comdMain(int argc, char** argv);                /* the reference's main(): CoMD.c:86-187 */

@@ -158,6 +158,17 @@ SimFlat* initSimulationHost(Command cmd)
    strcpy(sim->msdFile, cmd.msdFile);
    real_t latticeConstant = cmd.lat;
    if (cmd.lat < 0.0) latticeConstant = sim->pot->lat;
+   sim->lat = latticeConstant;
+   /* --csp (not in the reference): the threshold defaults to lat^2 / 4, half the parameter of an atom in a stacking fault; the coordination radius cannot
+    * exceed the force cutoff (the 27-cell walk of the kernel sees no further) */
+   if (cmd.cspThresholdSet && !(cmd.cspThreshold > 0.0)) { printf("Error: --cspThreshold must be > 0 Angstroms^2 (got %g).\n", cmd.cspThreshold); exit(-1); }
+   if (cmd.cspCoordSet && !(cmd.cspCoord > 0.0 && cmd.cspCoord <= sim->pot->cutoff)) {
+      printf("Error: --cspCoord must lie in (0, the force cutoff of %g Angstroms] (got %g).\n", (double)sim->pot->cutoff, cmd.cspCoord); exit(-1);
+   }
+   sim->csp = cmd.csp;
+   sim->cspThreshold = cmd.cspThresholdSet ? cmd.cspThreshold : 0.25 * sim->lat * sim->lat;
+   sim->cspCoord = cmd.cspCoordSet ? cmd.cspCoord : comdDefaultCoordRadius(sim);
+   strcpy(sim->cspFile, cmd.cspFile); strcpy(sim->cspDump, cmd.cspDump);
    sanityChecks(cmd, sim->pot->cutoff, latticeConstant, sim->pot->latticeType);
    sim->species = initSpecies(sim->pot);
 
@@ -260,6 +271,7 @@ void destroySimulation(SimFlat** ps)
    free(s->ljTable);
    free(s->rdfSum);
    free(s->msdRows);
+   free(s->cspRows); free(s->cspLast); free(s->cspStage);
    free(s->species); free(s->domain); free(s);
    *ps = NULL;
 }
@@ -283,8 +295,8 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
       s->firstPrint = 0;
       fprintf(screenOut,
               "#                                                                                         Performance\n"
-              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms%s%s\n",
-              s->pressure ? "    Pressure(GPa)" : "", s->msd ? "         MSD(A^2)" : "");
+              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms%s%s%s\n",
+              s->pressure ? "    Pressure(GPa)" : "", s->msd ? "         MSD(A^2)" : "", s->csp ? "      Defects" : "");
       fflush(screenOut);
    }
    real_t time = iStep * s->dt;
@@ -297,6 +309,7 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
            iStep, time, eTotal, eU, eK, Temp, timePerAtom, s->atoms->nGlobal);
    if (s->pressure) fprintf(screenOut, " %16.10f", pressureOf(s) * eVperA3inGPa);
    if (s->msd) fprintf(screenOut, " %16.10e", s->msdNow);
+   if (s->csp) fprintf(screenOut, " %12d", s->cspDefectsNow);
    fprintf(screenOut, "\n");
 }
 
@@ -415,6 +428,79 @@ static void writeMsd(FILE* yaml, SimFlat* s)
    fflush(yaml);
 }
 
+/* --csp: one more row {step, defects, atoms with fewer than 12 neighbours, mean and max of the finite csp, mean coordination, atoms with coordination != 12} */
+static void sampleCsp(SimFlat* s, int iStep)
+{
+   const size_t n = (size_t)s->atoms->nGlobal;
+   if (!s->cspLast) s->cspLast = (double*)malloc((n ? 2 * n : 1) * sizeof(double));
+   if (comdCentroSymmetry(s, s->cspCoord, s->cspLast, s->cspLast + n) != 0) { printf("Error: --csp --cspCoord %g was refused.\n", s->cspCoord); exit(-1); }
+   if (s->cspSamples == s->cspCap) { s->cspCap = s->cspCap ? 2 * s->cspCap : 64; s->cspRows = (double*)realloc(s->cspRows, (size_t)s->cspCap * 7 * sizeof(double)); }
+   double* row = s->cspRows + 7 * (size_t)s->cspSamples++;
+   double defects = 0.0, few = 0.0, sum = 0.0, top = 0.0, coordSum = 0.0, not12 = 0.0;
+   for (size_t g = 0; g < n; ++g) {
+      const double c = s->cspLast[g], z = s->cspLast[n + g];
+      if (c > s->cspThreshold) defects += 1.0;
+      if (isinf(c)) few += 1.0; else { sum += c; if (c > top) top = c; }
+      coordSum += z;
+      if (z != 12.0) not12 += 1.0;
+   }
+   row[0] = (double)iStep; row[1] = defects; row[2] = few;
+   row[3] = n > few ? sum / ((double)n - few) : 0.0; row[4] = top;
+   row[5] = n ? coordSum / (double)n : 0.0; row[6] = not12;
+   s->cspDefectsNow = (int)defects;
+}
+
+/* --csp: the file: a header line, then the rows of sampleCsp.  --cspDump: the defect atoms of the last sample as extended XYZ, Cu x y z csp coordination gid,
+ * the positions gathered by gid over the ranks as the results are.  The YAML block names the file and gives the last sample's defects and mean csp. */
+static void writeCsp(FILE* yaml, SimFlat* s)
+{
+   const size_t n = (size_t)s->atoms->nGlobal;
+   double* pos = NULL;
+   if (s->cspDump[0]) {          /* collective: before the other ranks leave */
+      double* mine = (double*)calloc(n ? 3 * n : 1, sizeof(double));
+      pos = (double*)malloc((n ? 3 * n : 1) * sizeof(double));
+      comdGatherByGid(s, 0, mine);
+      const size_t chunk = (size_t)1 << 28;
+      for (size_t o = 0; o < 3 * n; o += chunk) addDoubleParallel(mine + o, pos + o, (int)(3 * n - o < chunk ? 3 * n - o : chunk));
+      free(mine);
+   }
+   if (!printRank()) { free(pos); return; }
+   const int samples = s->cspSamples;
+   FILE* f = fopen(s->cspFile, "w");
+   if (!f) { printf("Error: cannot write %s\n", s->cspFile); exit(-1); }
+   fprintf(f, "# CSP: N %d threshold %.17g rCoord %.17g samples %d | columns: step, defects (csp > threshold), atoms with fewer than 12 neighbours, "
+              "mean csp (A^2, finite ones), max csp, mean coordination, atoms with coordination != 12\n", s->atoms->nGlobal, s->cspThreshold, s->cspCoord, samples);
+   const double* last = NULL;
+   for (int k = 0; k < samples; ++k) {
+      last = s->cspRows + 7 * (size_t)k;
+      fprintf(f, "%.0f %.0f %.0f %.17g %.17g %.17g %.0f\n", last[0], last[1], last[2], last[3], last[4], last[5], last[6]);
+   }
+   fclose(f);
+   if (pos && s->cspLast) {
+      f = fopen(s->cspDump, "w");
+      if (!f) { printf("Error: cannot write %s\n", s->cspDump); exit(-1); }
+      const real_t* L = s->domain->globalExtent;
+      fprintf(f, "%.0f\n", last ? last[1] : 0.0);
+      fprintf(f, "Lattice=\"%.17g 0 0 0 %.17g 0 0 0 %.17g\" Properties=species:S:1:pos:R:3:csp:R:1:coordination:I:1:gid:I:1 step=%.0f threshold=%.17g rCoord=%.17g\n",
+              (double)L[0], (double)L[1], (double)L[2], last ? last[0] : 0.0, s->cspThreshold, s->cspCoord);
+      for (size_t g = 0; g < n; ++g)
+         if (s->cspLast[g] > s->cspThreshold)
+            fprintf(f, "Cu %.17g %.17g %.17g %.17g %d %zu\n", pos[3 * g], pos[3 * g + 1], pos[3 * g + 2], s->cspLast[g], (int)s->cspLast[n + g], g);
+      fclose(f);
+   }
+   free(pos);
+   if (!yaml) return;
+   fprintf(yaml, "CSP:\n");
+   fprintf(yaml, "  threshold: %.12e\n", s->cspThreshold);
+   fprintf(yaml, "  rCoord: %.12e\n", s->cspCoord);
+   fprintf(yaml, "  samples: %d\n", samples);
+   fprintf(yaml, "  file: %s\n", s->cspFile);
+   fprintf(yaml, "  finalDefects: %.0f\n", last ? last[1] : 0.0);
+   fprintf(yaml, "  finalMeanCsp: %.12e\n", last ? last[3] : 0.0);
+   fprintf(yaml, "\n");
+   fflush(yaml);
+}
+
 Validate* initValidate(SimFlat* sim)
 {
    sumAtoms(sim);
@@ -514,6 +600,7 @@ int comdMain(int argc, char** argv)
       if (sim->pressure) { startTimer(pressureTimer); computePressure(sim); stopTimer(pressureTimer); }
       if (sim->rdfBins) { startTimer(rdfTimer); sampleRdf(sim); stopTimer(rdfTimer); }
       if (sim->msd && iStep >= sim->msdStart) { startTimer(msdTimer); if (iStep == sim->msdStart) startMsd(sim); sampleMsd(sim, iStep); stopTimer(msdTimer); }
+      if (sim->csp) { startTimer(cspTimer); sampleCsp(sim, iStep); stopTimer(cspTimer); }
       printThings(sim, iStep, getElapsedTime(timestepTimer));
       /* --msdStart between two printed steps: the interval is taken as two timestep() calls (which give the bits of one) with the origin in between */
       const int toOrigin = sim->msd && sim->msdStart > iStep && sim->msdStart < iStep + printRate ? sim->msdStart - iStep : 0;
@@ -528,11 +615,13 @@ int comdMain(int argc, char** argv)
    if (sim->pressure) { startTimer(pressureTimer); computePressure(sim); stopTimer(pressureTimer); }
    if (sim->rdfBins) { startTimer(rdfTimer); sampleRdf(sim); stopTimer(rdfTimer); }
    if (sim->msd && iStep >= sim->msdStart) { startTimer(msdTimer); if (iStep == sim->msdStart) startMsd(sim); sampleMsd(sim, iStep); stopTimer(msdTimer); }
+   if (sim->csp) { startTimer(cspTimer); sampleCsp(sim, iStep); stopTimer(cspTimer); }
    printThings(sim, iStep, getElapsedTime(timestepTimer));
    timestampBarrier("Ending simulation\n");
    if (sim->pressure) printPressureYaml(yamlFile, sim);
    if (sim->rdfBins) writeRdf(yamlFile, sim);
    if (sim->msd) writeMsd(yamlFile, sim);
+   if (sim->csp) writeCsp(yamlFile, sim);
 
    validateResult(validate, sim);
    profileStop(totalTimer);
@@ -610,6 +699,7 @@ int comdLjTable(SimFlat* s, double* x0, double* invDx, double* values)
 }
 
 double comdCutoff(SimFlat* s) { return s->pot->cutoff; }
+double comdLatticeConstant(SimFlat* s) { return s->lat; }
 double comdVolume(SimFlat* s) { return (double)s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2]; }
 
 void comdGridInfo(SimFlat* s, int out[6])

@@ -6,6 +6,7 @@
 #include "comd_host.h"
 #include <math.h>
 #include <stdlib.h>
+#include <string.h>
 
 static void advanceVelocity(SimFlat* s, real_t dt) { advanceVelocityGpu(&s->gpu, dt); }
 
@@ -114,6 +115,55 @@ int comdPairHistogram(SimFlat* s, int nBins, double rMax, double* outCounts)
    addDoubleParallel(mine, outCounts, nBins);
    for (int k = 0; k < nBins; ++k) outCounts[k] *= 0.5;
    free(local); free(mine);
+   return 0;
+}
+
+/* ---- centro-symmetry and coordination (not in the reference; comd_host.h) ---- */
+double comdDefaultCoordRadius(SimFlat* s)
+{
+   const double r = 0.5 * (M_SQRT1_2 + 1.0) * s->lat, cutoff = s->pot->cutoff;
+   return r < cutoff ? r : cutoff;
+}
+
+int comdCentroSymmetry(SimFlat* s, double rCoord, double* cspByGid, double* coordByGid)
+{
+   const double cutoff = s->pot->cutoff;
+   if (rCoord <= 0.0) rCoord = comdDefaultCoordRadius(s);
+   if (!(rCoord <= cutoff)) return -1;
+   const int cap = s->boxes->maxAtoms, nLocalBoxes = s->boxes->nLocalBoxes;
+   const size_t nSlots = (size_t)nLocalBoxes * cap, n = (size_t)s->atoms->nGlobal;
+   /* staging for the by-slot arrays, kept with the simulation: fresh pages for 64 MB at 80^3 would cost more than the kernel */
+   const size_t need = (nSlots + 1) * (sizeof(real_t) + 2 * sizeof(int)) + ((size_t)nLocalBoxes + 1) * sizeof(int);
+   if (need > s->cspStageBytes) { free(s->cspStage); s->cspStage = malloc(need); s->cspStageBytes = need; }
+   real_t* csp = (real_t*)s->cspStage;
+   int* coord = (int*)(csp + nSlots + 1);
+   int* gid = coord + nSlots + 1;
+   int* nAtoms = gid + nSlots + 1;
+   computeCentroSymmetry(&s->gpu, (real_t)rCoord, csp, coord);          /* blocks: the stream is drained, the two copies below see the same state */
+   comdMemcpyDtoH(gid, s->gpu.atoms.gid, (long)(nSlots * sizeof(int)));
+   comdMemcpyDtoH(nAtoms, s->gpu.boxes.nAtoms, (long)((size_t)nLocalBoxes * sizeof(int)));
+   const int one = getNRanks() == 1;
+   double* mine = one ? NULL : (double*)calloc(n ? 2 * n : 1, sizeof(double));
+   double* outCsp = one ? cspByGid : mine;
+   double* outCoord = one ? coordByGid : mine + n;
+   if (one) { memset(cspByGid, 0, n * sizeof(double)); memset(coordByGid, 0, n * sizeof(double)); }
+   for (int b = 0; b < nLocalBoxes; ++b)
+      for (size_t o = (size_t)b * cap, e = o + (size_t)nAtoms[b]; o < e; ++o) {
+         const size_t g = (size_t)gid[o];
+         if (g < n) { outCsp[g] = (double)csp[o]; outCoord[g] = (double)coord[o]; }
+      }
+   if (!one) {
+      /* every other rank holds 0 for a gid (and inf + 0 = inf); in chunks whose count fits addDoubleParallel's int */
+      const size_t chunk = (size_t)1 << 28;
+      startTimer(commReduceTimer);
+      for (size_t o = 0; o < n; o += chunk) {
+         const int len = (int)(n - o < chunk ? n - o : chunk);
+         addDoubleParallel(mine + o, cspByGid + o, len);
+         addDoubleParallel(mine + n + o, coordByGid + o, len);
+      }
+      stopTimer(commReduceTimer);
+   }
+   free(mine);
    return 0;
 }
 

@@ -242,6 +242,8 @@ typedef struct SimGpuSt {
    int64_t*     dispBuf;               /* device [dispN][4]: displacement records by gid (comdTrackDisplacementGpu), NULL = not tracking */
    double*      dispSumBuf;            /* device: the workgroups' partial sums for computeDisplacementSums, allocated with dispBuf */
    int          dispN;                 /* records dispBuf holds = nGlobal */
+   real_t*      cspBuf;                /* device [nLocalBoxes*maxAtoms]: the centro-symmetry parameters of computeCentroSymmetry, allocated by its first call */
+   int*         cspCoordBuf;           /* device [nLocalBoxes*maxAtoms]: its coordination numbers, allocated with cspBuf */
    void*        legs;                  /* private to the device library: what the last force launches of this simulation ran (hip/comd_device.hip ForceLegs, comdForceLegReport) */
 } SimGpu;
 
@@ -444,6 +446,17 @@ void computeVirial(SimGpu* sim, real_t* out12);
  * counters private to each workgroup in LDS, flushed with 64-bit integer atomics into a buffer zeroed on the same stream, so the result is
  * bit-reproducible; reads r and the cell tables only.  Blocks until the result is on the host. */
 void computePairHistogram(SimGpu* sim, int nBins, real_t rMax, uint64_t* outCounts);
+/* Not in the reference (CoMD has no structural analysis): per-atom defect analysis of THIS rank's local atoms (hip/csp_kernels.h).  For the atom in
+ * local slot o = cell * maxAtoms + index, with its neighbours j != i (local or halo image) closer than the force cutoff:
+ *   outCoordBySlot[o] = number of neighbours closer than rCoord, 0 < rCoord <= the force cutoff (the caller checks; the host's comdCentroSymmetry does);
+ *   outCspBySlot[o]   = the centro-symmetry parameter in Angstroms^2: the sum, in ascending order, of the 6 smallest |R_a + R_b|^2 over the 66 pairs
+ *                       of its 12 nearest neighbours' offset vectors; +inf with fewer than 12 neighbours inside the cutoff.  A tie between the 12th and
+ *                       13th nearest distance goes to the neighbour met first in the kernel's walk order.
+ * Both arrays hold nLocalBoxes * maxAtoms entries in host memory; entries of empty slots (index >= the cell's nAtoms) mean nothing.
+ * Call it when the halo images are current: after a complete force evaluation (timestep, computeForce), the same condition as computePairHistogram.  Any
+ * method.  Launched on the stream computeEnergy uses, after the force work of both streams of the overlap mode; no atomics, bit-reproducible; reads r
+ * and the cell tables, writes only its own two buffers (allocated by the first call, freed by DestroyGpu).  Blocks until the result is on the host. */
+void computeCentroSymmetry(SimGpu* sim, real_t rCoord, real_t* outCspBySlot, int* outCoordBySlot);
 /* Not in the reference: unwrapped displacements since an origin, for the mean-squared displacement (hip/msd_kernels.h).  on != 0: allocate and zero
  * one 32-byte record {dx, dy, dz, spare} per global atom id, signed 64-bit fixed point in units of 2^-32 Angstroms; from then on the drift kernels
  * of this simulation (advancePositionGpu and the fused forms, plain and Langevin) add dt p/m of every local atom into the record of its gid.  Already
