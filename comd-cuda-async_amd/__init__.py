@@ -27,6 +27,9 @@ _SFX = "_sp" if PRECISION == "single" else ""
 c_real = ctypes.c_float if PRECISION == "single" else ctypes.c_double
 c_real_p = ctypes.POINTER(c_real)
 
+# structure types of Simulation.common_neighbor_analysis(): OVITO's numbers (3, BCC, is never returned)
+CNA_OTHER, CNA_FCC, CNA_HCP, CNA_ICO = 0, 1, 2, 4
+
 
 class HostAtoms(ctypes.Structure):
     """include/comd_hip.h HostAtoms"""
@@ -139,6 +142,8 @@ def lib_host():
         lib.comdMsd.restype = ctypes.c_int
         lib.comdCentroSymmetry.argtypes = [vp, ctypes.c_double, c_double_p, c_double_p]
         lib.comdCentroSymmetry.restype = ctypes.c_int
+        lib.comdCommonNeighbors.argtypes = [vp, c_int_p, ctypes.POINTER(ctypes.c_longlong)]
+        lib.comdCommonNeighbors.restype = ctypes.c_int
         lib.comdDefaultCoordRadius.argtypes = [vp]
         lib.comdDefaultCoordRadius.restype = ctypes.c_double
         lib.comdLatticeConstant.argtypes = [vp]
@@ -482,6 +487,29 @@ class Simulation:
             threshold = 0.25 * self.lattice_constant ** 2
         csp, _ = self.centro_symmetry(r_coord)
         return np.nonzero(csp > float(threshold))[0].astype(np.int64)
+
+    # --- structure identification (not in the reference: comd-hip --cna, --cnaFile, --cnaDump) ---
+    def _cna(self, what):
+        np = self._np
+        if self.host_only:
+            raise RuntimeError(f"{what}: a host-only simulation has no device state")
+        n = self.n_global
+        types, counts = np.zeros(max(n, 1), dtype=np.int32), (ctypes.c_longlong * 5)()
+        if self.lib.comdCommonNeighbors(self.ptr, types.ctypes.data_as(c_int_p), counts) != 0:
+            raise RuntimeError(f"{what}: comdCommonNeighbors failed")
+        return types[:n], counts
+
+    def common_neighbor_analysis(self):
+        """int32[n_global] keyed by gid: the structure every atom of the current state sits in, by adaptive common neighbour analysis (Stukowski 2012)
+        on its 12 nearest neighbours inside the force cutoff -- CNA_FCC (1), CNA_HCP (2), CNA_ICO (4), CNA_OTHER (0) for everything else, atoms with
+        fewer than 12 such neighbours included; OVITO's numbers, 3 (BCC) is never returned.  Computed on the device by computeCommonNeighbors, summed
+        over the ranks (every rank gets the global array); valid whenever centro_symmetry() is."""
+        return self._cna("common_neighbor_analysis")[0]
+
+    def structure_counts(self):
+        """{"other", "fcc", "hcp", "ico"}: how many atoms common_neighbor_analysis() gives each type."""
+        counts = self._cna("structure_counts")[1]
+        return {"other": int(counts[CNA_OTHER]), "fcc": int(counts[CNA_FCC]), "hcp": int(counts[CNA_HCP]), "ico": int(counts[CNA_ICO])}
 
     # --- dynamics (not in the reference: comd-hip --msd, --msdStart, --msdFile) ---
     def track_displacement(self, on=True):

@@ -23,6 +23,7 @@
 #include "virial_kernels.h"
 #include "rdf_kernels.h"
 #include "csp_kernels.h"
+#include "cna_kernels.h"
 #include "langevin_kernels.h"
 #include "msd_kernels.h"
 
@@ -600,7 +601,7 @@ extern "C" void DestroyGpu(SimGpu* sim)
                     sim->boxes.boxIDLookUp, sim->boxes.boxIDLookUpReverse, sim->eam_pot.phiS.coefficients, sim->eam_pot.rhoS.coefficients,
                     sim->eam_pot.pairRows, sim->eam_pot.pairRowCount, sim->eam_pot.cellSel, sim->eam_pot.brickGroup, sim->eam_pot.brickList, sim->eam_pot.brickSel, sim->eam_pot.brickStats, sim->eam_pot.atomRows, sim->eam_pot.atomRowCount, sim->eam_pot.atomBrickSel,
                     sim->atoms.neighborList.brickRows, sim->atoms.neighborList.brickRowCount, sim->adapterScan, sim->lj_pot.waveCand, sim->lj_pot.waveCandCount, sim->lj_pot.packedR[0], sim->lj_pot.packedR[1], sim->lj_pot.packedF[0], sim->lj_pot.packedF[1],
-                    sim->lj_pot.lj_interpolation.values, sim->virialBuf, sim->pairHistBuf, sim->dispBuf, sim->dispSumBuf, sim->cspBuf, sim->cspCoordBuf };
+                    sim->lj_pot.lj_interpolation.values, sim->virialBuf, sim->pairHistBuf, sim->dispBuf, sim->dispSumBuf, sim->cspBuf, sim->cspCoordBuf, sim->cnaBuf };
    for (void* p : ptrs) if (p) HIP_CHECK(hipFree(p));
    if (sim->statusEvent) (void)hipEventDestroy((hipEvent_t)sim->statusEvent);
    if (sim->pinned) HIP_CHECK(hipHostFree(sim->pinned));
@@ -1216,6 +1217,28 @@ extern "C" void computeCentroSymmetry(SimGpu* sim, real_t rCoord, real_t* outCsp
    LAUNCH_CHECK();
    HIP_CHECK(hipMemcpyAsync(outCspBySlot, sim->cspBuf, nSlots * sizeof(real_t), hipMemcpyDeviceToHost, st));
    HIP_CHECK(hipMemcpyAsync(outCoordBySlot, sim->cspCoordBuf, nSlots * sizeof(int), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// Not in the reference: adaptive common neighbour analysis, the structure type of every local atom (cna_kernels.h).  One instance for every potential
+// and method, as computeCentroSymmetry, whose walk it shares.  The per-slot buffer is allocated by the first call.
+extern "C" void computeCommonNeighbors(SimGpu* sim, int* outTypeBySlot)
+{
+   hipStream_t st = S(sim->boundary_stream);
+   if (sim->interior_stream) HIP_CHECK(hipStreamSynchronize(S(sim->interior_stream)));      // -a 1: the interior cells' force work is done
+   const real_t cutoff = sim->do_eam ? sim->eam_pot.cutoff : sim->lj_pot.cutoff;
+   if ((double)sim->boxes.nTotalBoxes * sim->maxAtoms >= 2147483648.0) { fprintf(stderr, "computeCommonNeighbors: more than 2^31 slots\n"); exit(-1); }
+   const size_t nSlots = (size_t)sim->boxes.nLocalBoxes * sim->maxAtoms;
+   if (!sim->cnaBuf) sim->cnaBuf = dalloc<int>(nSlots);
+   CnaArgs v;
+   v.rx = sim->atoms.r.x; v.ry = sim->atoms.r.y; v.rz = sim->atoms.r.z;
+   v.nAtoms = sim->boxes.nAtoms; v.nbr = sim->neighbor_cells;
+   v.nLocalBoxes = sim->boxes.nLocalBoxes; v.cap = sim->maxAtoms; v.chunks = ceilDiv(sim->maxAtoms, WAVE);
+   v.rc2 = cutoff * cutoff;
+   v.type = sim->cnaBuf;
+   hipLaunchKernelGGL(Cna_thread_atom, dim3(CNA_BLOCKS), dim3(256), 0, st, v);
+   LAUNCH_CHECK();
+   HIP_CHECK(hipMemcpyAsync(outTypeBySlot, sim->cnaBuf, nSlots * sizeof(int), hipMemcpyDeviceToHost, st));
    HIP_CHECK(hipStreamSynchronize(st));
 }
 

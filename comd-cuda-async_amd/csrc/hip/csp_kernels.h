@@ -29,6 +29,8 @@
 // X[a], X[b] at run time (scratch), and predicating shares on compile-time indices leaves every lane issuing all 66 anyway.  Measured at 80^3 the EAM
 // kernel takes 4.3 ms against 10.2 ms for LJ 5 sigma: this stage and the merge are what does not shrink with the candidates.
 //
+// The walk and the merge are the text of nearest12_walk.h, which Cna_thread_atom (cna_kernels.h) includes too; the 66-pair stage is this kernel's own.
+//
 // The kernel reads r, nAtoms and nbr and writes nothing but its own two per-slot buffers; no atomics: bit-reproducible.
 #pragma once
 #include "device_common.h"
@@ -82,75 +84,9 @@ void CentroSym_thread_atom(CentroSymArgs v)
    const long w0 = (long)xcdRemap(blockIdx.x, gridDim.x) * per;
    const long w1 = w0 + per < nWork ? w0 + per : nWork;
    for (long w = w0 + wave; w < w1; w += 4) {
-      const int iBox = uniform((int)(w / v.chunks));
-      const int first = uniform((int)(w - (long)iBox * v.chunks)) * WAVE;
-      const int ni = uniform(v.nAtoms[iBox]);
-      if (first >= ni) continue;
-      // a chunk of m <= 32 atoms is replicated: reps copies of its atoms, copy q walks the stencil cells q, q + reps, ... (as PairHist_thread_atom)
-      const int m = ni - first < WAVE ? ni - first : WAVE;
-      int reps = 1;
-      while (reps < 16 && 2 * reps * m <= WAVE) reps *= 2;
-      const int span = WAVE / reps, q = lane / span;
-      const int ia = first + (lane & (span - 1));
-      const bool active = ia < first + m;
-      const int me = iBox * v.cap + (active ? ia : first);
-      const real_t xi = v.rx[me], yi = v.ry[me], zi = v.rz[me];
-
-      real_t d[CSP_NN]; int id[CSP_NN];
-#pragma unroll
-      for (int k = 0; k < CSP_NN; ++k) { d[k] = active ? v.rc2 : R(0.0); id[k] = -1; }      // an idle lane takes nothing
-      int coord = 0;
-      auto test = [&](real_t xj, real_t yj, real_t zj, int slot) {
-         const real_t dx = xj - xi, dy = yj - yi, dz = zj - zi;
-         const real_t r2 = dx*dx + dy*dy + dz*dz;
-         const bool other = slot != me;
-         coord += (other && r2 < v.rCoord2) ? 1 : 0;
-         if (other && r2 < d[CSP_NN - 1]) cspOffer<CSP_NN>(d, id, r2, slot);
-      };
-      const int* __restrict__ nb = v.nbr + (size_t)iBox * 27;
-      if (reps > 1) {
-         for (int k = q; k < 27; k += reps) {
-            const int jBox = nb[k];
-            const int nj = v.nAtoms[jBox];
-            const int base = jBox * v.cap;
-            for (int j = 0; j < nj; ++j) test(v.rx[base + j], v.ry[base + j], v.rz[base + j], base + j);
-         }
-         // the copies' sets into one: after the doubling over s every lane holds the 12 nearest of the copies lane ^ s, lane ^ 2s, ... as well
-         for (int s = span; s < WAVE; s <<= 1) {
-            const int addr = (lane ^ s) << 2;
-            real_t pd[CSP_NN]; int pi[CSP_NN];
-#pragma unroll
-            for (int k = 0; k < CSP_NN; ++k) { pd[k] = bpermuteAddrR(d[k], addr); pi[k] = __builtin_amdgcn_ds_bpermute(addr, id[k]); }
-            coord += __builtin_amdgcn_ds_bpermute(addr, coord);
-            // the lower copy's entries win ties in both lanes of a pair: the upper copy's set is rebuilt from the lower one's
-            const bool upper = (lane & s) != 0;
-#pragma unroll
-            for (int k = 0; k < CSP_NN; ++k) {
-               const real_t td = d[k]; const int ti = id[k];
-               d[k] = upper ? pd[k] : td; id[k] = upper ? pi[k] : ti;
-               pd[k] = upper ? td : pd[k]; pi[k] = upper ? ti : pi[k];
-            }
-#pragma unroll
-            for (int k = 0; k < CSP_NN; ++k)
-               if (pi[k] >= 0 && pd[k] < d[CSP_NN - 1]) cspOffer<CSP_NN>(d, id, pd[k], pi[k]);
-         }
-      } else for (int k = 0; k < 27; ++k) {
-         const int jBox = uniform(nb[k]);
-         const int nj = uniform(v.nAtoms[jBox]);
-         const int base = jBox * v.cap;
-         const real_t* __restrict__ qx = v.rx + base;
-         const real_t* __restrict__ qy = v.ry + base;
-         const real_t* __restrict__ qz = v.rz + base;
-         int j = 0;
-         for (; j + 8 <= nj; j += 8) {
-            real_t xs[8], ys[8], zs[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { xs[u] = qx[j + u]; ys[u] = qy[j + u]; zs[u] = qz[j + u]; }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) test(xs[u], ys[u], zs[u], base + j + u);
-         }
-         for (; j < nj; ++j) test(qx[j], qy[j], qz[j], base + j);
-      }
+#define NN12_COORD(x) x
+#include "nearest12_walk.h"       // the 12 nearest of the lane's atom: me, xi, yi, zi, d[], id[], coord, active, q
+#undef NN12_COORD
 
       if (active && q == 0) {
          const bool full = id[CSP_NN - 1] >= 0;

@@ -12,7 +12,9 @@
  * kernels, sampled at every printed step and written to PATH with a diffusion coefficient; the reference has no dynamical analysis),
  * --csp, --cspThreshold X, --cspCoord R, --cspFile PATH, --cspDump PATH (per-atom defect analysis: the centro-symmetry parameter of every atom's 12
  * nearest neighbours and its coordination number within R Angstroms, sampled at every printed step; a Defects column counts the atoms above X
- * Angstroms^2, PATH gets a line per sample and the dump the defect atoms of the last step as extended XYZ). */
+ * Angstroms^2, PATH gets a line per sample and the dump the defect atoms of the last step as extended XYZ),
+ * --cna, --cnaFile PATH, --cnaDump PATH (adaptive common neighbour analysis: every atom is FCC, HCP, ICO or other, sampled at every printed step; a
+ * NonFCC column, PATH gets the four counts per sample and the dump the non-FCC atoms of the last step as extended XYZ). */
 #include "comd_host.h"
 #include <getopt.h>
 #include <math.h>
@@ -48,6 +50,7 @@ Command parseCommandLine(int argc, char** argv)
    strcpy(cmd.rdfFile, "rdf.dat");
    strcpy(cmd.msdFile, "msd.dat");
    strcpy(cmd.cspFile, "csp.dat");
+   strcpy(cmd.cnaFile, "cna.dat");
    int help = 0;
 
    const ArgDef defs[] = {
@@ -97,6 +100,9 @@ Command parseCommandLine(int argc, char** argv)
       { "cspCoord",      0,  1, 'd', &cmd.cspCoord,       0, "radius of the coordination count in Angstroms (default (1/sqrt 2 + 1) lat / 2; at most the force cutoff)" },
       { "cspFile",       0,  1, 's', cmd.cspFile, sizeof cmd.cspFile, "file the samples are written to (default csp.dat)" },
       { "cspDump",       0,  1, 's', cmd.cspDump, sizeof cmd.cspDump, "extended-XYZ file of the defect atoms of the last step (default: none)" },
+      { "cna",           0,  0, 'i', &cmd.cna,            0, "adaptive common neighbour analysis (FCC / HCP / ICO / other per atom), sampled at every printed step (a NonFCC column)" },
+      { "cnaFile",       0,  1, 's', cmd.cnaFile, sizeof cmd.cnaFile, "file the structure counts are written to (default cna.dat)" },
+      { "cnaDump",       0,  1, 's', cmd.cnaDump, sizeof cmd.cnaDump, "extended-XYZ file of the non-FCC atoms of the last step (default: none)" },
    };
    const int nDefs = (int)(sizeof defs / sizeof defs[0]);
 
@@ -175,6 +181,7 @@ void printCmdYaml(FILE* file, Command* cmd)
               "  Langevin seed: %llu\n",
               cmd->langevinTemp, cmd->langevinDamp, (unsigned long long)cmd->seed);
    if (cmd->csp) fprintf(file, "  CSP file: %s\n", cmd->cspFile);
+   if (cmd->cna) fprintf(file, "  CNA file: %s\n", cmd->cnaFile);
    if (cmd->msd) fprintf(file, "  MSD from step: %d\n  MSD file: %s\n", cmd->msdStart, cmd->msdFile);
    fprintf(file, "\n");
    fflush(file);

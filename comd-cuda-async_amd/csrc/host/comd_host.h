@@ -60,6 +60,9 @@ typedef struct CommandSt {
    char cspFile[1024];    /* extension: where the print rank writes the samples (default csp.dat) */
    char cspDump[1024];    /* extension: extended-XYZ file of the defect atoms of the last step; empty = none */
    int cspThresholdSet, cspCoordSet;   /* the two values were given (a given 0 is refused, an absent one means the default) */
+   int cna;               /* extension: adaptive common neighbour analysis, FCC / HCP / ICO / other per atom, sampled at every printed step */
+   char cnaFile[1024];    /* extension: where the print rank writes the samples (default cna.dat) */
+   char cnaDump[1024];    /* extension: extended-XYZ file of the non-FCC atoms of the last step; empty = none */
 } Command;
 
 #define COMD_LANGEVIN_SEED 0x436f4d44ull     /* "CoMD" */
@@ -325,6 +328,14 @@ typedef struct SimFlatSt {
    void* cspStage;                  /* comdCentroSymmetry: host staging for the by-slot results, the gids and the occupancies, kept between calls */
    size_t cspStageBytes;
    int cspDefectsNow;               /* the Defects column of printThings: the last sample */
+   int cna;                         /* --cna: comdMain samples the structure types at every printed step */
+   char cnaFile[1024], cnaDump[1024];
+   long long* cnaRows;              /* [cnaSamples][5]: step, atoms of type OTHER, FCC, HCP, ICO */
+   int cnaSamples, cnaCap;
+   int* cnaLast;                    /* [nGlobal]: type by gid of the last sample (--cnaDump) */
+   void* cnaStage;                  /* comdCommonNeighbors: host staging for the by-slot types, the gids and the occupancies, kept between calls */
+   size_t cnaStageBytes;
+   long long cnaNonFccNow;          /* the NonFCC column of printThings: the last sample */
 } SimFlat;
 
 SimFlat* initSimulation(Command cmd);
@@ -370,12 +381,18 @@ int comdMsd(SimFlat* s, double* out7);
  * (1/sqrt 2 + 1) lat / 2, or the force cutoff where that is smaller.  -1 and nothing launched for rCoord > the force cutoff. */
 int comdCentroSymmetry(SimFlat* s, double rCoord, double* cspByGid, double* coordByGid);
 double comdDefaultCoordRadius(SimFlat* s);              /* that default */
+/* not in the reference: adaptive common neighbour analysis of the current state (valid whenever comdCentroSymmetry is), keyed by gid: typeByGid[g],
+ * nGlobal ints, is COMD_CNA_OTHER, _FCC, _HCP or _ICO (OVITO's numbers; 3, BCC, is never returned), and counts[t] the atoms of type t.  Each rank fills
+ * the entries of its local atoms from computeCommonNeighbors, the others stay 0, and the array is summed over the ranks: the same on every rank.
+ * Collective.  Returns 0. */
+enum { COMD_CNA_OTHER = 0, COMD_CNA_FCC = 1, COMD_CNA_HCP = 2, COMD_CNA_BCC = 3, COMD_CNA_ICO = 4 };
+int comdCommonNeighbors(SimFlat* s, int* typeByGid, long long counts[5]);
 void redistributeAtoms(SimFlat* sim);
 void ensureInteriorForceLaunched(SimFlat* sim);
 
 /* ---- performanceTimers.h ---- */
 enum TimerHandle { totalTimer, loopTimer, timestepTimer, positionTimer, velocityTimer, redistributeTimer, atomHaloTimer,
-                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, cspTimer, numberOfTimers };
+                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, cspTimer, cnaTimer, numberOfTimers };
 void profileStart(enum TimerHandle handle);
 void profileStop(enum TimerHandle handle);
 double getElapsedTime(enum TimerHandle handle);

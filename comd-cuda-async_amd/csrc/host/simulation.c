@@ -169,6 +169,8 @@ SimFlat* initSimulationHost(Command cmd)
    sim->cspThreshold = cmd.cspThresholdSet ? cmd.cspThreshold : 0.25 * sim->lat * sim->lat;
    sim->cspCoord = cmd.cspCoordSet ? cmd.cspCoord : comdDefaultCoordRadius(sim);
    strcpy(sim->cspFile, cmd.cspFile); strcpy(sim->cspDump, cmd.cspDump);
+   sim->cna = cmd.cna;
+   strcpy(sim->cnaFile, cmd.cnaFile); strcpy(sim->cnaDump, cmd.cnaDump);
    sanityChecks(cmd, sim->pot->cutoff, latticeConstant, sim->pot->latticeType);
    sim->species = initSpecies(sim->pot);
 
@@ -272,6 +274,7 @@ void destroySimulation(SimFlat** ps)
    free(s->rdfSum);
    free(s->msdRows);
    free(s->cspRows); free(s->cspLast); free(s->cspStage);
+   free(s->cnaRows); free(s->cnaLast); free(s->cnaStage);
    free(s->species); free(s->domain); free(s);
    *ps = NULL;
 }
@@ -295,8 +298,8 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
       s->firstPrint = 0;
       fprintf(screenOut,
               "#                                                                                         Performance\n"
-              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms%s%s%s\n",
-              s->pressure ? "    Pressure(GPa)" : "", s->msd ? "         MSD(A^2)" : "", s->csp ? "      Defects" : "");
+              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms%s%s%s%s\n",
+              s->pressure ? "    Pressure(GPa)" : "", s->msd ? "         MSD(A^2)" : "", s->csp ? "      Defects" : "", s->cna ? "       NonFCC" : "");
       fflush(screenOut);
    }
    real_t time = iStep * s->dt;
@@ -310,6 +313,7 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
    if (s->pressure) fprintf(screenOut, " %16.10f", pressureOf(s) * eVperA3inGPa);
    if (s->msd) fprintf(screenOut, " %16.10e", s->msdNow);
    if (s->csp) fprintf(screenOut, " %12d", s->cspDefectsNow);
+   if (s->cna) fprintf(screenOut, " %12lld", s->cnaNonFccNow);
    fprintf(screenOut, "\n");
 }
 
@@ -501,6 +505,72 @@ static void writeCsp(FILE* yaml, SimFlat* s)
    fflush(yaml);
 }
 
+/* --cna: one more row {step, atoms of type OTHER, FCC, HCP, ICO} */
+static void sampleCna(SimFlat* s, int iStep)
+{
+   const size_t n = (size_t)s->atoms->nGlobal;
+   if (!s->cnaLast) s->cnaLast = (int*)malloc((n ? n : 1) * sizeof(int));
+   long long counts[5];
+   comdCommonNeighbors(s, s->cnaLast, counts);
+   if (s->cnaSamples == s->cnaCap) { s->cnaCap = s->cnaCap ? 2 * s->cnaCap : 64; s->cnaRows = (long long*)realloc(s->cnaRows, (size_t)s->cnaCap * 5 * sizeof(long long)); }
+   long long* row = s->cnaRows + 5 * (size_t)s->cnaSamples++;
+   row[0] = iStep; row[1] = counts[COMD_CNA_OTHER]; row[2] = counts[COMD_CNA_FCC]; row[3] = counts[COMD_CNA_HCP]; row[4] = counts[COMD_CNA_ICO];
+   s->cnaNonFccNow = (long long)n - counts[COMD_CNA_FCC];
+}
+
+/* --cna: the file: a header line, then the rows of sampleCna.  --cnaDump: the non-FCC atoms of the last sample as extended XYZ, Cu x y z type gid, the
+ * positions gathered by gid over the ranks as the types are.  The YAML block names the file and gives the last sample's counts and HCP fraction. */
+static void writeCna(FILE* yaml, SimFlat* s)
+{
+   const size_t n = (size_t)s->atoms->nGlobal;
+   double* pos = NULL;
+   if (s->cnaDump[0]) {          /* collective: before the other ranks leave */
+      double* mine = (double*)calloc(n ? 3 * n : 1, sizeof(double));
+      pos = (double*)malloc((n ? 3 * n : 1) * sizeof(double));
+      comdGatherByGid(s, 0, mine);
+      const size_t chunk = (size_t)1 << 28;
+      for (size_t o = 0; o < 3 * n; o += chunk) addDoubleParallel(mine + o, pos + o, (int)(3 * n - o < chunk ? 3 * n - o : chunk));
+      free(mine);
+   }
+   if (!printRank()) { free(pos); return; }
+   const int samples = s->cnaSamples;
+   FILE* f = fopen(s->cnaFile, "w");
+   if (!f) { printf("Error: cannot write %s\n", s->cnaFile); exit(-1); }
+   fprintf(f, "# CNA: N %d samples %d | columns: step, atoms of type other (0), FCC (1), HCP (2), ICO (4)\n", s->atoms->nGlobal, samples);
+   const long long zero[5] = { 0, 0, 0, 0, 0 };
+   const long long* last = zero;
+   for (int k = 0; k < samples; ++k) {
+      last = s->cnaRows + 5 * (size_t)k;
+      fprintf(f, "%lld %lld %lld %lld %lld\n", last[0], last[1], last[2], last[3], last[4]);
+   }
+   fclose(f);
+   const long long nonFcc = samples ? (long long)n - last[2] : 0;
+   if (pos && s->cnaLast) {
+      f = fopen(s->cnaDump, "w");
+      if (!f) { printf("Error: cannot write %s\n", s->cnaDump); exit(-1); }
+      const real_t* L = s->domain->globalExtent;
+      fprintf(f, "%lld\n", nonFcc);
+      fprintf(f, "Lattice=\"%.17g 0 0 0 %.17g 0 0 0 %.17g\" Properties=species:S:1:pos:R:3:type:I:1:gid:I:1 step=%lld\n",
+              (double)L[0], (double)L[1], (double)L[2], last[0]);
+      for (size_t g = 0; g < n; ++g)
+         if (s->cnaLast[g] != COMD_CNA_FCC)
+            fprintf(f, "Cu %.17g %.17g %.17g %d %zu\n", pos[3 * g], pos[3 * g + 1], pos[3 * g + 2], s->cnaLast[g], g);
+      fclose(f);
+   }
+   free(pos);
+   if (!yaml) return;
+   fprintf(yaml, "CNA:\n");
+   fprintf(yaml, "  samples: %d\n", samples);
+   fprintf(yaml, "  file: %s\n", s->cnaFile);
+   fprintf(yaml, "  finalOther: %lld\n", last[1]);
+   fprintf(yaml, "  finalFCC: %lld\n", last[2]);
+   fprintf(yaml, "  finalHCP: %lld\n", last[3]);
+   fprintf(yaml, "  finalICO: %lld\n", last[4]);
+   fprintf(yaml, "  finalHCPFraction: %.12e\n", n ? (double)last[3] / (double)n : 0.0);
+   fprintf(yaml, "\n");
+   fflush(yaml);
+}
+
 Validate* initValidate(SimFlat* sim)
 {
    sumAtoms(sim);
@@ -601,6 +671,7 @@ int comdMain(int argc, char** argv)
       if (sim->rdfBins) { startTimer(rdfTimer); sampleRdf(sim); stopTimer(rdfTimer); }
       if (sim->msd && iStep >= sim->msdStart) { startTimer(msdTimer); if (iStep == sim->msdStart) startMsd(sim); sampleMsd(sim, iStep); stopTimer(msdTimer); }
       if (sim->csp) { startTimer(cspTimer); sampleCsp(sim, iStep); stopTimer(cspTimer); }
+      if (sim->cna) { startTimer(cnaTimer); sampleCna(sim, iStep); stopTimer(cnaTimer); }
       printThings(sim, iStep, getElapsedTime(timestepTimer));
       /* --msdStart between two printed steps: the interval is taken as two timestep() calls (which give the bits of one) with the origin in between */
       const int toOrigin = sim->msd && sim->msdStart > iStep && sim->msdStart < iStep + printRate ? sim->msdStart - iStep : 0;
@@ -616,12 +687,14 @@ int comdMain(int argc, char** argv)
    if (sim->rdfBins) { startTimer(rdfTimer); sampleRdf(sim); stopTimer(rdfTimer); }
    if (sim->msd && iStep >= sim->msdStart) { startTimer(msdTimer); if (iStep == sim->msdStart) startMsd(sim); sampleMsd(sim, iStep); stopTimer(msdTimer); }
    if (sim->csp) { startTimer(cspTimer); sampleCsp(sim, iStep); stopTimer(cspTimer); }
+   if (sim->cna) { startTimer(cnaTimer); sampleCna(sim, iStep); stopTimer(cnaTimer); }
    printThings(sim, iStep, getElapsedTime(timestepTimer));
    timestampBarrier("Ending simulation\n");
    if (sim->pressure) printPressureYaml(yamlFile, sim);
    if (sim->rdfBins) writeRdf(yamlFile, sim);
    if (sim->msd) writeMsd(yamlFile, sim);
    if (sim->csp) writeCsp(yamlFile, sim);
+   if (sim->cna) writeCna(yamlFile, sim);
 
    validateResult(validate, sim);
    profileStop(totalTimer);

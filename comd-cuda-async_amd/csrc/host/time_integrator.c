@@ -167,6 +167,41 @@ int comdCentroSymmetry(SimFlat* s, double rCoord, double* cspByGid, double* coor
    return 0;
 }
 
+/* ---- adaptive common neighbour analysis (not in the reference; comd_host.h) ---- */
+int comdCommonNeighbors(SimFlat* s, int* typeByGid, long long counts[5])
+{
+   const int cap = s->boxes->maxAtoms, nLocalBoxes = s->boxes->nLocalBoxes;
+   const size_t nSlots = (size_t)nLocalBoxes * cap, n = (size_t)s->atoms->nGlobal;
+   /* staging for the by-slot arrays, kept with the simulation as comdCentroSymmetry's */
+   const size_t need = (2 * (nSlots + 1) + (size_t)nLocalBoxes + 1) * sizeof(int);
+   if (need > s->cnaStageBytes) { free(s->cnaStage); s->cnaStage = malloc(need); s->cnaStageBytes = need; }
+   int* type = (int*)s->cnaStage;
+   int* gid = type + nSlots + 1;
+   int* nAtoms = gid + nSlots + 1;
+   computeCommonNeighbors(&s->gpu, type);          /* blocks: the stream is drained, the two copies below see the same state */
+   comdMemcpyDtoH(gid, s->gpu.atoms.gid, (long)(nSlots * sizeof(int)));
+   comdMemcpyDtoH(nAtoms, s->gpu.boxes.nAtoms, (long)((size_t)nLocalBoxes * sizeof(int)));
+   const int one = getNRanks() == 1;
+   int* mine = one ? typeByGid : (int*)malloc((n ? n : 1) * sizeof(int));
+   memset(mine, 0, n * sizeof(int));
+   for (int b = 0; b < nLocalBoxes; ++b)
+      for (size_t o = (size_t)b * cap, e = o + (size_t)nAtoms[b]; o < e; ++o) {
+         const size_t g = (size_t)gid[o];
+         if (g < n) mine[g] = type[o];
+      }
+   if (!one) {
+      /* every other rank holds 0 for a gid; in chunks whose count fits addIntParallel's int */
+      const size_t chunk = (size_t)1 << 28;
+      startTimer(commReduceTimer);
+      for (size_t o = 0; o < n; o += chunk) addIntParallel(mine + o, typeByGid + o, (int)(n - o < chunk ? n - o : chunk));
+      stopTimer(commReduceTimer);
+      free(mine);
+   }
+   for (int t = 0; t < 5; ++t) counts[t] = 0;
+   for (size_t g = 0; g < n; ++g) { const int t = typeByGid[g]; counts[t >= 0 && t <= 4 ? t : 0] += 1; }
+   return 0;
+}
+
 /* ---- displacement tracking (not in the reference; comd_host.h) ---- */
 int comdTrackDisplacement(SimFlat* s, int on)
 {

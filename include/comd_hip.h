@@ -244,6 +244,7 @@ typedef struct SimGpuSt {
    int          dispN;                 /* records dispBuf holds = nGlobal */
    real_t*      cspBuf;                /* device [nLocalBoxes*maxAtoms]: the centro-symmetry parameters of computeCentroSymmetry, allocated by its first call */
    int*         cspCoordBuf;           /* device [nLocalBoxes*maxAtoms]: its coordination numbers, allocated with cspBuf */
+   int*         cnaBuf;                /* device [nLocalBoxes*maxAtoms]: the structure types of computeCommonNeighbors, allocated by its first call */
    void*        legs;                  /* private to the device library: what the last force launches of this simulation ran (hip/comd_device.hip ForceLegs, comdForceLegReport) */
 } SimGpu;
 
@@ -457,6 +458,15 @@ void computePairHistogram(SimGpu* sim, int nBins, real_t rMax, uint64_t* outCoun
  * method.  Launched on the stream computeEnergy uses, after the force work of both streams of the overlap mode; no atomics, bit-reproducible; reads r
  * and the cell tables, writes only its own two buffers (allocated by the first call, freed by DestroyGpu).  Blocks until the result is on the host. */
 void computeCentroSymmetry(SimGpu* sim, real_t rCoord, real_t* outCspBySlot, int* outCoordBySlot);
+/* Not in the reference: adaptive common neighbour analysis of THIS rank's local atoms (hip/cna_kernels.h; Stukowski 2012, the 12-neighbour signatures).
+ * outTypeBySlot[o], o = cell * maxAtoms + index, is the structure the atom sits in, with OVITO's numbers: 1 FCC (its 12 nearest neighbours all have
+ * the signature (4,2,1)), 2 HCP (six (4,2,1), six (4,2,2)), 4 ICO (twelve (5,5,5)), 0 everything else, atoms with fewer than 12 neighbours inside the
+ * force cutoff included; 3 (BCC) is never returned.  The 12 nearest are the ones computeCentroSymmetry takes, ties included; two of them are bonded
+ * when no further apart than (1 + sqrt 2)/2 times the mean of the 12 distances.  nLocalBoxes * maxAtoms entries in host memory; entries of empty slots
+ * mean nothing.  Valid when computeCentroSymmetry is (halo images current, any method, cells sized for cutoff + skin and not re-binned included); same
+ * stream, no atomics, bit-reproducible; reads r and the cell tables, writes only its own buffer (allocated by the first call, freed by DestroyGpu).
+ * Blocks until the result is on the host. */
+void computeCommonNeighbors(SimGpu* sim, int* outTypeBySlot);
 /* Not in the reference: unwrapped displacements since an origin, for the mean-squared displacement (hip/msd_kernels.h).  on != 0: allocate and zero
  * one 32-byte record {dx, dy, dz, spare} per global atom id, signed 64-bit fixed point in units of 2^-32 Angstroms; from then on the drift kernels
  * of this simulation (advancePositionGpu and the fused forms, plain and Langevin) add dt p/m of every local atom into the record of its gid.  Already
