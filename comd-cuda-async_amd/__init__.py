@@ -152,6 +152,14 @@ def lib_host():
         lib.comdCutoff.restype = ctypes.c_double
         lib.comdVolume.argtypes = [vp]
         lib.comdVolume.restype = ctypes.c_double
+        lib.comdSetBox.argtypes = [vp, c_double_p]
+        lib.comdSetBox.restype = ctypes.c_int
+        lib.comdDeformTo.argtypes = [vp, c_double_p]
+        lib.comdDeformTo.restype = ctypes.c_int
+        lib.comdSetStrainRate.argtypes = [vp, c_double_p]
+        lib.comdSetStrainRate.restype = ctypes.c_int
+        lib.comdGetBox.argtypes = [vp, c_double_p]
+        lib.comdLocalBounds.argtypes = [vp, c_double_p]
         lib.comdSetLangevin.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_int]
         lib.comdSetLangevin.restype = ctypes.c_int
         lib.comdGetLangevin.argtypes = [vp, c_double_p, ctypes.POINTER(ctypes.c_uint64)]
@@ -510,6 +518,73 @@ class Simulation:
         """{"other", "fcc", "hcp", "ico"}: how many atoms common_neighbor_analysis() gives each type."""
         counts = self._cna("structure_counts")[1]
         return {"other": int(counts[CNA_OTHER]), "fcc": int(counts[CNA_FCC]), "hcp": int(counts[CNA_HCP]), "ico": int(counts[CNA_ICO])}
+
+    # --- box deformation (not in the reference: comd-hip --erateX, --erateY, --erateZ, --deformStart, --deformFile) ---
+    def _box6(self):
+        out = (ctypes.c_double * 6)()
+        self.lib.comdGetBox(self.ptr, out)
+        return self._np.array(out[0:6], dtype=self._np.float64)
+
+    @property
+    def box(self):
+        """float64 (3,): the current extents of the global box in Angstroms (its origin is 0)."""
+        return self._box6()[0:3].copy()
+
+    @property
+    def box0(self):
+        """float64 (3,): the extents the simulation was created with."""
+        return self._box6()[3:6].copy()
+
+    @property
+    def strain(self):
+        """float64 (3,): the engineering strain box / box0 - 1."""
+        b = self._box6()
+        return b[0:3] / b[3:6] - 1.0
+
+    @property
+    def volume(self):
+        """The current volume of the global box in Angstroms^3."""
+        return self.lib.comdVolume(self.ptr)
+
+    def local_bounds(self):
+        """(localMin, localMax): float64 (3,) each, this rank's brick of the global box."""
+        out = (ctypes.c_double * 6)()
+        self.lib.comdLocalBounds(self.ptr, out)
+        return self._np.array(out[0:3], dtype=self._np.float64), self._np.array(out[3:6], dtype=self._np.float64)
+
+    def set_box(self, extents):
+        """Remap to a box of `extents` (3 lengths in Angstroms): every atom's position is scaled with the box, L_new / L_old per axis about the origin, on the
+        device (momenta stay: LAMMPS's `remap x`); then the atoms are redistributed (with Verlet lists: the lists built), the forces evaluated and the
+        energies read, so energy(), virial(), gather() and the analyses see the new state.  Every rank of a multi-rank run makes the call.  ValueError, state
+        unchanged, for an extent that is not positive or a box whose link cells would be narrower than the interaction range the grid was built for (the
+        cutoff, plus the skin with thread_atom_nl and -L).  On a host-only simulation only the host geometry changes (Domain, LinkCell, the periodic
+        shifts); no atom moves."""
+        np = self._np
+        L = np.ascontiguousarray(np.broadcast_to(np.asarray(extents, dtype=np.float64), (3,)))
+        fn = self.lib.comdSetBox if self.host_only else self.lib.comdDeformTo
+        if fn(self.ptr, L.ctypes.data_as(c_double_p)) != 0:
+            raise ValueError(f"set_box: extents {L.tolist()} refused: they must be positive and leave every link cell at least as wide as the range the grid was built for")
+
+    def deform(self, scale):
+        """set_box(box * scale); a scalar scales all three axes."""
+        if self.host_only:
+            raise RuntimeError("deform: a host-only simulation has no atoms to remap (set_box changes its geometry)")
+        np = self._np
+        self.set_box(self.box * np.broadcast_to(np.asarray(scale, dtype=np.float64), (3,)))
+
+    def set_strain_rate(self, rates_per_ps):
+        """Engineering strain rates (x, y, z) in 1/ps for the coming step() calls (1e9/s = 0.001; negative compresses): at the top of every step the box is
+        set to box0 (1 + strain), the strain growing by rate dt / 1000 per step from its current value, and the positions are remapped with it.
+        (0, 0, 0) switches it off.  A scalar is refused: say which axes."""
+        if self.host_only:
+            raise RuntimeError("set_strain_rate: a host-only simulation has no integrator")
+        np = self._np
+        r = np.asarray(rates_per_ps, dtype=np.float64)
+        if r.shape != (3,):
+            raise ValueError(f"set_strain_rate: need three rates (x, y, z) in 1/ps (got {rates_per_ps!r})")
+        r = np.ascontiguousarray(r)
+        if self.lib.comdSetStrainRate(self.ptr, r.ctypes.data_as(c_double_p)) != 0:
+            raise ValueError(f"set_strain_rate: rates {r.tolist()} refused (not finite, or the simulation runs in profile mode -s)")
 
     # --- dynamics (not in the reference: comd-hip --msd, --msdStart, --msdFile) ---
     def track_displacement(self, on=True):

@@ -26,6 +26,7 @@
 #include "cna_kernels.h"
 #include "langevin_kernels.h"
 #include "msd_kernels.h"
+#include "deform_kernels.h"
 
 static int g_rank = 0;
 
@@ -349,6 +350,10 @@ extern "C" void AllocateGpu(SimGpu* sim, const GpuConfig* cfg)
    sim->maxAtoms = cfg->maxAtoms;
    sim->needEnergy = 1;
    sim->latticeConstant = cfg->latticeConstant;
+   {  // (the expression the launch layer evaluated on LinkCellGpu.invBoxSize at every launch while the box could not change)
+      const real_t i0 = 1.0 / cfg->boxSize[0], i1 = 1.0 / cfg->boxSize[1], i2 = 1.0 / cfg->boxSize[2];
+      sim->cellVolume0 = 1.0 / (i0 * i1 * i2);
+   }
    sim->do_eam = cfg->do_eam;
    sim->mass = cfg->mass;
    const ComdTuning& tune = tuningOf(sim);
@@ -1044,6 +1049,10 @@ static SkinCheck skinCheckOf(SimGpu* sim)
    if (!n->lastR.x || n->nBuilds == 0 || n->forceRebuildFlag) return sk;
    sk.lastX = n->lastR.x; sk.lastY = n->lastR.y; sk.lastZ = n->lastR.z; sk.skinHalf2 = n->skinDistanceHalf2;
    sk.softHalf2 = n->softHalf2 > R(0.0) ? n->softHalf2 : n->skinDistanceHalf2;
+   if (n->affineBudget > R(0.0) && n->affineBudget < R(1.0)) {      // a box compressed since the build has eaten into the skin (comdSetListBudgetGpu)
+      const real_t b2 = n->affineBudget * n->affineBudget;
+      sk.skinHalf2 *= b2; sk.softHalf2 *= b2;
+   }
    sk.hard = n->updateRequired + 1; sk.soft = n->updateRequired + 2; sk.progress = n->updateRequired + 3; sk.stamp = ++n->driftCount;
    n->checkFused = 1;
    return sk;
@@ -1101,6 +1110,31 @@ extern "C" void advanceVelocityVelocityPositionLangevinGpu(SimGpu* sim, real_t d
                       sim->boxes.nAtoms, sim->boxes.nLocalBoxes, sim->maxAtoms, dtKick1, dtKick2, dtHalfDrift, langevinOf(c1, c2, kT, seed, step),
                       sk, dispTrackOf(sim), integratorLaneBits(sim));
    LAUNCH_CHECK();
+}
+
+// Not in the reference: the affine remap of the positions to a new box (deform_kernels.h) and the device copy of the geometry that goes with it.  Lists built:
+// their snapshot lastR is scaled in the same pass.  Grid sizes, capacities and cell lists do not change; whatever the kernels derive from the geometry
+// (ljBoxMargins, the geometry of the EAM bricks, the packed positions of LJ thread_atom) is derived from sim->boxes at every launch.
+extern "C" void comdRemapBoxGpu(SimGpu* sim, const double scale[3], const real_t localMin[3], const real_t localMax[3], const real_t boxSize[3], comdStream_t stream)
+{
+   NeighborListGpu* n = &sim->atoms.neighborList;
+   RemapSnapshot last = { nullptr, nullptr, nullptr };
+   if (n->lastR.x && n->nBuilds > 0) { last.x = n->lastR.x; last.y = n->lastR.y; last.z = n->lastR.z; }
+   hipLaunchKernelGGL(RemapBox, integratorGrid(sim), dim3(256), 0, S(stream), sim->atoms.r.x, sim->atoms.r.y, sim->atoms.r.z, last,
+                      sim->boxes.nAtoms, sim->boxes.nLocalBoxes, sim->maxAtoms, (real_t)scale[0], (real_t)scale[1], (real_t)scale[2], integratorLaneBits(sim));
+   LAUNCH_CHECK();
+   for (int a = 0; a < 3; ++a) {
+      sim->boxes.localMin[a] = localMin[a]; sim->boxes.localMax[a] = localMax[a];
+      sim->boxes.invBoxSize[a] = 1.0 / boxSize[a];
+   }
+}
+
+// Verlet lists under a changing box: `budget` in (0, 1] is the share of skin/2 that is left for the non-affine motion of an atom once the compression of the box
+// since the build has been paid for, (skin - e_c (rc + skin)) / skin; the hard and the soft threshold of the skin test are scaled by it.
+// 1 (and the value after every build): the reference's rule, bit for bit.
+extern "C" void comdSetListBudgetGpu(SimGpu* sim, double budget)
+{
+   sim->atoms.neighborList.affineBudget = budget >= 1.0 ? R(1.0) : (real_t)budget;
 }
 
 extern "C" void computeEnergy(SimGpu* sim, real_t* eLocal)
@@ -1549,7 +1583,8 @@ extern "C" int neighborListUpdateRequiredGpu(SimGpu* sim)
    *n->updateRequiredHost = 0;                               // (raised only; cleared here, when nothing that writes it is in flight)
    hipLaunchKernelGGL(NeighborListUpdateRequired, dim3(ceilDiv((long)sim->boxes.nLocalBoxes * sim->maxAtoms, 256)), dim3(256), 0, st,
                       sim->atoms.r.x, sim->atoms.r.y, sim->atoms.r.z, n->lastR.x, n->lastR.y, n->lastR.z,
-                      sim->boxes.nAtoms, sim->boxes.nLocalBoxes, sim->maxAtoms, n->skinDistanceHalf2, n->updateRequired);
+                      sim->boxes.nAtoms, sim->boxes.nLocalBoxes, sim->maxAtoms,
+                      n->affineBudget > R(0.0) && n->affineBudget < R(1.0) ? n->skinDistanceHalf2 * n->affineBudget * n->affineBudget : n->skinDistanceHalf2, n->updateRequired);
    LAUNCH_CHECK();
    HIP_CHECK(hipStreamSynchronize(st));
    const int v = *(volatile int*)n->updateRequiredHost;

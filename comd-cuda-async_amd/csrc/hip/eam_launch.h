@@ -38,7 +38,10 @@ static int eamRowsPerAtom(const SimGpu* sim, double factor, int lo, int hi)
    const int rows = ((int)(SPHERE_VOLUME * rc * rc * rc * 4.0 / (lat * lat * lat) * factor) + 7) / 8 * 8;
    return rows < lo ? lo : rows > hi ? hi : rows;
 }
-static double eamCellVolume(const SimGpu* sim) { return 1.0 / (sim->boxes.invBoxSize[0] * sim->boxes.invBoxSize[1] * sim->boxes.invBoxSize[2]); }
+// The volume of a link cell AS ALLOCATED (AllocateGpu), not the current one: everything sized from it -- row threads and with them the stride of the row buffers of
+// thread_atom, LDS slices, the first guess of an image -- is an estimate of how many atoms a cell holds, and a box remapped by comdRemapBoxGpu stretches its cells WITH
+// their atoms.  Derived from the current volume, the row stride of launchEamAtomBrick changed under a stretched box while its buffers kept the stride they were allocated with.
+static double eamCellVolume(const SimGpu* sim) { return sim->cellVolume0; }
 // a launch with dynamic LDS: the size is allowed for the kernel first
 template <typename... P, typename... A>
 static void launchLds(void (*kernel)(P...), int grid, int threads, size_t lds, hipStream_t st, const A&... args)
@@ -309,7 +312,7 @@ static void launchEamAtomBrick(SimGpu* sim, const EamArgs& a, int num_cells, int
    int rows = t.eamAtomRows ? t.eamAtomRows : eamRowsPerAtom(sim, 1.5, 32, 128);      // (COMD_EAM_ATOM_ROWS: tests, rows that overflow)
    EamBrickArgs b;
    eamBrickGeometry(sim, &b);      // (the grid; the shape is this method's own)
-   const double lat = latticeConstantOf(sim), perCell = 4.0 / (lat * lat * lat) / (sim->boxes.invBoxSize[0] * sim->boxes.invBoxSize[1] * sim->boxes.invBoxSize[2]);      // atoms of a cell at the lattice's density
+   const double lat = latticeConstantOf(sim), perCell = 4.0 / (lat * lat * lat) * eamCellVolume(sim);      // atoms of a cell at the lattice's density
    // the threads that take atoms: whole waves for the brick's atoms + 8 % (a fuller brick's threads take a second atom)
    auto rowThreadsOf = [&](double atoms) { int th = ((int)(atoms * 1.08) + 63) / 64 * 64; return th < 64 ? 64 : th > EAM_ATOM_BRICK_THREADS ? EAM_ATOM_BRICK_THREADS : th; };
    // The brick: as many atoms as the workgroup has threads, the block within the 192 cells the staging covers, two workgroups per CU (80 KB of LDS each) in

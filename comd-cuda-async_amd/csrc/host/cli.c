@@ -14,7 +14,9 @@
  * nearest neighbours and its coordination number within R Angstroms, sampled at every printed step; a Defects column counts the atoms above X
  * Angstroms^2, PATH gets a line per sample and the dump the defect atoms of the last step as extended XYZ),
  * --cna, --cnaFile PATH, --cnaDump PATH (adaptive common neighbour analysis: every atom is FCC, HCP, ICO or other, sampled at every printed step; a
- * NonFCC column, PATH gets the four counts per sample and the dump the non-FCC atoms of the last step as extended XYZ). */
+ * NonFCC column, PATH gets the four counts per sample and the dump the non-FCC atoms of the last step as extended XYZ),
+ * --erateX R, --erateY R, --erateZ R, --deformStart S, --deformFile PATH (box deformation: engineering strain rates in 1/ps applied from global step S on, the
+ * positions remapped affinely at the top of every step; V/V0 and Sxx(GPa) columns, PATH gets strain, box and stress tensor per sample; the reference's box is fixed). */
 #include "comd_host.h"
 #include <getopt.h>
 #include <math.h>
@@ -51,6 +53,7 @@ Command parseCommandLine(int argc, char** argv)
    strcpy(cmd.msdFile, "msd.dat");
    strcpy(cmd.cspFile, "csp.dat");
    strcpy(cmd.cnaFile, "cna.dat");
+   strcpy(cmd.deformFile, "deform.dat");
    int help = 0;
 
    const ArgDef defs[] = {
@@ -103,6 +106,11 @@ Command parseCommandLine(int argc, char** argv)
       { "cna",           0,  0, 'i', &cmd.cna,            0, "adaptive common neighbour analysis (FCC / HCP / ICO / other per atom), sampled at every printed step (a NonFCC column)" },
       { "cnaFile",       0,  1, 's', cmd.cnaFile, sizeof cmd.cnaFile, "file the structure counts are written to (default cna.dat)" },
       { "cnaDump",       0,  1, 's', cmd.cnaDump, sizeof cmd.cnaDump, "extended-XYZ file of the non-FCC atoms of the last step (default: none)" },
+      { "erateX",        0,  1, 'd', &cmd.erate[0],       0, "engineering strain rate of the box along x in 1/ps (1e9/s = 0.001; negative compresses; V/V0 and Sxx(GPa) columns)" },
+      { "erateY",        0,  1, 'd', &cmd.erate[1],       0, "engineering strain rate of the box along y in 1/ps" },
+      { "erateZ",        0,  1, 'd', &cmd.erate[2],       0, "engineering strain rate of the box along z in 1/ps" },
+      { "deformStart",   0,  1, 'i', &cmd.deformStart,    0, "global step straining begins at (default 0)" },
+      { "deformFile",    0,  1, 's', cmd.deformFile, sizeof cmd.deformFile, "file the stress-strain samples are written to (default deform.dat)" },
    };
    const int nDefs = (int)(sizeof defs / sizeof defs[0]);
 
@@ -183,6 +191,8 @@ void printCmdYaml(FILE* file, Command* cmd)
    if (cmd->csp) fprintf(file, "  CSP file: %s\n", cmd->cspFile);
    if (cmd->cna) fprintf(file, "  CNA file: %s\n", cmd->cnaFile);
    if (cmd->msd) fprintf(file, "  MSD from step: %d\n  MSD file: %s\n", cmd->msdStart, cmd->msdFile);
+   if (cmd->erate[0] != 0.0 || cmd->erate[1] != 0.0 || cmd->erate[2] != 0.0)
+      fprintf(file, "  Strain rates: [ %g, %g, %g ] 1/ps\n  Deform from step: %d\n  Deform file: %s\n", cmd->erate[0], cmd->erate[1], cmd->erate[2], cmd->deformStart, cmd->deformFile);
    fprintf(file, "\n");
    fflush(file);
 }

@@ -63,6 +63,9 @@ typedef struct CommandSt {
    int cna;               /* extension: adaptive common neighbour analysis, FCC / HCP / ICO / other per atom, sampled at every printed step */
    char cnaFile[1024];    /* extension: where the print rank writes the samples (default cna.dat) */
    char cnaDump[1024];    /* extension: extended-XYZ file of the non-FCC atoms of the last step; empty = none */
+   double erate[3];       /* extension: engineering strain rates of the box along x, y, z in 1/ps (1e9/s = 0.001), negative compresses; all 0 = a fixed box, as in the reference */
+   int deformStart;       /* extension: the global step straining begins at (default 0) */
+   char deformFile[1024]; /* extension: where the print rank writes the stress-strain samples (default deform.dat) */
 } Command;
 
 #define COMD_LANGEVIN_SEED 0x436f4d44ull     /* "CoMD" */
@@ -102,6 +105,7 @@ typedef struct DomainSt {
    real_t localMin[3], localMax[3], localExtent[3];
 } Domain;
 Domain* initDecomposition(int xproc, int yproc, int zproc, const real_t globalExtent[3]);
+void setDomainExtent(Domain* domain, const real_t globalExtent[3]);    /* global and local extents of a decomposition: initDecomposition and comdSetBox */
 int processorNum(Domain* domain, int dix, int diy, int diz);
 
 /* ---- linkCells.h ---- */
@@ -113,8 +117,10 @@ typedef struct LinkCellSt {
    int maxAtoms;          /* slot capacity per cell */
    int *boxIDLookUp, *boxIDLookUpReverse;   /* -H: Hilbert numbering of the local cells (linkCells.h:27-28); NULL otherwise */
    CellGeom geom;
+   real_t builtRange;     /* the interaction range the grid was sized for (cutoff, + skin for the *_nl methods): no cell may become narrower (comdSetBox) */
 } LinkCell;
 LinkCell* initLinkCells(const Domain* domain, real_t cutoff, int useHilbert);
+void setLinkCellExtent(LinkCell* boxes, const Domain* domain);          /* bounds, cell widths and geom of the same grid over the domain as it is now */
 void destroyLinkCells(LinkCell** boxes);
 int getNeighborBoxes(LinkCell* boxes, int iBox, int* nbrBoxes);
 int getBoxFromTuple(LinkCell* boxes, int x, int y, int z);
@@ -253,6 +259,7 @@ typedef struct ForceExchangeParmsSt {
    /* mirror map of the self-neighbour tail firstAxis..2 (built on first use): halo cell mirrorDst[k] is the image of mirrorSrc[k] displaced by mirrorShift[3k..] */
    int mirrorFirst, mirrorPairs;
    int *mirrorDstGpu, *mirrorSrcGpu; real_t* mirrorShiftGpu;
+   int mirrorStale;                       /* haloSetBox: shift[][] has changed since mirrorShiftGpu was filled */
    real_t shift[6][3];
    int msgBytesCached[6];                 /* positions: message sizes are fixed between list builds; -1 = unknown */
    int sendBound[6];                      /* agreed message sizes in atoms, 0 = none */
@@ -263,6 +270,7 @@ HaloExchange* initForceHaloExchange(Domain* domain, LinkCell* boxes, int allocDe
 /* Verlet-list mode: refresh of the halo copies' positions between list builds, over the force exchange's cell lists */
 HaloExchange* initPositionHaloExchange(Domain* domain, LinkCell* boxes, int allocDevice);
 void preparePositionExchange(HaloExchange* positionExchange, struct SimFlatSt* sim);   /* after every list build */
+void haloSetBox(HaloExchange* haloExchange, const Domain* domain);                     /* the periodic shifts (and the mirror path's table of them) after comdSetBox */
 void destroyHaloExchange(HaloExchange** haloExchange);
 void invalidateHaloSizes(HaloExchange* haloExchange);      /* the next exchange of every axis swaps exact sizes again */
 void haloExchange(HaloExchange* haloExchange, void* data);
@@ -336,6 +344,21 @@ typedef struct SimFlatSt {
    void* cnaStage;                  /* comdCommonNeighbors: host staging for the by-slot types, the gids and the occupancies, kept between calls */
    size_t cnaStageBytes;
    long long cnaNonFccNow;          /* the NonFCC column of printThings: the last sample */
+   /* box deformation (--erateX/Y/Z, comdSetBox, comdSetStrainRate): the box is box0 (1 + strain), strain = deformEpsBase + erate * deformTime / 1000 */
+   double box0[3];                  /* the global extents the simulation was created with */
+   double erate[3];                 /* strain rates in 1/ps */
+   int deform;                      /* a rate is non-zero: timestep() sets the box at the top of every step from deformStart on */
+   int deformStart;
+   double deformTime;               /* fs strained at the current rates */
+   double deformEpsBase[3];         /* the strain the current rates started from */
+   double nextExtent[3];            /* the extents the remap of the coming step will set (the current ones when nothing strains): the list rule looks a step ahead */
+   double listExtent[3];            /* *_nl: the global extents at the last list build */
+   int boxChanged;                  /* comdSetBox has changed the box at least once: g(r) is normalised with the mean density of its samples */
+   double rdfDensitySum;            /* sum over the g(r) samples of N / V */
+   int deformReport;                /* comdMain: V/V0 and Sxx(GPa) columns, the samples below, the file and the YAML block */
+   char deformFile[1024];
+   double* deformRows;              /* [deformSamples][15]: step, time (fs), strain (3), extents (3), volume, stress xx yy zz yz xz xy (GPa), temperature (K) */
+   int deformSamples, deformCap;
 } SimFlat;
 
 SimFlat* initSimulation(Command cmd);
@@ -387,12 +410,31 @@ double comdDefaultCoordRadius(SimFlat* s);              /* that default */
  * Collective.  Returns 0. */
 enum { COMD_CNA_OTHER = 0, COMD_CNA_FCC = 1, COMD_CNA_HCP = 2, COMD_CNA_BCC = 3, COMD_CNA_ICO = 4 };
 int comdCommonNeighbors(SimFlat* s, int* typeByGid, long long counts[5]);
+/* not in the reference (its box is nx lat for the whole run): box deformation, LAMMPS's `fix deform ... remap x`.
+ * comdSetBox: the global box becomes L[3] Angstroms (the origin stays at 0) and the positions of the local atoms are scaled with it, L_new / L_old per axis, by
+ *    comdRemapBoxGpu.  Every copy of the geometry follows: Domain (the expressions of initDecomposition, so neighbouring ranks agree bit for bit on their shared
+ *    face), LinkCell (bounds, cell widths, geom; the cell COUNT stays), the periodic shifts of the atom and position exchanges and the mirror path's table of
+ *    them, the device's LinkCellGpu.  Momenta, halo cells and the displacement records of comdTrackDisplacement are not touched: a redistribution must follow
+ *    before anything reads the cells (timestep() remaps at the top of a step; comdDeformTo does the rest itself).  Collective: every rank makes the call with
+ *    the same L.  Returns -1 with NOTHING changed or launched when an L is not positive or a cell would become narrower than the range the grid was built for
+ *    (the cutoff, + the skin for the *_nl methods): re-gridding is not implemented.  On a host-only simulation the host geometry alone changes, no atom moves.
+ * comdDeformTo: comdSetBox, then a redistribution (with lists: a list build), a force evaluation and an energy read, so that the energy, the virial, the gathered
+ *    arrays and the analyses are those of the new state.  -1 as comdSetBox.
+ * comdSetStrainRate: engineering strain rates in 1/ps for the coming timestep() calls, from the current box on; all zero = off, and timestep() is then what it was
+ *    without the feature, bit for bit.  -1, nothing changed, for a rate that is not finite or with -s (no redistribution there).
+ * comdGetBox: out[0..2] the current global extents, out[3..5] those at creation.  comdLocalBounds: out[0..2] this rank's localMin, out[3..5] its localMax. */
+int  comdSetBox(SimFlat* s, const double L[3]);
+int  comdDeformTo(SimFlat* s, const double L[3]);
+int  comdSetStrainRate(SimFlat* s, const double ratesPerPs[3]);
+void comdGetBox(SimFlat* s, double out[6]);
+void comdLocalBounds(SimFlat* s, double out[6]);
+void deformListBudget(SimFlat* s);      /* *_nl: the skin left to the displacement test by the compression since the build; after a box change and after a list build */
 void redistributeAtoms(SimFlat* sim);
 void ensureInteriorForceLaunched(SimFlat* sim);
 
 /* ---- performanceTimers.h ---- */
 enum TimerHandle { totalTimer, loopTimer, timestepTimer, positionTimer, velocityTimer, redistributeTimer, atomHaloTimer,
-                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, cspTimer, cnaTimer, numberOfTimers };
+                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, cspTimer, cnaTimer, deformTimer, numberOfTimers };
 void profileStart(enum TimerHandle handle);
 void profileStop(enum TimerHandle handle);
 double getElapsedTime(enum TimerHandle handle);

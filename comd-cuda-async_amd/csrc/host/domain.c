@@ -15,6 +15,14 @@ Domain* initDecomposition(int xproc, int yproc, int zproc, const real_t globalEx
    dd->procCoord[0] = r % xproc; r /= xproc;
    dd->procCoord[1] = r % yproc;
    dd->procCoord[2] = r / yproc;
+   setDomainExtent(dd, globalExtent);
+   return dd;
+}
+
+/* the extents of the global box and of this rank's brick of it: the one place they are computed (initDecomposition, comdSetBox), so that two ranks always agree
+ * bit for bit on the face they share -- rank c's localMax and rank c + 1's localMin are the same expression */
+void setDomainExtent(Domain* dd, const real_t globalExtent[3])
+{
    for (int a = 0; a < 3; ++a) {
       dd->globalMin[a] = 0;
       dd->globalMax[a] = globalExtent[a];
@@ -23,7 +31,6 @@ Domain* initDecomposition(int xproc, int yproc, int zproc, const real_t globalEx
       dd->localMin[a] = dd->globalMin[a] +  dd->procCoord[a]      * dd->localExtent[a];
       dd->localMax[a] = dd->globalMin[a] + (dd->procCoord[a] + 1) * dd->localExtent[a];
    }
-   return dd;
 }
 
 int processorNum(Domain* domain, int dix, int diy, int diz)

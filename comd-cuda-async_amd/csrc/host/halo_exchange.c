@@ -36,6 +36,16 @@ static HaloExchange* initHaloExchangeBase(Domain* domain)
    return hh;
 }
 
+/* periodic shift of what leaves through each face (haloExchange.c:316-323): pbcFactor * globalExtent, non-zero on the ranks at the ends of an axis */
+static void faceShifts(const Domain* domain, real_t shift[6][3])
+{
+   memset(shift, 0, 18 * sizeof(real_t));
+   for (int a = 0; a < 3; ++a) {
+      if (domain->procCoord[a] == 0)                       shift[2*a][a]     = +1.0 * domain->globalExtent[a];
+      if (domain->procCoord[a] == domain->procGrid[a] - 1) shift[2*a + 1][a] = -1.0 * domain->globalExtent[a];
+   }
+}
+
 static int* cellBlock(LinkCell* boxes, const int lo[3], const int hi[3], int nCells)
 {
    int* list = (int*)malloc((size_t)nCells * sizeof(int));
@@ -205,10 +215,7 @@ HaloExchange* initAtomHaloExchange(Domain* domain, LinkCell* boxes, int allocDev
    parms->nCells[HALO_Y_MINUS] = parms->nCells[HALO_Y_PLUS] = 2 * size1;
    parms->nCells[HALO_Z_MINUS] = parms->nCells[HALO_Z_PLUS] = 2 * size2;
    for (int f = 0; f < 6; ++f) parms->cellList[f] = mkAtomCellList(boxes, (enum HaloFaceOrder)f, parms->nCells[f]);
-   for (int a = 0; a < 3; ++a) {
-      if (domain->procCoord[a] == 0)                       parms->shift[2*a][a]     = +1.0 * domain->globalExtent[a];
-      if (domain->procCoord[a] == domain->procGrid[a] - 1) parms->shift[2*a + 1][a] = -1.0 * domain->globalExtent[a];
-   }
+   faceShifts(domain, parms->shift);
    hh->type = 0;
    hh->parms = parms;
    hh->deviceBuffers = allocDevice;
@@ -339,7 +346,8 @@ static void slotMirror(HaloExchange* hh, void* vdata, int firstAxis)
 {
    ForceExchangeParms* parms = (ForceExchangeParms*)hh->parms;
    SimFlat* s = (SimFlat*)vdata;
-   if (!parms->mirrorDstGpu || parms->mirrorFirst != firstAxis) {
+   const int rebuild = !parms->mirrorDstGpu || parms->mirrorFirst != firstAxis;
+   if (rebuild || parms->mirrorStale) {
       int n = 0;
       for (int a = firstAxis; a < 3; ++a) n += 2 * parms->nCells[2 * a];
       int* dst = (int*)malloc((size_t)n * sizeof(int)); int* src = (int*)malloc((size_t)n * sizeof(int));
@@ -360,11 +368,13 @@ static void slotMirror(HaloExchange* hh, void* vdata, int firstAxis)
                dst[k] = to; src[k] = from; for (int d = 0; d < 3; ++d) sh[3 * k + d] = t[d];
             }
          }
-      if (parms->mirrorDstGpu) { comdDeviceFree(parms->mirrorDstGpu); comdDeviceFree(parms->mirrorSrcGpu); comdDeviceFree(parms->mirrorShiftGpu); }
-      parms->mirrorDstGpu = uploadInts(dst, n); parms->mirrorSrcGpu = uploadInts(src, n);
-      parms->mirrorShiftGpu = (real_t*)comdDeviceMalloc((long)3 * n * sizeof(real_t));
+      if (rebuild) {
+         if (parms->mirrorDstGpu) { comdDeviceFree(parms->mirrorDstGpu); comdDeviceFree(parms->mirrorSrcGpu); comdDeviceFree(parms->mirrorShiftGpu); }
+         parms->mirrorDstGpu = uploadInts(dst, n); parms->mirrorSrcGpu = uploadInts(src, n);
+         parms->mirrorShiftGpu = (real_t*)comdDeviceMalloc((long)3 * n * sizeof(real_t));
+      } else comdStreamSynchronize(s->gpu.boundary_stream);      /* comdSetBox changed the shifts: the pairs stand, and the launch of the step before has read the old table */
       comdMemcpyHtoD(parms->mirrorShiftGpu, sh, (long)3 * n * sizeof(real_t));
-      parms->mirrorFirst = firstAxis; parms->mirrorPairs = n;
+      parms->mirrorFirst = firstAxis; parms->mirrorPairs = n; parms->mirrorStale = 0;
       free(dst); free(src); free(sh); free(rootOf); free(shiftOf);
    }
    mirrorSlotCellsGpu(parms->positions ? 1 : 0, parms->mirrorPairs, parms->mirrorDstGpu, parms->mirrorSrcGpu, parms->mirrorShiftGpu, &s->gpu, s->gpu.boundary_stream);
@@ -472,10 +482,7 @@ HaloExchange* initPositionHaloExchange(Domain* domain, LinkCell* boxes, int allo
       parms->recvCells[f] = mkForceRecvCellList(boxes, f, parms->nCells[f]);
       parms->msgBytesCached[f] = -1;
    }
-   for (int a = 0; a < 3; ++a) {               /* haloExchange.c:316-323 */
-      if (domain->procCoord[a] == 0)                       parms->shift[2*a][a]     = +1.0 * domain->globalExtent[a];
-      if (domain->procCoord[a] == domain->procGrid[a] - 1) parms->shift[2*a + 1][a] = -1.0 * domain->globalExtent[a];
-   }
+   faceShifts(domain, parms->shift);
    hh->type = 2;
    hh->parms = parms;
    hh->deviceBuffers = allocDevice;
@@ -496,6 +503,17 @@ HaloExchange* initPositionHaloExchange(Domain* domain, LinkCell* boxes, int allo
       hh->recvBufM = (char*)comdDeviceMalloc(hh->bufCapacity); hh->recvBufP = (char*)comdDeviceMalloc(hh->bufCapacity);
    }
    return hh;
+}
+
+/* comdSetBox: the global box has changed -- the periodic shifts of an exchange that carries some (atoms, positions; dF/drho has none) are taken from the
+ * domain again, and the folded shift table of the mirror path is dropped: slotMirror makes it again on its next call */
+void haloSetBox(HaloExchange* hh, const Domain* domain)
+{
+   if (hh->type == 0) { faceShifts(domain, ((AtomExchangeParms*)hh->parms)->shift); return; }
+   ForceExchangeParms* parms = (ForceExchangeParms*)hh->parms;
+   if (!parms->positions) return;
+   faceShifts(domain, parms->shift);
+   parms->mirrorStale = 1;
 }
 
 /* after a list build: occupancies are frozen until the next one -- scan the twelve cell lists once, forget the cached sizes */

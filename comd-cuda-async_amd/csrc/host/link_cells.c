@@ -57,13 +57,9 @@ static void hilbertOrder(LinkCell* ll)
 LinkCell* initLinkCells(const Domain* domain, real_t cutoff, int useHilbert)
 {
    LinkCell* ll = (LinkCell*)calloc(1, sizeof(LinkCell));
-   for (int a = 0; a < 3; ++a) {
-      ll->localMin[a] = domain->localMin[a];
-      ll->localMax[a] = domain->localMax[a];
-      ll->gridSize[a] = (int)(domain->localExtent[a] / cutoff);
-      ll->boxSize[a] = domain->localExtent[a] / (real_t)ll->gridSize[a];
-      ll->invBoxSize[a] = 1.0 / ll->boxSize[a];
-   }
+   for (int a = 0; a < 3; ++a) ll->gridSize[a] = (int)(domain->localExtent[a] / cutoff);
+   ll->builtRange = cutoff;
+   setLinkCellExtent(ll, domain);
    ll->nLocalBoxes = ll->gridSize[0] * ll->gridSize[1] * ll->gridSize[2];
    ll->nHaloBoxes = 2 * ((ll->gridSize[0] + 2) * (ll->gridSize[1] + ll->gridSize[2] + 2) + ll->gridSize[1] * ll->gridSize[2]);
    ll->nTotalBoxes = ll->nLocalBoxes + ll->nHaloBoxes;
@@ -72,12 +68,21 @@ LinkCell* initLinkCells(const Domain* domain, real_t cutoff, int useHilbert)
       exit(-1);
    }
    ll->nAtoms = (int*)calloc((size_t)ll->nTotalBoxes, sizeof(int));
-   for (int a = 0; a < 3; ++a) {
-      ll->geom.g[a] = ll->gridSize[a]; ll->geom.lmin[a] = ll->localMin[a]; ll->geom.lmax[a] = ll->localMax[a]; ll->geom.inv[a] = ll->invBoxSize[a];
-   }
    ll->geom.nLocal = ll->nLocalBoxes; ll->geom.nTotal = ll->nTotalBoxes;
    if (useHilbert) hilbertOrder(ll);
    return ll;
+}
+
+/* the geometry of a grid of gridSize cells over the rank's brick of the domain: the one place it is computed (initLinkCells, comdSetBox).  The cell count stays */
+void setLinkCellExtent(LinkCell* ll, const Domain* domain)
+{
+   for (int a = 0; a < 3; ++a) {
+      ll->localMin[a] = domain->localMin[a];
+      ll->localMax[a] = domain->localMax[a];
+      ll->boxSize[a] = domain->localExtent[a] / (real_t)ll->gridSize[a];
+      ll->invBoxSize[a] = 1.0 / ll->boxSize[a];
+      ll->geom.g[a] = ll->gridSize[a]; ll->geom.lmin[a] = ll->localMin[a]; ll->geom.lmax[a] = ll->localMax[a]; ll->geom.inv[a] = ll->invBoxSize[a];
+   }
 }
 
 void destroyLinkCells(LinkCell** boxes)

@@ -171,11 +171,20 @@ SimFlat* initSimulationHost(Command cmd)
    strcpy(sim->cspFile, cmd.cspFile); strcpy(sim->cspDump, cmd.cspDump);
    sim->cna = cmd.cna;
    strcpy(sim->cnaFile, cmd.cnaFile); strcpy(sim->cnaDump, cmd.cnaDump);
+   /* --erateX/Y/Z (not in the reference): the box strains at constant engineering rates; profile mode never redistributes, which the remap needs */
+   for (int a = 0; a < 3; ++a) if (!(fabs(cmd.erate[a]) < 1e300)) { printf("Error: --erate%c must be a finite rate in 1/ps (got %g).\n", 'X' + a, cmd.erate[a]); exit(-1); }
+   sim->deform = cmd.erate[0] != 0.0 || cmd.erate[1] != 0.0 || cmd.erate[2] != 0.0;
+   if (sim->deform && cmd.gpuProfile) { printf("Error: --erateX/Y/Z cannot be combined with -s (profile mode does not redistribute the atoms).\n"); exit(-1); }
+   if (cmd.deformStart < 0) { printf("Error: --deformStart must be >= 0 (got %d).\n", cmd.deformStart); exit(-1); }
+   for (int a = 0; a < 3; ++a) sim->erate[a] = cmd.erate[a];
+   sim->deformStart = cmd.deformStart; sim->deformReport = sim->deform;
+   strcpy(sim->deformFile, cmd.deformFile);
    sanityChecks(cmd, sim->pot->cutoff, latticeConstant, sim->pot->latticeType);
    sim->species = initSpecies(sim->pot);
 
    const real_t globalExtent[3] = { cmd.nx * latticeConstant, cmd.ny * latticeConstant, cmd.nz * latticeConstant };
    sim->domain = initDecomposition(cmd.xproc, cmd.yproc, cmd.zproc, globalExtent);
+   for (int a = 0; a < 3; ++a) sim->box0[a] = sim->nextExtent[a] = sim->listExtent[a] = (double)sim->domain->globalExtent[a];
    /* CoMD.c:257-268: the *_nl methods list neighbours out to cutoff + skin and size the link cells to match */
    sim->skinDistance = sim->useNL ? sim->pot->cutoff * cmd.relativeSkinDistance : 0.0;
    if (sim->useNL && printRank() && !cmd.quiet) printf("Skin-Distance: %f\n", sim->skinDistance);
@@ -275,6 +284,7 @@ void destroySimulation(SimFlat** ps)
    free(s->msdRows);
    free(s->cspRows); free(s->cspLast); free(s->cspStage);
    free(s->cnaRows); free(s->cnaLast); free(s->cnaStage);
+   free(s->deformRows);
    free(s->species); free(s->domain); free(s);
    *ps = NULL;
 }
@@ -298,8 +308,9 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
       s->firstPrint = 0;
       fprintf(screenOut,
               "#                                                                                         Performance\n"
-              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms%s%s%s%s\n",
-              s->pressure ? "    Pressure(GPa)" : "", s->msd ? "         MSD(A^2)" : "", s->csp ? "      Defects" : "", s->cna ? "       NonFCC" : "");
+              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms%s%s%s%s%s\n",
+              s->pressure ? "    Pressure(GPa)" : "", s->msd ? "         MSD(A^2)" : "", s->csp ? "      Defects" : "", s->cna ? "       NonFCC" : "",
+              s->deformReport ? "           V/V0         Sxx(GPa)" : "");
       fflush(screenOut);
    }
    real_t time = iStep * s->dt;
@@ -314,6 +325,7 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
    if (s->msd) fprintf(screenOut, " %16.10e", s->msdNow);
    if (s->csp) fprintf(screenOut, " %12d", s->cspDefectsNow);
    if (s->cna) fprintf(screenOut, " %12lld", s->cnaNonFccNow);
+   if (s->deformReport) fprintf(screenOut, " %14.10f %16.10f", (double)s->V / (s->box0[0] * s->box0[1] * s->box0[2]), -((double)s->K[0] + s->W[0]) / s->V * eVperA3inGPa);
    fprintf(screenOut, "\n");
 }
 
@@ -336,18 +348,21 @@ static void sampleRdf(SimFlat* s)
    double* counts = (double*)malloc((size_t)s->rdfBins * sizeof(double));
    if (comdPairHistogram(s, s->rdfBins, s->rdfMax, counts) != 0) { printf("Error: --rdf %d --rdfMax %g was refused.\n", s->rdfBins, s->rdfMax); exit(-1); }
    for (int k = 0; k < s->rdfBins; ++k) s->rdfSum[k] += counts[k];
+   s->rdfDensitySum += (double)s->atoms->nGlobal / ((double)s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2]);
    s->rdfSamples++;
    free(counts);
 }
 
-/* --rdf: g_k = counts_k / (samples (N/2) (N/V) (4 pi/3) ((k + 1)^3 - k^3) dr^3), the ideal-gas count of unordered pairs in the shell of bin k.
+/* --rdf: g_k = counts_k / (samples (N/2) (N/V) (4 pi/3) ((k + 1)^3 - k^3) dr^3), the ideal-gas count of unordered pairs in the shell of bin k; with a box
+ * that changed during the run (--erateX/Y/Z) N/V is the mean over the samples, and the header's V is N over that mean.
  * The file: a header line, then per bin its centre, g, the running coordination number n(r) = 2 sum counts / (samples N) up to the bin's upper edge and the
  * mean pair count per sample.  The YAML block names the file and the position of the highest peak. */
 static void writeRdf(FILE* yaml, SimFlat* s)
 {
    if (!printRank()) return;
    const int nBins = s->rdfBins, samples = s->rdfSamples;
-   const double N = (double)s->atoms->nGlobal, V = (double)s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2];
+   const double N = (double)s->atoms->nGlobal;
+   const double V = s->boxChanged && samples > 0 ? N / (s->rdfDensitySum / samples) : (double)s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2];
    const double dr = s->rdfMax / nBins, shell = 4.0 * M_PI / 3.0 * dr * dr * dr;
    FILE* f = fopen(s->rdfFile, "w");
    if (!f) { printf("Error: cannot write %s\n", s->rdfFile); exit(-1); }
@@ -571,6 +586,51 @@ static void writeCna(FILE* yaml, SimFlat* s)
    fflush(yaml);
 }
 
+/* --erateX/Y/Z: one more row {step, time, strain (3), extents (3), volume, stress = -(K + W) / V in GPa (xx yy zz yz xz xy; tension positive), temperature} from
+ * the tensors computePressure has just left in W, K, V */
+static void sampleDeform(SimFlat* s, int iStep)
+{
+   if (s->deformSamples == s->deformCap) { s->deformCap = s->deformCap ? 2 * s->deformCap : 64; s->deformRows = (double*)realloc(s->deformRows, (size_t)s->deformCap * 15 * sizeof(double)); }
+   double* row = s->deformRows + 15 * (size_t)s->deformSamples++;
+   row[0] = (double)iStep; row[1] = iStep * s->dt;
+   for (int a = 0; a < 3; ++a) { row[5 + a] = (double)s->domain->globalExtent[a]; row[2 + a] = row[5 + a] / s->box0[a] - 1.0; }
+   row[8] = (double)s->V;
+   for (int c = 0; c < 6; ++c) row[9 + c] = -((double)s->K[c] + s->W[c]) / s->V * eVperA3inGPa;
+   row[14] = (s->eKinetic / s->atoms->nGlobal) / (kB_eV * 1.5);
+}
+
+/* --erateX/Y/Z: the file: a header with N, the initial box and the rates, then the rows of sampleDeform.  The YAML block gives the rates, the start step, the
+ * final strains and box, the file and the number of samples. */
+static void writeDeform(FILE* yaml, SimFlat* s)
+{
+   if (!printRank()) return;
+   const int samples = s->deformSamples;
+   FILE* f = fopen(s->deformFile, "w");
+   if (!f) { printf("Error: cannot write %s\n", s->deformFile); exit(-1); }
+   fprintf(f, "# Deform: N %d L0 %.17g %.17g %.17g rates(1/ps) %.17g %.17g %.17g startStep %d samples %d | columns: step, time (fs), strain x y z, L x y z (A), V (A^3), "
+              "stress xx yy zz yz xz xy (GPa, tension positive), T (K)\n",
+           s->atoms->nGlobal, s->box0[0], s->box0[1], s->box0[2], s->erate[0], s->erate[1], s->erate[2], s->deformStart, samples);
+   for (int k = 0; k < samples; ++k) {
+      const double* r = s->deformRows + 15 * (size_t)k;
+      fprintf(f, "%.0f %.17g", r[0], r[1]);
+      for (int c = 2; c < 15; ++c) fprintf(f, " %.17g", r[c]);
+      fprintf(f, "\n");
+   }
+   fclose(f);
+   if (!yaml) return;
+   const real_t* L = s->domain->globalExtent;
+   fprintf(yaml, "Deform:\n");
+   fprintf(yaml, "  rates: [ %.12e, %.12e, %.12e ]\n", s->erate[0], s->erate[1], s->erate[2]);
+   fprintf(yaml, "  rateUnits: 1/ps\n");
+   fprintf(yaml, "  startStep: %d\n", s->deformStart);
+   fprintf(yaml, "  finalStrain: [ %.12e, %.12e, %.12e ]\n", (double)L[0] / s->box0[0] - 1.0, (double)L[1] / s->box0[1] - 1.0, (double)L[2] / s->box0[2] - 1.0);
+   fprintf(yaml, "  finalBox: [ %.12e, %.12e, %.12e ]\n", (double)L[0], (double)L[1], (double)L[2]);
+   fprintf(yaml, "  file: %s\n", s->deformFile);
+   fprintf(yaml, "  samples: %d\n", samples);
+   fprintf(yaml, "\n");
+   fflush(yaml);
+}
+
 Validate* initValidate(SimFlat* sim)
 {
    sumAtoms(sim);
@@ -667,7 +727,8 @@ int comdMain(int argc, char** argv)
       startTimer(commReduceTimer);
       sumAtoms(sim);
       stopTimer(commReduceTimer);
-      if (sim->pressure) { startTimer(pressureTimer); computePressure(sim); stopTimer(pressureTimer); }
+      if (sim->pressure || sim->deformReport) { startTimer(pressureTimer); computePressure(sim); stopTimer(pressureTimer); }
+      if (sim->deformReport) sampleDeform(sim, iStep);
       if (sim->rdfBins) { startTimer(rdfTimer); sampleRdf(sim); stopTimer(rdfTimer); }
       if (sim->msd && iStep >= sim->msdStart) { startTimer(msdTimer); if (iStep == sim->msdStart) startMsd(sim); sampleMsd(sim, iStep); stopTimer(msdTimer); }
       if (sim->csp) { startTimer(cspTimer); sampleCsp(sim, iStep); stopTimer(cspTimer); }
@@ -683,7 +744,8 @@ int comdMain(int argc, char** argv)
    }
    profileStop(loopTimer);
    sumAtoms(sim);
-   if (sim->pressure) { startTimer(pressureTimer); computePressure(sim); stopTimer(pressureTimer); }
+   if (sim->pressure || sim->deformReport) { startTimer(pressureTimer); computePressure(sim); stopTimer(pressureTimer); }
+   if (sim->deformReport) sampleDeform(sim, iStep);
    if (sim->rdfBins) { startTimer(rdfTimer); sampleRdf(sim); stopTimer(rdfTimer); }
    if (sim->msd && iStep >= sim->msdStart) { startTimer(msdTimer); if (iStep == sim->msdStart) startMsd(sim); sampleMsd(sim, iStep); stopTimer(msdTimer); }
    if (sim->csp) { startTimer(cspTimer); sampleCsp(sim, iStep); stopTimer(cspTimer); }
@@ -695,6 +757,7 @@ int comdMain(int argc, char** argv)
    if (sim->msd) writeMsd(yamlFile, sim);
    if (sim->csp) writeCsp(yamlFile, sim);
    if (sim->cna) writeCna(yamlFile, sim);
+   if (sim->deformReport) writeDeform(yamlFile, sim);
 
    validateResult(validate, sim);
    profileStop(totalTimer);

@@ -23,6 +23,109 @@ static Langevin langevinOf(const SimFlat* s, real_t dt)
    return l;
 }
 
+/* ---- box deformation (not in the reference; comd_host.h) ---- */
+static void extentsAt(const SimFlat* s, double t, double L[3])
+{
+   for (int a = 0; a < 3; ++a) L[a] = s->box0[a] * (1.0 + (s->deformEpsBase[a] + s->erate[a] * t / 1000.0));
+}
+
+/* One step's strain: the box is set from box0 and the strained time, never by multiplying up, so it is a pure function of the steps taken; the kernel gets
+ * L_new / L_old.  A box the grid cannot follow ends the run here, before anything is launched. */
+static void deformStep(SimFlat* s, real_t dt)
+{
+   double L[3];
+   s->deformTime += (double)dt;
+   extentsAt(s, s->deformTime, L);
+   if (comdSetBox(s, L) != 0) {
+      if (printRank())
+         printf("Error: at step %llu the box [ %g, %g, %g ] would make a link cell narrower than the %g Angstroms the grid was built for (or is not positive); "
+                "re-gridding is not implemented.\n", (unsigned long long)s->stepCount, L[0], L[1], L[2], (double)s->boxes->builtRange);
+      fflush(stdout);
+      exit(-1);
+   }
+   extentsAt(s, s->deformTime + (double)dt, s->nextExtent);
+   deformListBudget(s);
+}
+
+/* Verlet lists under a changing box.  A pair further apart than rc + skin at the build is, after the box has been compressed to the share
+ * Lambda_a of its extent at the build, still further apart than (1 - e_c) (rc + skin) before any non-affine motion, e_c = max_a max(0, 1 - Lambda_a); it stays
+ * outside rc while every atom's non-affine displacement -- what the drift kernels measure against the remapped snapshot -- is below (skin - e_c (rc + skin)) / 2.
+ * The drift kernel of a step runs before the remap of the next, so e_c is taken over the current box and the one the coming step will set.  Below half of the
+ * skin's own skin / 2 the lists are built again. */
+void deformListBudget(SimFlat* s)
+{
+   if (!s->useNL || !s->gpu.boxes.nAtoms) return;
+   double ec = 0.0;
+   for (int a = 0; a < 3; ++a) {
+      const double now = (double)s->domain->globalExtent[a], low = s->nextExtent[a] < now ? s->nextExtent[a] : now;
+      const double e = 1.0 - low / s->listExtent[a];
+      if (e > ec) ec = e;
+   }
+   const double skin = (double)s->skinDistance, budget = (skin - ec * ((double)s->pot->cutoff + skin)) / skin;
+   if (budget < 0.5) neighborListForceRebuildGpu(&s->gpu.atoms.neighborList);
+   comdSetListBudgetGpu(&s->gpu, budget < 0.5 ? 1.0 : budget);
+}
+
+int comdSetBox(SimFlat* s, const double L[3])
+{
+   Domain* dd = s->domain; LinkCell* ll = s->boxes;
+   real_t ext[3]; double scale[3];
+   for (int a = 0; a < 3; ++a) {
+      if (!(L[a] > 0.0) || !(L[a] < 1e300)) return -1;
+      ext[a] = (real_t)L[a];
+      /* the cell width setDomainExtent and setLinkCellExtent would arrive at */
+      const real_t localExtent = ext[a] / dd->procGrid[a];
+      if (!(localExtent / (real_t)ll->gridSize[a] >= ll->builtRange)) return -1;
+      scale[a] = (double)ext[a] / (double)dd->globalExtent[a];
+   }
+   setDomainExtent(dd, ext);
+   setLinkCellExtent(ll, dd);
+   if (s->atomExchange) haloSetBox(s->atomExchange, dd);
+   if (s->positionExchange) haloSetBox(s->positionExchange, dd);
+   if (s->cmdDoeam && ((EamPotential*)s->pot)->forceExchange) haloSetBox(((EamPotential*)s->pot)->forceExchange, dd);
+   if (s->gpu.boxes.nAtoms) comdRemapBoxGpu(&s->gpu, scale, ll->localMin, ll->localMax, ll->boxSize, s->gpu.boundary_stream);
+   for (int a = 0; a < 3; ++a) s->nextExtent[a] = (double)ext[a];
+   s->boxChanged = 1;
+   return 0;
+}
+
+int comdDeformTo(SimFlat* s, const double L[3])
+{
+   if (comdSetBox(s, L) != 0) return -1;
+   if (!s->gpu.boxes.nAtoms) return 0;
+   if (s->useNL) neighborListForceRebuildGpu(&s->gpu.atoms.neighborList);
+   redistributeAtoms(s);
+   computeForce(s);
+   kineticEnergyGpu(s);
+   return 0;
+}
+
+int comdSetStrainRate(SimFlat* s, const double r[3])
+{
+   const int on = r[0] != 0.0 || r[1] != 0.0 || r[2] != 0.0;
+   for (int a = 0; a < 3; ++a) if (!(r[a] == r[a]) || !(fabs(r[a]) < 1e300)) return -1;
+   if (on && s->gpuProfile) return -1;
+   for (int a = 0; a < 3; ++a) {
+      s->deformEpsBase[a] = (double)s->domain->globalExtent[a] / s->box0[a] - 1.0;
+      s->erate[a] = r[a];
+   }
+   s->deformTime = 0.0;
+   s->deform = on;
+   for (int a = 0; a < 3; ++a) s->nextExtent[a] = (double)s->domain->globalExtent[a];
+   deformListBudget(s);
+   return 0;
+}
+
+void comdGetBox(SimFlat* s, double out[6])
+{
+   for (int a = 0; a < 3; ++a) { out[a] = (double)s->domain->globalExtent[a]; out[3 + a] = s->box0[a]; }
+}
+
+void comdLocalBounds(SimFlat* s, double out[6])
+{
+   for (int a = 0; a < 3; ++a) { out[a] = (double)s->domain->localMin[a]; out[3 + a] = (double)s->domain->localMax[a]; }
+}
+
 double timestep(SimFlat* s, int nSteps, real_t dt)
 {
    const Langevin lv = langevinOf(s, dt);
@@ -36,6 +139,14 @@ double timestep(SimFlat* s, int nSteps, real_t dt)
          else advanceVelocityPositionGpu(&s->gpu, 0.5 * dt, dt);
          stopTimer(positionTimer);
          stopTimer(velocityTimer);
+      }
+
+      /* box deformation: the remap sits behind the drift that has just run (the opening kernel above, or the fused closing kernel of the step before) and in front of
+       * the redistribution, on the same stream: the re-binning, the halo images and -- with -a 1 -- the interior force work all see the final geometry */
+      if (s->deform && s->stepCount >= (uint64_t)s->deformStart) {
+         startTimer(deformTimer);
+         deformStep(s, dt);
+         stopTimer(deformTimer);
       }
 
       /* e[] is read by kineticEnergyGpu below only: the last step's forces must carry energies, the others need not
@@ -306,7 +417,8 @@ static void redistributeAtomsNL(SimFlat* sim)
     * lower threshold rebuilds the lists every 18 instead of every 22 steps; the blocking form stays the default. */
    static int deferred = -1;
    if (deferred < 0) { const char* e = getenv("COMD_NL_DEFERRED"); deferred = e && atoi(e) != 0; }
-   int need = deferred ? comdNeighborListUpdateDeferredGpu(g) : neighborListUpdateRequiredGpu(g), needAll = 0;
+   /* a box that changes every step changes the thresholds every step: the blocking form */
+   int need = deferred && !sim->deform ? comdNeighborListUpdateDeferredGpu(g) : neighborListUpdateRequiredGpu(g), needAll = 0;
    startTimer(commReduceTimer);
    maxIntParallel(&need, &needAll, 1);
    stopTimer(commReduceTimer);
@@ -321,6 +433,10 @@ static void redistributeAtomsNL(SimFlat* sim)
       preparePositionExchange(sim->positionExchange, sim);
       stopTimer(neighborListBuildTimer);
       sim->nlBuilds++;
+      if (sim->boxChanged) {          /* Lambda = 1 again */
+         for (int a = 0; a < 3; ++a) sim->listExtent[a] = (double)sim->domain->globalExtent[a];
+         deformListBudget(sim);
+      }
    } else {
       if (sim->gpuAsync) { comdStreamSynchronize(g->boundary_stream); launchInteriorForce(sim); }
       startTimer(atomHaloTimer);

@@ -1,4 +1,4 @@
-/* timers.c -- the reference's twelve wall-clock timers (+ pressure, rdf, msd, csp and cna, shown only when used) and its end-of-run report
+/* timers.c -- the reference's twelve wall-clock timers (+ pressure, rdf, msd, csp, cna and deform, shown only when used) and its end-of-run report
  * (performanceTimers.c:55-340: names, per-rank table, cross-rank statistics, three rate figures,
  * YAML block).  Like the reference's, these are host timers: GPU work lands in whichever timer
  * hits the next blocking call (performanceTimers.h:29-44).  With --deviceTimers (timersUseDevice) every
@@ -14,7 +14,7 @@
 
 static const char* timerName[numberOfTimers] = {
    "total", "loop", "timestep", "  position", "  velocity", "  redistribute", "    atomHalo",
-   "  force", "    eamHalo", "commHalo", "commReduce", "  neighborList", "pressure", "rdf", "msd", "csp", "cna"
+   "  force", "    eamHalo", "commHalo", "commReduce", "  neighborList", "pressure", "rdf", "msd", "csp", "cna", "  deform"
 };
 
 typedef struct { uint64_t start, total, count, elapsed; int minRank, maxRank; double minValue, maxValue, average, stdev; } Timers;
@@ -42,7 +42,7 @@ static void** devFree = NULL; static int nFree = 0, capFree = 0;
 static int devicePhase(enum TimerHandle h)
 {
    return h == positionTimer || h == velocityTimer || h == redistributeTimer || h == atomHaloTimer || h == computeForceTimer || h == eamHaloTimer
-          || h == neighborListBuildTimer;
+          || h == neighborListBuildTimer || h == deformTimer;
 }
 static void* devEvent(void) { return nFree > 0 ? devFree[--nFree] : comdEventCreate(); }
 static void devRelease(void* e)

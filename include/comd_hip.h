@@ -171,6 +171,7 @@ typedef struct NeighborListGpuSt {
    void*  brickStatsEvent;             /* recorded behind that copy */
    int    forceRebuildFlag;            /* host: the next neighborListUpdateRequiredGpu answers 1 without looking */
    int    nBuilds;                     /* host: builds since AllocateGpu */
+   real_t affineBudget;                /* host: comdSetListBudgetGpu -- share of skin/2 left to the skin test by the compression of the box since the build; 0 or 1: all of it */
 } NeighborListGpu;
 
 /* gpu_types.h:148-157 */
@@ -246,6 +247,7 @@ typedef struct SimGpuSt {
    int*         cspCoordBuf;           /* device [nLocalBoxes*maxAtoms]: its coordination numbers, allocated with cspBuf */
    int*         cnaBuf;                /* device [nLocalBoxes*maxAtoms]: the structure types of computeCommonNeighbors, allocated by its first call */
    void*        legs;                  /* private to the device library: what the last force launches of this simulation ran (hip/comd_device.hip ForceLegs, comdForceLegReport) */
+   double       cellVolume0;           /* host: volume of a link cell at AllocateGpu, in A^3: the occupancy estimates behind row, image and LDS sizes keep it when comdRemapBoxGpu changes the box */
 } SimGpu;
 
 /* Everything AllocateGpu needs to know about the rank's geometry and potential.
@@ -427,6 +429,18 @@ void advanceVelocityVelocityPositionLangevinGpu(SimGpu* sim, real_t dtKick1, rea
 /* computeEnergy(SimFlat*, real_t eLocal[2]), gpu_kernels.cu:1045-1059: {sum e, sum p^2/2m} of local atoms.
  * Deterministic two-stage reduction (the reference uses fp64 atomics). Blocks until the result is on the host. */
 void computeEnergy(SimGpu* sim, real_t* eLocal);
+/* Not in the reference (its box is fixed for the whole run): box deformation, LAMMPS's `fix deform ... remap x` (hip/deform_kernels.h).  One kernel on `stream`
+ * over the occupied slots of the LOCAL cells, r_a <- r_a * scale_a about the global origin (the scale formed in double by the caller, applied in real_t); with
+ * Verlet lists built, the snapshot lastR is scaled in the same pass, so the skin test keeps measuring non-affine motion only.  Momenta, halo cells and the
+ * displacement records of comdTrackDisplacementGpu are not touched.  Behind the launch the device copy of the geometry -- boxes.localMin, localMax, invBoxSize
+ * = 1 / boxSize -- takes the values given (this rank's new domain and cell widths); grid sizes, capacities and cell lists stay.  Call it directly before a
+ * redistribution (updateLinkCellsGpu + atom exchange, or the positional refresh of the list mode): that re-bins the atoms the scaling moved across a cell or
+ * domain face and refills the halo cells with the new periodic shifts. */
+void comdRemapBoxGpu(SimGpu* sim, const double scale[3], const real_t localMin[3], const real_t localMax[3], const real_t boxSize[3], comdStream_t stream);
+/* Verlet lists under a changing box: the skin test of the drift kernels and of neighborListUpdateRequiredGpu compares the displacement since the build with
+ * budget * skin/2 (the soft threshold of the deferred form scaled alike); budget in (0, 1], 1 = the reference's rule.  buildNeighborListGpu does not change it:
+ * the host that compresses the box sets it again after a build. */
+void comdSetListBudgetGpu(SimGpu* sim, double budget);
 /* Not in the reference (CoMD computes no virial): this rank's share of the pair virial and of the kinetic tensor, in eV,
  *   out12[0..5]  W_ab = sum over pairs i<j of r_ij,a f_ij,b  (r_ij = r_i - r_j to the image j interacts with, f_ij the force on i due to j),
  *   out12[6..11] K_ab = sum over local atoms of p_a p_b / m,
