@@ -205,20 +205,25 @@ def test_unfused_drift_entry_is_tracked(gpu):
 
 
 # ---------------------------------------------------------------- GPU 3: wraps, cell changes, slot churn
-def _incremental(sim, steps, box, chunk=1):
+def _incremental(sim, steps, box, chunk=1, strained=False):
     """sum over the steps of the minimum-image increment of the gathered positions -> (displacement, first positions, last positions, faces
-    crossed per atom).  Every increment must be far below box / 2 for the minimum image to be the motion: asserted."""
+    crossed per atom).  Every increment must be far below box / 2 for the minimum image to be the motion: asserted.  box: the edge of a cube or
+    the three extents.  strained: the box changes under the steps (set_strain_rate), `box` is the one before the first step and the later ones are
+    read from sim.box; a step drifts and then remaps, r_k = S_k (r_{k-1} + drift), S_k = L_k / L_{k-1}, so the increment is taken in the box of
+    before the step, inc_k = minimum_image(r_k / S_k - r_{k-1}, L_{k-1}): the non-affine displacement."""
+    box = np.broadcast_to(np.asarray(box, dtype=np.float64), (3,))
     r_first = sim.gather(0).copy()
     prev, total, crossed = r_first, np.zeros_like(r_first), np.zeros(r_first.shape[0], dtype=np.int64)
     for _ in range(steps // chunk):
         sim.step(chunk)
         r = sim.gather(0).copy()
-        raw = r - prev
+        new = sim.box if strained else box
+        raw = (r / (new / box) if strained else r) - prev
         inc = _wrap(raw, box)
-        assert np.abs(inc).max() < 0.25 * box
+        assert np.all(np.abs(inc) < 0.25 * box)
         crossed += (np.rint(raw / box) != 0).any(axis=1)
         total += inc
-        prev = r
+        prev, box = r, new
     return total, r_first, prev, crossed
 
 

@@ -89,7 +89,9 @@ def test_halved_counts_keep_every_pair(pkg):
 
 # ---------------------------------------------------------------- numpy restatement
 def _distances(pos, extent, rc):
-    """sorted distances of all ordered pairs i != j with r < rc under the minimum image (every unordered pair appears twice, with the same bits)"""
+    """sorted distances of all ordered pairs i != j with r < rc under the minimum image (every unordered pair appears twice, with the same bits);
+    extent: the edge of a cube, or the three extents of the box"""
+    extent = np.broadcast_to(np.asarray(extent, dtype=np.float64), (3,))
     out = []
     for s in range(0, len(pos), 256):
         d = pos[s:s + 256, None, :] - pos[None, :, :]
