@@ -398,7 +398,7 @@ class Simulation:
                 "eam_cover": self._EAM_COVERS[out[17]], "eam_byte_offset_limit": out[18], "eam_tables_in_lds": bool(out[19]), "eam_spline": bool(out[20]),
                 "eam_clamps_kept": bool(out[21]), "eam_stencil_records": out[22], "neighbor_list_format": out[23], "lj_prefetch": bool(out[24]),
                 "lj_full_waves_listed": out[25], "lj_full_rows_not_multiple_of_64": out[26], "lj_full_rows_own_part_not_multiple_of_8": out[27],
-                "lj_full_rows_min": out[28], "lj_prefetch_distance": out[29]}
+                "lj_full_rows_min": out[28], "lj_prefetch_distance": out[29], "nl_row_capacity": out[30], "nl_longest_row": out[31]}
 
     # --- results ---
     def energy(self):

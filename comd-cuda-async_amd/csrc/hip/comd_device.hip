@@ -1002,6 +1002,26 @@ extern "C" void comdForceLegReport(SimGpu* sim, int out[COMD_LEG_REPORT_N])
    if (sim->eam_pot.brickStats) HIP_CHECK(hipMemcpy(&out[14], sim->eam_pot.brickStats + 2, sizeof(int), hipMemcpyDeviceToHost));
    out[15] = g.eamRows; out[16] = g.eamPass3ReadsRows; out[17] = g.eamCover; out[18] = g.eamRunMax; out[19] = g.eamTablesInLds; out[20] = g.eamSpline;
    out[21] = g.eamClampsKept; out[22] = g.eamStencil; out[23] = sim->atoms.neighborList.slabFormat; out[24] = g.ljPrefetch;
+   // Verlet rows: the entries a row holds in this format, and the longest row the last build left (the counts the force kernels read: clamped to the capacity)
+   const NeighborListGpu* n = &sim->atoms.neighborList;
+   const int fmt = n->slabFormat, nCells = sim->boxes.nLocalBoxes, cap = sim->maxAtoms;
+   const int groups = fmt == 1 ? NL_GROUPS : 1;
+   out[30] = fmt == 4 ? n->brickRowLen : (fmt == 1 || fmt == 2) ? n->slabRows : (fmt == 0 && n->list) ? n->maxNeighbors : 0;
+   if (n->nBuilds > 0 && (fmt == 4 ? n->brickRowCount != nullptr : fmt != 3 && n->nNeighbors != nullptr)) {
+      const size_t slots = (size_t)nCells * groups * cap;
+      std::vector<int> counts((size_t)nCells), len(slots);
+      HIP_CHECK(hipMemcpy(counts.data(), sim->boxes.nAtoms, counts.size() * sizeof(int), hipMemcpyDeviceToHost));
+      if (fmt == 4) {
+         std::vector<unsigned short> len16(slots);
+         HIP_CHECK(hipMemcpy(len16.data(), n->brickRowCount, slots * sizeof(unsigned short), hipMemcpyDeviceToHost));
+         for (size_t s = 0; s < slots; ++s) len[s] = len16[s];
+      } else HIP_CHECK(hipMemcpy(len.data(), n->nNeighbors, slots * sizeof(int), hipMemcpyDeviceToHost));
+      int longest = 0;
+      for (int c = 0; c < nCells; ++c)
+         for (int g2 = 0; g2 < groups; ++g2)
+            for (int i = 0; i < counts[c] && i < cap; ++i) { const int v = len[((size_t)c * groups + g2) * cap + i]; if (v > longest) longest = v; }
+      out[31] = longest;
+   }
 }
 
 extern "C" void updateNeighborsGpu(SimGpu*, int*) {}

@@ -187,7 +187,9 @@ void UpdateLinkCells(AtomArrays at, int* __restrict__ nAtoms, const int* __restr
    if (nb == c) return;
    if (!comdCoordInHalo(&g, x, y, z)) { atomicOr(&status[1], 1); return; }     // flew past the halo: lost
    const int slot = atomicAdd(&nAtoms[nb], 1);
-   if (slot >= cap) { atomicOr(&status[0], 1); return; }
+   // no room: the atom stays where it is.  nAtoms[nb] now exceeds cap, so the cell is marked for CompactSortCells, which clamps the count back to the slots
+   // that exist: no force kernel ever sees an occupancy beyond cap while the run waits for the host to read the status word
+   if (slot >= cap) { atomicOr(&status[0], 1); dirty[nb] = 1; return; }
    const size_t d = (size_t)nb * cap + slot;
    at.rx[d] = x; at.ry[d] = y; at.rz[d] = z;
    at.px[d] = at.px[tid]; at.py[d] = at.py[tid]; at.pz[d] = at.pz[tid];
@@ -408,7 +410,7 @@ void UnloadAtomsBufferPacked(AtomUnpackJob j0, AtomUnpackJob j1, AtomArrays at, 
          pending = false;
       }
    }
-   if (slot >= cap) { atomicOr(&status[0], 1); return; }
+   if (slot >= cap) { atomicOr(&status[0], 1); dirty[c] = 1; return; }      // (dirty: CompactSortCells clamps the count, as after UpdateLinkCells)
    const size_t d = (size_t)c * cap + slot;
    at.gid[d] = mg[i]; at.spec[d] = mt[i];
    at.rx[d] = x; at.ry[d] = y; at.rz[d] = z;
@@ -540,7 +542,7 @@ void MirrorAtomCells(MirrorAtomsJob jb, AtomArrays at, const int* __restrict__ n
    int start = nAtoms[d];
    for (int a = firstAxis; a < axis; ++a) start += arrivals[(size_t)a * nTotal + d];
    const int k = start + at0;
-   if (k >= cap) { atomicOr(&status[0], 1); return; }
+   if (k >= cap) { atomicOr(&status[0], 1); dirty[d] = 1; return; }         // (dirty: CompactSortCells folds the arrivals in and clamps the count)
    const size_t to = (size_t)d * cap + k;
    at.gid[to] = at.gid[o]; at.spec[to] = at.spec[o];
    at.rx[to] = x; at.ry[to] = y; at.rz[to] = z;

@@ -395,7 +395,9 @@ void comdForcePathInfo(SimGpu* sim, int out[4]);
  *  [23] Verlet-list format (NeighborListGpu.slabFormat)   [24] LJ thread_atom: the launch ran the list kernel with the L2 prefetch (0 under COMD_LJ_PREFETCH=0,
  *       without lists, and for the -I kernel)
  *  [25] listed waves of more than 32 atoms (the ones that run the list loop)   [26] of them, rows whose length is no multiple of 64
- *  [27] of them, rows whose own-cell part is no multiple of 8 (the rest of the row starts off the batch grid)   [28] the shortest of their rows   [29] the prefetch distance (LJ_PREFETCH_D) */
+ *  [27] of them, rows whose own-cell part is no multiple of 8 (the rest of the row starts off the batch grid)   [28] the shortest of their rows   [29] the prefetch distance (LJ_PREFETCH_D)
+ *  [30] Verlet rows: the entries a row holds as AllocateGpu derived them from --maxNeighbors (formats 0 and 2: that number; 1: a group's share of it, rounded up to 8; 4: rounded up
+ *       to 8; 0 for pairlists and without lists)   [31] the longest row the last list build left, per atom (format 1: per atom and group), never more than [30] */
 #define COMD_LEG_REPORT_N 32
 void comdForceLegReport(SimGpu* sim, int out[COMD_LEG_REPORT_N]);
 /* updateNeighborsGpu[Async], gpu_kernels.cu:251-279: the reference materialises 27*MAXATOMS neighbour

@@ -14,6 +14,7 @@ import sys
 import numpy as np
 import pytest
 
+from test_capacities import GPU_CASE_COUNT
 from test_kernel_legs import FAMILY_LEG_COUNT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -71,6 +72,16 @@ def test_single_precision_kernel_legs(family):
     out = _run(["tests/test_kernel_legs.py"], family, "gpu", 300)
     passed = re.search(r"(\d+) passed", out)
     assert passed and int(passed.group(1)) == FAMILY_LEG_COUNT[family] and "skipped" not in out and "failed" not in out, out[-1500:]
+
+
+@pytest.mark.gpu
+def test_single_precision_capacities():
+    """tests/test_capacities.py in the float build: cells, Verlet rows and the halo exactly full and one unit short.  The states' figures are the same in float
+    (its CPU tests assert them on the float checker first), the halo's edge and the landing points are computed in float32; none skipped."""
+    _run(["tests/test_capacities.py"], None, "not gpu", 300)
+    out = _run(["tests/test_capacities.py"], None, "gpu", 600)
+    passed = re.search(r"(\d+) passed", out)
+    assert passed and int(passed.group(1)) == GPU_CASE_COUNT and "skipped" not in out and "failed" not in out, out[-1500:]
 
 
 SPLINE_CASE = r"""
