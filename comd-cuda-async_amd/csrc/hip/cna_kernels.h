@@ -11,8 +11,8 @@
 //   type       CNA_FCC 1: twelve (4,2,1); CNA_HCP 2: six (4,2,1) and six (4,2,2); CNA_ICO 4: twelve (5,5,5); CNA_OTHER 0 for the rest.  3 is OVITO's BCC,
 //              which needs 14 neighbours and a cutoff beyond the second shell: never returned.
 //
-// The walk is nearest12_walk.h, the text CentroSym_thread_atom compiles too: one wave per 64-slot chunk, lane = atom, scalar candidate stream, small
-// chunks replicated and merged by the butterfly.  After it the lane reads the 12 offset vectors again (36 values, in ascending order of distance; the
+// The mapping is the chunk walk of stencil_walk.h; the selection of the 12 and the butterfly merge of replicated chunks are nearest12_walk.h, the
+// text CentroSym_thread_atom compiles too.  After it the lane reads the 12 offset vectors again (36 values, in ascending order of distance; the
 // distances are computed from them, so the sorted keys die with the walk), and builds one 12-bit mask per neighbour from the 66 tests, all at
 // compile-time indices; from there on the offsets are dead and the state is 12 integers.
 //
@@ -39,12 +39,8 @@
 #define CNA_HCP 2
 #define CNA_ICO 4
 
-struct CnaArgs {
-   const real_t* __restrict__ rx; const real_t* __restrict__ ry; const real_t* __restrict__ rz;
-   const int* __restrict__ nAtoms;
-   const int* __restrict__ nbr;        // [nLocal*27], self first
-   int nLocalBoxes, cap, chunks;       // chunks = 64-slot chunks per cell
-   real_t rc2;                         // cutoff^2
+struct CnaArgs : StencilArgs {
+   real_t rc2;                        // cutoff^2
    int* __restrict__ type;             // [nLocalBoxes*cap]
 };
 
@@ -63,13 +59,9 @@ void Cna_thread_atom(CnaArgs v)
 {
    const int lane = laneId(), wave = (int)threadIdx.x >> 6;
 
-   const long nWork = (long)v.nLocalBoxes * v.chunks;
-   const long per = (nWork + gridDim.x - 1) / gridDim.x;
-   const long w0 = (long)xcdRemap(blockIdx.x, gridDim.x) * per;
-   const long w1 = w0 + per < nWork ? w0 + per : nWork;
-   for (long w = w0 + wave; w < w1; w += 4) {
+   forEachChunk(v, lane, wave, [&](int iBox, int first, int, int reps, int span, int q, int ia, bool active) {
 #define NN12_COORD(x)
-#include "nearest12_walk.h"       // the 12 nearest of the lane's atom: me, xi, yi, zi, d[], id[], active, q
+#include "nearest12_walk.h"       // the 12 nearest of the lane's atom: me, xi, yi, zi, d[], id[]
 #undef NN12_COORD
 
       if (active && q == 0) {
@@ -132,5 +124,5 @@ void Cna_thread_atom(CnaArgs v)
          asm("" : "+v"(out));
          v.type[out] = full ? type : CNA_OTHER;
       }
-   }
+   });
 }

@@ -1173,18 +1173,30 @@ extern "C" void computeEnergy(SimGpu* sim, real_t* eLocal)
    eLocal[0] = sim->pinned[0]; eLocal[1] = sim->pinned[1];
 }
 
+// The analysis entry points below (stencil_walk.h) share their prologue and the fields of the chunk walk.
+// They run on the boundary stream; -a 1: the interior cells' force work is done first
+static hipStream_t analysisStream(SimGpu* sim)
+{
+   if (sim->interior_stream) HIP_CHECK(hipStreamSynchronize(S(sim->interior_stream)));
+   return S(sim->boundary_stream);
+}
+
+static void fillStencilArgs(StencilArgs& v, const SimGpu* sim)
+{
+   v.rx = sim->atoms.r.x; v.ry = sim->atoms.r.y; v.rz = sim->atoms.r.z;
+   v.nAtoms = sim->boxes.nAtoms; v.nbr = sim->neighbor_cells;
+   v.nLocalBoxes = sim->boxes.nLocalBoxes; v.cap = sim->maxAtoms; v.chunks = ceilDiv(sim->maxAtoms, WAVE);
+}
+
 // Not in the reference: the pair virial and the kinetic tensor (virial_kernels.h), one kernel instance per pair function of the force paths
 extern "C" void computeVirial(SimGpu* sim, real_t* out12)
 {
-   hipStream_t st = S(sim->boundary_stream);
-   if (sim->interior_stream) HIP_CHECK(hipStreamSynchronize(S(sim->interior_stream)));      // -a 1: the interior cells' force work is done
+   hipStream_t st = analysisStream(sim);
    if (!sim->virialBuf) sim->virialBuf = dalloc<double>((size_t)(VIRIAL_BLOCKS + 1) * VIRIAL_N, false);
    VirialArgs v;
-   v.rx = sim->atoms.r.x; v.ry = sim->atoms.r.y; v.rz = sim->atoms.r.z;
+   fillStencilArgs(v, sim);
    v.px = sim->atoms.p.x; v.py = sim->atoms.p.y; v.pz = sim->atoms.p.z;
    v.iSpecies = sim->atoms.iSpecies; v.speciesMass = sim->species_mass;
-   v.nAtoms = sim->boxes.nAtoms; v.nbr = sim->neighbor_cells;
-   v.nLocalBoxes = sim->boxes.nLocalBoxes; v.cap = sim->maxAtoms; v.chunks = ceilDiv(sim->maxAtoms, WAVE);
    v.partial = sim->virialBuf;
    double* out = sim->virialBuf + (size_t)VIRIAL_BLOCKS * VIRIAL_N;
    const dim3 grid(VIRIAL_BLOCKS), block(256);
@@ -1220,8 +1232,7 @@ extern "C" void computeVirial(SimGpu* sim, real_t* out12)
 // Not in the reference: the pair-distance histogram (rdf_kernels.h).  One instance for every potential and method: it reads positions and cells only
 extern "C" void computePairHistogram(SimGpu* sim, int nBins, real_t rMax, uint64_t* outCounts)
 {
-   hipStream_t st = S(sim->boundary_stream);
-   if (sim->interior_stream) HIP_CHECK(hipStreamSynchronize(S(sim->interior_stream)));      // -a 1: the interior cells' force work is done
+   hipStream_t st = analysisStream(sim);
    if (nBins < 1 || nBins > PAIRHIST_MAX_BINS) { fprintf(stderr, "computePairHistogram: %d bins (1..%d)\n", nBins, PAIRHIST_MAX_BINS); exit(-1); }
    if (nBins > sim->pairHistCap) {
       if (sim->pairHistBuf) { HIP_CHECK(hipStreamSynchronize(st)); HIP_CHECK(hipFree(sim->pairHistBuf)); }
@@ -1229,9 +1240,7 @@ extern "C" void computePairHistogram(SimGpu* sim, int nBins, real_t rMax, uint64
       sim->pairHistCap = nBins;
    }
    PairHistArgs v;
-   v.rx = sim->atoms.r.x; v.ry = sim->atoms.r.y; v.rz = sim->atoms.r.z;
-   v.nAtoms = sim->boxes.nAtoms; v.nbr = sim->neighbor_cells;
-   v.nLocalBoxes = sim->boxes.nLocalBoxes; v.cap = sim->maxAtoms; v.chunks = ceilDiv(sim->maxAtoms, WAVE);
+   fillStencilArgs(v, sim);
    v.nBins = nBins; v.rMax2 = rMax * rMax; v.invDr = (real_t)nBins / rMax;
    v.counts = sim->pairHistBuf;
    const size_t lds = (size_t)4 * nBins * sizeof(unsigned);      // one copy per wave
@@ -1251,8 +1260,7 @@ extern "C" void computePairHistogram(SimGpu* sim, int nBins, real_t rMax, uint64
 // potential and method: it reads positions and cells only.  The two per-slot buffers are allocated by the first call.
 extern "C" void computeCentroSymmetry(SimGpu* sim, real_t rCoord, real_t* outCspBySlot, int* outCoordBySlot)
 {
-   hipStream_t st = S(sim->boundary_stream);
-   if (sim->interior_stream) HIP_CHECK(hipStreamSynchronize(S(sim->interior_stream)));      // -a 1: the interior cells' force work is done
+   hipStream_t st = analysisStream(sim);
    const real_t cutoff = sim->do_eam ? sim->eam_pot.cutoff : sim->lj_pot.cutoff;
    if (!(rCoord > R(0.0)) || rCoord > cutoff) { fprintf(stderr, "computeCentroSymmetry: rCoord %g outside (0, cutoff = %g]\n", (double)rCoord, (double)cutoff); exit(-1); }
    if ((double)sim->boxes.nTotalBoxes * sim->maxAtoms >= 2147483648.0) { fprintf(stderr, "computeCentroSymmetry: more than 2^31 slots\n"); exit(-1); }
@@ -1262,9 +1270,7 @@ extern "C" void computeCentroSymmetry(SimGpu* sim, real_t rCoord, real_t* outCsp
       sim->cspCoordBuf = dalloc<int>(nSlots);
    }
    CentroSymArgs v;
-   v.rx = sim->atoms.r.x; v.ry = sim->atoms.r.y; v.rz = sim->atoms.r.z;
-   v.nAtoms = sim->boxes.nAtoms; v.nbr = sim->neighbor_cells;
-   v.nLocalBoxes = sim->boxes.nLocalBoxes; v.cap = sim->maxAtoms; v.chunks = ceilDiv(sim->maxAtoms, WAVE);
+   fillStencilArgs(v, sim);
    v.rc2 = cutoff * cutoff; v.rCoord2 = rCoord * rCoord;
    v.csp = sim->cspBuf; v.coord = sim->cspCoordBuf;
    hipLaunchKernelGGL(CentroSym_thread_atom, dim3(CSP_BLOCKS), dim3(256), 0, st, v);
@@ -1278,16 +1284,13 @@ extern "C" void computeCentroSymmetry(SimGpu* sim, real_t rCoord, real_t* outCsp
 // and method, as computeCentroSymmetry, whose walk it shares.  The per-slot buffer is allocated by the first call.
 extern "C" void computeCommonNeighbors(SimGpu* sim, int* outTypeBySlot)
 {
-   hipStream_t st = S(sim->boundary_stream);
-   if (sim->interior_stream) HIP_CHECK(hipStreamSynchronize(S(sim->interior_stream)));      // -a 1: the interior cells' force work is done
+   hipStream_t st = analysisStream(sim);
    const real_t cutoff = sim->do_eam ? sim->eam_pot.cutoff : sim->lj_pot.cutoff;
    if ((double)sim->boxes.nTotalBoxes * sim->maxAtoms >= 2147483648.0) { fprintf(stderr, "computeCommonNeighbors: more than 2^31 slots\n"); exit(-1); }
    const size_t nSlots = (size_t)sim->boxes.nLocalBoxes * sim->maxAtoms;
    if (!sim->cnaBuf) sim->cnaBuf = dalloc<int>(nSlots);
    CnaArgs v;
-   v.rx = sim->atoms.r.x; v.ry = sim->atoms.r.y; v.rz = sim->atoms.r.z;
-   v.nAtoms = sim->boxes.nAtoms; v.nbr = sim->neighbor_cells;
-   v.nLocalBoxes = sim->boxes.nLocalBoxes; v.cap = sim->maxAtoms; v.chunks = ceilDiv(sim->maxAtoms, WAVE);
+   fillStencilArgs(v, sim);
    v.rc2 = cutoff * cutoff;
    v.type = sim->cnaBuf;
    hipLaunchKernelGGL(Cna_thread_atom, dim3(CNA_BLOCKS), dim3(256), 0, st, v);

@@ -8,9 +8,7 @@
 // A tie between the 12th and the 13th nearest distance goes to the neighbour met first in walk order (stencil cell by stencil cell, slot by
 // slot; with a replicated chunk, see below, the copy with the lower number wins).
 //
-// Mapping: the one of PairHist_thread_atom (rdf_kernels.h), whose header also says why the 27-cell walk sees every pair within the cutoff when
-// the cells are sized for cutoff + skin and not re-binned.  One wave = one 64-slot chunk of a local cell, lane = atom i, the candidates j
-// wave-uniform through the scalar load stream, 8 per batch.
+// Mapping: the chunk walk of stencil_walk.h, which also says why 27 cells are enough for the cells of the *_nl methods and of -L.
 //
 // The 12 nearest: every lane keeps {r^2, slot} of its 12 best candidates sorted by r^2 in registers.  A candidate closer than the lane's 12th
 // (which starts at cutoff^2, so this is the cutoff test too) is carried through the 12 positions with compare / select at compile-time indices: it
@@ -20,7 +18,7 @@
 // cells hold shifted images, so r_j - r_i is the offset vector as it stands, without a minimum image.
 //
 // Small chunks: a chunk of at most 32 atoms -- every EAM cell, LJ at 2.5 sigma, the tail chunk of an LJ cell -- would use 10 to 50 % of the lanes.  It
-// is replicated as PairHist does it: reps copies of its atoms, copy q walks the stencil cells q, q + reps, ... with per-lane loads, and the
+// is replicated (stencil_walk.h): reps copies of its atoms, copy q walks the stencil cells q, q + reps, ... with per-lane loads, and the
 // partial sets are merged by a butterfly over the copies (each lane reads the 12 entries of the lane `span` away through ds_bpermute and offers
 // them to its own set; the coordination counts add).  Packing several cells into a wave instead would keep the loads scalar only for the lanes of one
 // cell at a time and needs a per-lane cell table; replication reuses the walk the histogram and the virial already have, and the merge costs
@@ -29,21 +27,17 @@
 // X[a], X[b] at run time (scratch), and predicating shares on compile-time indices leaves every lane issuing all 66 anyway.  Measured at 80^3 the EAM
 // kernel takes 4.3 ms against 10.2 ms for LJ 5 sigma: this stage and the merge are what does not shrink with the candidates.
 //
-// The walk and the merge are the text of nearest12_walk.h, which Cna_thread_atom (cna_kernels.h) includes too; the 66-pair stage is this kernel's own.
+// The selection and the merge are the text of nearest12_walk.h, which Cna_thread_atom (cna_kernels.h) includes too; the 66-pair stage is this kernel's own.
 //
 // The kernel reads r, nAtoms and nbr and writes nothing but its own two per-slot buffers; no atomics: bit-reproducible.
 #pragma once
-#include "device_common.h"
+#include "stencil_walk.h"
 
 #define CSP_BLOCKS 2048
 #define CSP_NN 12                      // neighbours of the parameter: the first FCC shell
 
-struct CentroSymArgs {
-   const real_t* __restrict__ rx; const real_t* __restrict__ ry; const real_t* __restrict__ rz;
-   const int* __restrict__ nAtoms;
-   const int* __restrict__ nbr;        // [nLocal*27], self first
-   int nLocalBoxes, cap, chunks;       // chunks = 64-slot chunks per cell
-   real_t rc2, rCoord2;                // cutoff^2, rCoord^2
+struct CentroSymArgs : StencilArgs {
+   real_t rc2, rCoord2;               // cutoff^2, rCoord^2
    real_t* __restrict__ csp;           // [nLocalBoxes*cap]
    int* __restrict__ coord;            // [nLocalBoxes*cap]
 };
@@ -79,13 +73,9 @@ void CentroSym_thread_atom(CentroSymArgs v)
    const int lane = laneId(), wave = (int)threadIdx.x >> 6;
    const real_t inf = R(__builtin_huge_val());
 
-   const long nWork = (long)v.nLocalBoxes * v.chunks;
-   const long per = (nWork + gridDim.x - 1) / gridDim.x;
-   const long w0 = (long)xcdRemap(blockIdx.x, gridDim.x) * per;
-   const long w1 = w0 + per < nWork ? w0 + per : nWork;
-   for (long w = w0 + wave; w < w1; w += 4) {
+   forEachChunk(v, lane, wave, [&](int iBox, int first, int, int reps, int span, int q, int ia, bool active) {
 #define NN12_COORD(x) x
-#include "nearest12_walk.h"       // the 12 nearest of the lane's atom: me, xi, yi, zi, d[], id[], coord, active, q
+#include "nearest12_walk.h"       // the 12 nearest of the lane's atom: me, xi, yi, zi, d[], id[], coord
 #undef NN12_COORD
 
       if (active && q == 0) {
@@ -110,5 +100,5 @@ void CentroSym_thread_atom(CentroSymArgs v)
          v.csp[me] = full ? sum : inf;
          v.coord[me] = coord;
       }
-   }
+   });
 }

@@ -1,26 +1,15 @@
-// nearest12_walk.h -- the "12 nearest neighbours of a lane's atom" walk and merge that CentroSym_thread_atom (csp_kernels.h, which describes it) and
-// Cna_thread_atom (cna_kernels.h) share.  NOT a header of declarations: it is the text of the walk, included inside the kernel's loop over its units of
-// work, so that both kernels compile the very statements the csp kernel had in its own body.  (As a __forceinline__ function taking the sets by reference
-// the same statements cost CentroSym_thread_atom its allocation in the double build: 128 VGPRs and 104 to 1624 bytes of scratch instead of 124 and 0.)
+// nearest12_walk.h -- the "12 nearest neighbours of a lane's atom" selection and merge that CentroSym_thread_atom (csp_kernels.h, which describes it) and
+// Cna_thread_atom (cna_kernels.h) share, on the chunk walk of stencil_walk.h.  NOT a header of declarations: it is text, included inside the body the
+// kernel hands to forEachChunk, so that both kernels compile the very statements the csp kernel had in its own body.  (As a __forceinline__ function
+// taking the sets by reference, or handing them to a stage lambda, the same statements cost CentroSym_thread_atom its allocation in the double build:
+// 128 VGPRs and 20 to 1624 bytes of scratch instead of 124 and 0.)
 //
 // In scope at the point of inclusion:
-//   v                  the kernel's argument record with rx, ry, rz, nAtoms, nbr, cap, chunks, rc2 (and rCoord2 when NN12_COORD keeps its argument)
-//   w, lane            the unit of work, cell * v.chunks + chunk, and the lane
+//   v                  the kernel's argument record: StencilArgs with rc2 (and rCoord2 when NN12_COORD keeps its argument)
+//   iBox, first, reps, span, q, ia, active, lane        the values forEachChunk hands to the body, and the lane
 //   NN12_COORD(x)      a macro: x for a kernel that counts the coordination number, nothing otherwise
-// It `continue`s on an empty chunk.  After it: me = the lane's slot, xi, yi, zi its position, d[] / id[] = r^2 and slot of the 12 nearest in ascending
-// order (id[11] < 0: fewer than 12 inside the cutoff), coord (with NN12_COORD), and active && q == 0 = the lane holds an atom and is the copy of a
-// replicated chunk that writes the result.
-      const int iBox = uniform((int)(w / v.chunks));
-      const int first = uniform((int)(w - (long)iBox * v.chunks)) * WAVE;
-      const int ni = uniform(v.nAtoms[iBox]);
-      if (first >= ni) continue;
-      // a chunk of m <= 32 atoms is replicated: reps copies of its atoms, copy q walks the stencil cells q, q + reps, ... (as PairHist_thread_atom)
-      const int m = ni - first < WAVE ? ni - first : WAVE;
-      int reps = 1;
-      while (reps < 16 && 2 * reps * m <= WAVE) reps *= 2;
-      const int span = WAVE / reps, q = lane / span;
-      const int ia = first + (lane & (span - 1));
-      const bool active = ia < first + m;
+// After it: me = the lane's slot, xi, yi, zi its position, d[] / id[] = r^2 and slot of the 12 nearest in ascending order (id[11] < 0: fewer than 12
+// inside the cutoff), coord (with NN12_COORD), and active && q == 0 = the lane holds an atom and is the copy of a replicated chunk that writes the result.
       const int me = iBox * v.cap + (active ? ia : first);
       const real_t xi = v.rx[me], yi = v.ry[me], zi = v.rz[me];
 
@@ -40,14 +29,8 @@
          NN12_COORD(coord += (other && r2 < v.rCoord2) ? 1 : 0;)
          if (other && r2 < d[CSP_NN - 1]) cspOffer<CSP_NN>(d, id, r2, slot);
       };
-      const int* __restrict__ nb = v.nbr + (size_t)iBox * 27;
+      stencilWalk<int>(v, iBox, reps, q, test);
       if (reps > 1) {
-         for (int k = q; k < 27; k += reps) {
-            const int jBox = nb[k];
-            const int nj = v.nAtoms[jBox];
-            const int base = jBox * v.cap;
-            for (int j = 0; j < nj; ++j) test(v.rx[base + j], v.ry[base + j], v.rz[base + j], base + j);
-         }
          // the copies' sets into one: after the doubling over s every lane holds the 12 nearest of the copies lane ^ s, lane ^ 2s, ... as well
          for (int s = span; s < WAVE; s <<= 1) {
             const int addr = (lane ^ s) << 2;
@@ -68,20 +51,4 @@
             for (int k = 0; k < CSP_NN; ++k)
                if (pi[k] >= 0 && pd[k] < d[CSP_NN - 1]) cspOffer<CSP_NN>(d, id, pd[k], pi[k]);
          }
-      } else for (int k = 0; k < 27; ++k) {
-         const int jBox = uniform(nb[k]);
-         const int nj = uniform(v.nAtoms[jBox]);
-         const int base = jBox * v.cap;
-         const real_t* __restrict__ qx = v.rx + base;
-         const real_t* __restrict__ qy = v.ry + base;
-         const real_t* __restrict__ qz = v.rz + base;
-         int j = 0;
-         for (; j + 8 <= nj; j += 8) {
-            real_t xs[8], ys[8], zs[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { xs[u] = qx[j + u]; ys[u] = qy[j + u]; zs[u] = qz[j + u]; }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) test(xs[u], ys[u], zs[u], base + j + u);
-         }
-         for (; j < nj; ++j) test(qx[j], qy[j], qz[j], base + j);
       }

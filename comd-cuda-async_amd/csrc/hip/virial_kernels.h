@@ -7,20 +7,14 @@
 //   LJ:  f_ij = ljPair's f_pair (x 24 eps s6 once per lane) or ljTablePair's -v'(r)/r d
 //   EAM: f_ij = -(phi'(r) + (F'_i + F'_j) rho'(r)) / r d, F'_j read from dfEmbed, whose halo slots the force exchange has filled.
 //
-// Mapping: the shape of LJ_Force_thread_atom.  One wave = one 64-slot chunk of a local cell (a cell of more than 64 slots takes several
-// chunks), lane = i atom, the 27-cell stencil walked with the neighbour j wave-uniform (its position and F'_j through the scalar unit).
-// A chunk of at most 32 atoms -- every EAM cell, the tail chunk of an LJ cell -- is replicated across the lanes, each copy walking a share
-// of the stencil cells, as the tail wave of LJ_Force_thread_atom is.
-// Only local atoms are i, j runs over local and halo slots, so every pair is seen from both sides and weighs 1/2.
-// The link cells of the *_nl methods and of -L are sized for cutoff + skin and are not re-binned between list builds: an atom has moved
-// less than skin/2 since, so two atoms within the plain cutoff now were within cutoff + skin of each other when the cells were filled, i.e.
-// in neighbouring cells.  The 27-cell walk with the plain cutoff therefore finds every pair the lists hold.
+// Mapping: the chunk walk of stencil_walk.h, which also says why 27 cells are enough for the cells of the *_nl methods and of -L.  A full chunk
+// reads F'_j through the scalar unit with the position of j.  Every pair is seen from both sides and weighs 1/2.
 //
 // Reduction: each lane accumulates its 6 + 6 components in real_t, the workgroup sums them in double in a fixed order and writes one row of 12
 // partials; Virial_Final adds the rows in a fixed order (no atomics: runs are bit-reproducible).  The kernels read r, p, dfEmbed and the cell
 // tables and write nothing but their partial rows.
 #pragma once
-#include "device_common.h"
+#include "stencil_walk.h"
 #include "lj_kernels.h"
 #include "lj_table_kernels.h"
 #include "eam_kernels.h"
@@ -28,13 +22,9 @@
 #define VIRIAL_N 12                    // 6 virial + 6 kinetic components
 #define VIRIAL_BLOCKS 2048             // rows of partials: fixed, so the order of the sums does not depend on the system
 
-struct VirialArgs {
-   const real_t* __restrict__ rx; const real_t* __restrict__ ry; const real_t* __restrict__ rz;
+struct VirialArgs : StencilArgs {
    const real_t* __restrict__ px; const real_t* __restrict__ py; const real_t* __restrict__ pz;
    const int* __restrict__ iSpecies; const real_t* __restrict__ speciesMass;
-   const int* __restrict__ nAtoms;
-   const int* __restrict__ nbr;        // [nLocal*27], self first
-   int nLocalBoxes, cap, chunks;       // chunks = 64-slot chunks per cell
    real_t rc2;
    double* __restrict__ partial;       // [gridDim.x][VIRIAL_N]
 };
@@ -107,24 +97,7 @@ void Virial_thread_atom(VirialArgs v, PAIR pair)
 #pragma unroll
    for (int c = 0; c < VIRIAL_N; ++c) acc[c] = R(0.0);
 
-   // each workgroup takes a contiguous run of chunks (neighbouring cells share stencil cells), dealt XCD-contiguously; its waves interleave
-   const long nWork = (long)v.nLocalBoxes * v.chunks;
-   const long per = (nWork + gridDim.x - 1) / gridDim.x;
-   const long w0 = (long)xcdRemap(blockIdx.x, gridDim.x) * per;
-   const long w1 = w0 + per < nWork ? w0 + per : nWork;
-   for (long w = w0 + wave; w < w1; w += 4) {
-      const int iBox = uniform((int)(w / v.chunks));
-      const int first = uniform((int)(w - (long)iBox * v.chunks)) * WAVE;
-      const int ni = uniform(v.nAtoms[iBox]);
-      if (first >= ni) continue;
-      // a chunk of m <= 32 atoms (EAM cells, the tail chunk of an LJ cell) is replicated: reps copies of its atoms, copy q walks the stencil
-      // cells q, q + reps, ... (the neighbour then differs between copies: vector loads instead of the scalar stream of a full chunk)
-      const int m = ni - first < WAVE ? ni - first : WAVE;
-      int reps = 1;
-      while (reps < 16 && 2 * reps * m <= WAVE) reps *= 2;
-      const int span = WAVE / reps, q = lane / span;
-      const int ia = first + (lane & (span - 1));
-      const bool active = ia < first + m;
+   forEachChunk(v, lane, wave, [&](int iBox, int first, int, int reps, int, int q, int ia, bool active) {
       const size_t iOff = (size_t)iBox * v.cap + (active ? ia : first);
       const real_t xi = v.rx[iOff], yi = v.ry[iOff], zi = v.rz[iOff];
       pair.begin(iOff);
@@ -139,32 +112,7 @@ void Virial_thread_atom(VirialArgs v, PAIR pair)
             wyz = fmaR(dy, gz, wyz); wxz = fmaR(dx, gz, wxz); wxy = fmaR(dx, gy, wxy);
          }
       };
-      const int* __restrict__ nb = v.nbr + (size_t)iBox * 27;
-      if (reps > 1) {
-         for (int k = q; k < 27; k += reps) {
-            const int jBox = nb[k];
-            const int nj = v.nAtoms[jBox];
-            const size_t base = (size_t)jBox * v.cap;
-            for (int j = 0; j < nj; ++j) test(v.rx[base + j], v.ry[base + j], v.rz[base + j], base + j);
-         }
-      } else for (int k = 0; k < 27; ++k) {
-         const int jBox = uniform(nb[k]);
-         const int nj = uniform(v.nAtoms[jBox]);
-         const size_t base = (size_t)jBox * v.cap;
-         const real_t* __restrict__ qx = v.rx + base;
-         const real_t* __restrict__ qy = v.ry + base;
-         const real_t* __restrict__ qz = v.rz + base;
-         // as ljCellLoop: 8 wave-uniform neighbours per batch of scalar loads, then their tests
-         int j = 0;
-         for (; j + 8 <= nj; j += 8) {
-            real_t xs[8], ys[8], zs[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { xs[u] = qx[j + u]; ys[u] = qy[j + u]; zs[u] = qz[j + u]; }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) test(xs[u], ys[u], zs[u], base + j + u);
-         }
-         for (; j < nj; ++j) test(qx[j], qy[j], qz[j], base + j);
-      }
+      stencilWalk<size_t>(v, iBox, reps, q, test);
       if (active) {
          const real_t h = R(0.5) * pair.scale();
          acc[0] = fmaR(h, wxx, acc[0]); acc[1] = fmaR(h, wyy, acc[1]); acc[2] = fmaR(h, wzz, acc[2]);
@@ -176,7 +124,7 @@ void Virial_thread_atom(VirialArgs v, PAIR pair)
          acc[6] = fmaR(qx * qx, invMass, acc[6]); acc[7] = fmaR(qy * qy, invMass, acc[7]); acc[8] = fmaR(qz * qz, invMass, acc[8]);
          acc[9] = fmaR(qy * qz, invMass, acc[9]); acc[10] = fmaR(qx * qz, invMass, acc[10]); acc[11] = fmaR(qx * qy, invMass, acc[11]);
       }
-   }
+   });
 #pragma unroll
    for (int c = 0; c < VIRIAL_N; ++c) {
       const double s = waveSumD((double)acc[c]);

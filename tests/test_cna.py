@@ -19,13 +19,14 @@ and an atom with margin < DELTA is left out.  DELTAs and caps are those of test_
 import json
 import os
 import re
-import shutil
 import subprocess
 import sys
 import textwrap
 
 import numpy as np
 import pytest
+
+import device_isa
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -261,19 +262,13 @@ def test_common_neighbors_is_exported_and_declared(sfx):
 
 
 @pytest.mark.parametrize("precision", ["double", "single"])
-def test_cna_kernels_use_no_scratch(tmp_path, precision):
-    if shutil.which("hipcc") is None:
-        pytest.fail("hipcc not on PATH")
-    src = os.path.join(CSRC, "hip", "comd_device.hip")
-    out = tmp_path / "dev.s"
-    proc = subprocess.run(["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-Wno-comment", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.dirname(src), "-S", "--cuda-device-only", "-o", str(out), src]
-                          + (["-DCOMD_SINGLE"] if precision == "single" else []), capture_output=True, text=True)
-    assert proc.returncode == 0, proc.stderr[-2000:]
-    blocks = dict(re.findall(r"^\s*\.amdhsa_kernel (_Z\d+Cna_\w+)\n(.*?)\.end_amdhsa_kernel", out.read_text(), flags=re.S | re.M))
+def test_cna_kernels_use_no_scratch(precision):
+    """... and Cna_thread_atom keeps the registers of its 4 waves per SIMD"""
+    blocks = device_isa.blocks(precision, r"Cna_\w+")
     assert len(blocks) >= 1 and any("Cna_thread_atom" in n for n in blocks), sorted(blocks)
     for name, block in blocks.items():
         assert re.search(r"\.amdhsa_private_segment_fixed_size 0\n", block), name
+    device_isa.assert_keeps_waves(blocks, "Cna_thread_atom", 4)
 
 
 def test_host_only_simulation_refuses(pkg):

@@ -10,13 +10,14 @@ state; the executable writes the stress-strain file.  Tolerances are those of te
 import json
 import os
 import re
-import shutil
 import socket
 import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+import device_isa
 
 from test_pressure import (ADAMS, CSRC, GPA, HERE, MISHIN, RC, ROOT, SIGMA, EPS, SINGLE, TOL, _child, _interpolate, _pairs, _rel)
 
@@ -155,16 +156,8 @@ def test_two_host_only_ranks_agree_on_their_shared_face(single_rank):
 
 
 @pytest.mark.parametrize("precision", ["double", "single"])
-def test_remap_kernel_exists_and_uses_no_scratch(tmp_path, precision):
-    if shutil.which("hipcc") is None:
-        pytest.fail("hipcc not on PATH")
-    src = os.path.join(CSRC, "hip", "comd_device.hip")
-    out = tmp_path / "dev.s"
-    proc = subprocess.run(["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-Wno-comment", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.dirname(src), "-S", "--cuda-device-only", "-o", str(out), src]
-                          + (["-DCOMD_SINGLE"] if precision == "single" else []), capture_output=True, text=True)
-    assert proc.returncode == 0, proc.stderr[-2000:]
-    blocks = dict(re.findall(r"^\s*\.amdhsa_kernel (_Z\d+RemapBox\w+)\n(.*?)\.end_amdhsa_kernel", out.read_text(), flags=re.S | re.M))
+def test_remap_kernel_exists_and_uses_no_scratch(precision):
+    blocks = device_isa.blocks(precision, r"RemapBox\w+")
     assert len(blocks) == 1, sorted(blocks)
     for name, block in blocks.items():
         assert re.search(r"\.amdhsa_private_segment_fixed_size 0\n", block), name

@@ -15,6 +15,8 @@ import textwrap
 import numpy as np
 import pytest
 
+import device_isa
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(ROOT, "comd-cuda-async_amd", "csrc")
@@ -193,17 +195,8 @@ def test_langevin_entries_are_exported_and_declared(sfx):
 
 
 @pytest.mark.parametrize("precision", ["double", "single"])
-def test_langevin_kernels_use_no_scratch(tmp_path, precision):
-    if shutil.which("hipcc") is None:
-        pytest.fail("hipcc not on PATH")
-    src = os.path.join(CSRC, "hip", "comd_device.hip")
-    out = tmp_path / "dev.s"
-    proc = subprocess.run(["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-Wno-comment", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.dirname(src), "-S", "--cuda-device-only", "-o", str(out), src]
-                          + (["-DCOMD_SINGLE"] if precision == "single" else []), capture_output=True, text=True)
-    assert proc.returncode == 0, proc.stderr[-2000:]
-    blocks = dict(re.findall(r"^\s*\.amdhsa_kernel (_Z\d+AdvanceVelocity\w*Langevin\w*)\n(.*?)\.end_amdhsa_kernel", out.read_text(),
-                             flags=re.S | re.M))
+def test_langevin_kernels_use_no_scratch(precision):
+    blocks = device_isa.blocks(precision, r"AdvanceVelocity\w*Langevin\w*")
     assert len(blocks) == 2 and any("VelocityVelocity" in n for n in blocks), sorted(blocks)
     for name, block in blocks.items():
         assert re.search(r"\.amdhsa_private_segment_fixed_size 0\n", block), name

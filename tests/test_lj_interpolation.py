@@ -10,7 +10,6 @@ import json
 import math
 import os
 import re
-import shutil
 import subprocess
 import sys
 import textwrap
@@ -135,15 +134,9 @@ def test_no_table_without_the_flag(pkg):
 
 
 @pytest.fixture(scope="module")
-def device_isa(tmp_path_factory):
-    if shutil.which("hipcc") is None:
-        pytest.fail("hipcc not on PATH")
-    src = os.path.join(CSRC, "hip", "comd_device.hip")
-    out = tmp_path_factory.mktemp("isa") / "dev.s"
-    proc = subprocess.run(["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-Wno-comment", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.dirname(src), "-S", "--cuda-device-only", "-o", str(out), src], capture_output=True, text=True)
-    assert proc.returncode == 0, proc.stderr[-2000:]
-    return out.read_text()
+def device_isa():
+    import device_isa as isa
+    return isa.assembly("double")
 
 
 def test_table_kernel_keeps_the_scalar_load_stream(device_isa):

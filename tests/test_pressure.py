@@ -12,13 +12,14 @@ Tensors are compared component by component against the largest component of the
 import json
 import os
 import re
-import shutil
 import subprocess
 import sys
 import textwrap
 
 import numpy as np
 import pytest
+
+import device_isa
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -32,6 +33,9 @@ MISHIN = ["-e", "-t", "setfl", "-p", "Cu01.eam.alloy"]
 ADAMS = ["-e"]
 RC = {"lj5": 5.0 * SIGMA, "lj2.5": 2.5 * SIGMA, "adams": 4.95, "mishin": 5.50679}
 POT = {"lj5": [], "lj2.5": ["--ljCutoffSigmas", 2.5], "adams": ADAMS, "mishin": MISHIN}
+# waves per SIMD of the instances of Virial_thread_atom, by the mangled name of the pair functor (VirialEam<false>: the quadratic tables)
+VIRIAL_WAVES = {"double": {"8VirialLj": 6, "13VirialLjTable": 5, "9VirialEamILb1EE": 5, "9VirialEamILb0EE": 4},
+                "single": {"8VirialLj": 8, "13VirialLjTable": 7, "9VirialEamILb1EE": 7, "9VirialEamILb0EE": 7}}
 
 
 def _cube(n):
@@ -88,17 +92,10 @@ def test_compute_virial_is_exported_and_declared(sfx):
 
 
 @pytest.mark.parametrize("precision", ["double", "single"])
-def test_virial_kernels_use_no_scratch(tmp_path, precision):
-    """Every pair function has its instance (LJ analytic, LJ table, EAM quadratic tables, EAM splines), none spills to scratch."""
-    if shutil.which("hipcc") is None:
-        pytest.fail("hipcc not on PATH")
-    src = os.path.join(CSRC, "hip", "comd_device.hip")
-    out = tmp_path / "dev.s"
-    proc = subprocess.run(["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-Wno-comment", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.dirname(src), "-S", "--cuda-device-only", "-o", str(out), src]
-                          + (["-DCOMD_SINGLE"] if precision == "single" else []), capture_output=True, text=True)
-    assert proc.returncode == 0, proc.stderr[-2000:]
-    blocks = dict(re.findall(r"^\s*\.amdhsa_kernel (_Z\d+Virial_\w+)\n(.*?)\.end_amdhsa_kernel", out.read_text(), flags=re.S | re.M))
+def test_virial_kernels_use_no_scratch(precision):
+    """Every pair function has its instance (LJ analytic, LJ table, EAM quadratic tables, EAM splines), none spills to scratch, and each keeps
+    the registers of its waves per SIMD."""
+    blocks = device_isa.blocks(precision, r"Virial_\w+")
     names = sorted(blocks)
     assert len(names) == 5, names
     for pair in ("VirialLj", "VirialLjTable", "VirialEamILb0E", "VirialEamILb1E"):
@@ -106,6 +103,8 @@ def test_virial_kernels_use_no_scratch(tmp_path, precision):
     assert any("Virial_Final" in n for n in names)
     for name, block in blocks.items():
         assert re.search(r"\.amdhsa_private_segment_fixed_size 0\n", block), name
+    for pair, waves in VIRIAL_WAVES[precision].items():
+        device_isa.assert_keeps_waves(blocks, f"Virial_thread_atomI{pair}Ev", waves)
 
 
 # ---------------------------------------------------------------- numpy restatement

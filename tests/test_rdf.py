@@ -13,13 +13,14 @@ that edge -- and the sum of near[] is itself capped, so that a loose input fails
 import json
 import os
 import re
-import shutil
 import subprocess
 import sys
 import textwrap
 
 import numpy as np
 import pytest
+
+import device_isa
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -65,19 +66,13 @@ def test_pair_histogram_is_exported_and_declared(sfx):
 
 
 @pytest.mark.parametrize("precision", ["double", "single"])
-def test_pair_histogram_kernels_use_no_scratch(tmp_path, precision):
-    if shutil.which("hipcc") is None:
-        pytest.fail("hipcc not on PATH")
-    src = os.path.join(CSRC, "hip", "comd_device.hip")
-    out = tmp_path / "dev.s"
-    proc = subprocess.run(["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-Wno-comment", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.dirname(src), "-S", "--cuda-device-only", "-o", str(out), src]
-                          + (["-DCOMD_SINGLE"] if precision == "single" else []), capture_output=True, text=True)
-    assert proc.returncode == 0, proc.stderr[-2000:]
-    blocks = dict(re.findall(r"^\s*\.amdhsa_kernel (_Z\d+PairHist_\w+)\n(.*?)\.end_amdhsa_kernel", out.read_text(), flags=re.S | re.M))
+def test_pair_histogram_kernels_use_no_scratch(precision):
+    """... and PairHist_thread_atom keeps the registers of its 7 (double) or 8 (single) waves per SIMD"""
+    blocks = device_isa.blocks(precision, r"PairHist_\w+")
     assert len(blocks) >= 1 and any("PairHist_thread_atom" in n for n in blocks), sorted(blocks)
     for name, block in blocks.items():
         assert re.search(r"\.amdhsa_private_segment_fixed_size 0\n", block), name
+    device_isa.assert_keeps_waves(blocks, "PairHist_thread_atom", {"double": 7, "single": 8}[precision])
 
 
 def test_halved_counts_keep_every_pair(pkg):
