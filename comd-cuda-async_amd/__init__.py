@@ -382,6 +382,13 @@ class Simulation:
         return {"lj_candidate_lists_active": bool(a[0]), "eam_brick_image_records": a[1], "neighbor_list_format": a[2], "eam_brick_cells": a[3] & 255, "eam_brick_lists_made": a[3] >> 8,
                 "eam_bricks_in_thread_per_atom_fallback": b[0], "eam_bricks_per_launch": b[1]}
 
+    def overlap_cell_counts(self):
+        """The cell lists the overlap mode (-a 1) launches over, as the host built them for this grid: {"boundary" (local cells within two rings of the
+        surface), "interior" (the other local cells), "boundary_ring1" (local cells that touch the halo)}.  Host state; launches nothing."""
+        out = (ctypes.c_int * 3)()
+        lib_hip().comdOverlapCellCounts(ctypes.c_void_p(self.lib.comdSimGpu(self.ptr)), out)
+        return {"boundary": out[0], "interior": out[1], "boundary_ring1": out[2]}
+
     _LJ_CTA_FORMS = {0: None, 1: "boxes", 2: "slabs", 3: "pairlist"}
     _EAM_KERNELS = {0: None, 1: "brick", 2: "atom_brick", 3: "cta_cell_round2", 4: "listed_rows", 5: "nl_lds", 6: "thread_atom_round2", 7: "nl_global"}
     _EAM_COVERS = {0: "all_cells", 1: "whole_bricks", 2: "cell_by_cell"}

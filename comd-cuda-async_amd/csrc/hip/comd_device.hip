@@ -960,6 +960,11 @@ extern "C" void comdForcePathInfo(SimGpu* sim, int out[4])
    out[3] = (sim->eam_pot.brickBy ? sim->eam_pot.brickBy * sim->eam_pot.brickBz : sim->eam_pot.atomBrickBy * sim->eam_pot.atomBrickBz) + 256 * sim->eam_pot.brickListMakes;      // (cells per brick in the low byte, times the brick lists were made above)
 }
 
+extern "C" void comdOverlapCellCounts(SimGpu* sim, int out[3])
+{
+   out[0] = sim->n_boundary_cells; out[1] = sim->n_interior_cells; out[2] = sim->n_boundary1_cells;
+}
+
 // what the last force evaluation ran (comd_hip.h has the entries): host records of the launch wrappers, and counts taken from waveCandCount / brickStats as they stand
 extern "C" void comdForceLegReport(SimGpu* sim, int out[COMD_LEG_REPORT_N])
 {

@@ -379,6 +379,9 @@ void comdEamBrickResize(SimGpu* sim);
 /* what the force wrappers decided for this simulation: {LJ thread_atom candidate lists in use (0: the plain 27-cell walk -- lists did not fit the device memory),
  * records of the EAM brick image, Verlet-list format (NeighborListGpu.slabFormat), cells per EAM brick + 256 x the times the brick lists of the list method were made} */
 void comdForcePathInfo(SimGpu* sim, int out[4]);
+/* the cell lists of the overlap mode (-a 1) as SetBoundaryCells received them: {boundary cells (both rings), interior cells, ring-1 cells}.  Host state: reads
+ * nothing from the device, launches nothing. */
+void comdOverlapCellCounts(SimGpu* sim, int out[3]);
 /* What the LAST force evaluation of this simulation ran, for tests that must know a forced leg was taken: written down by the launch wrappers as they launch (host
  * state) and counted from the small device arrays they fill anyway.  Waits for the device, launches nothing, clears nothing.  out[] (unused entries are 0):
  *  [0] LJ thread_atom: waves per cell of the launch   [1] entries a candidate row holds   [2] candidate lists used by the launch (0: the 27-cell walk)

@@ -32,7 +32,7 @@ What runs between a raise and the host's read, and why it is safe (read before t
     brick build (kA < b.rows) test every entry they write and store counts clamped to the row; the force kernels loop over those counts.
 
 Out of scope: the row limit of the EAM cta_cell kernel (status[3] bit 1, the compare in EAM_Force_cta_cell: not user-settable, and reached only at a density no
-state here has), 2-cell axes, multi-rank runs.
+state here has), capacities on 2-cell axes (the force, list and analysis paths on such boxes, at default capacities, are tests/test_two_cell_boxes.py), multi-rank runs.
 """
 import json
 import os

@@ -24,7 +24,8 @@ TOL = G["tolerances_single" if SINGLE else "tolerances"]
 TOL_SPLINE = G["tolerances_single_spline"] if SINGLE else TOL      # -P in float: the float checker is itself further from the double one (see the block's _about)
 
 SETFL = ["-t", "setfl", "-p", "Cu01.eam.alloy"]
-# Shapes: no 2-cell axis, interior cells under -a 1.  Occupancies from the checker (after 3 steps):
+# Shapes: no 2-cell axis, interior cells under -a 1 (tests/test_two_cell_boxes.py runs every leg of this table again on boxes of two cells along an axis).  Occupancies
+# from the checker (after 3 steps):
 BOXES = {
     "lj":      dict(n=(10, 10, 11), delta=0.15, eam=0, flags=[], oracle={}),                                          # 3 x 3 x 3 cells of 126-196 atoms, 4400 atoms
     "eam":     dict(n=(8, 7, 9), delta=0.1, eam=1, flags=[], oracle={}),                                               # 5 x 5 x 6 cells of 9-18 atoms, 2016 atoms, 42-45 neighbours

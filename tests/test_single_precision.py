@@ -16,6 +16,7 @@ import pytest
 
 from test_capacities import GPU_CASE_COUNT
 from test_kernel_legs import FAMILY_LEG_COUNT
+from test_two_cell_boxes import GPU_CASE_COUNT as TWO_CELL_GPU_CASE_COUNT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "comd-cuda-async_amd", "csrc")
@@ -82,6 +83,16 @@ def test_single_precision_capacities():
     out = _run(["tests/test_capacities.py"], None, "gpu", 600)
     passed = re.search(r"(\d+) passed", out)
     assert passed and int(passed.group(1)) == GPU_CASE_COUNT and "skipped" not in out and "failed" not in out, out[-1500:]
+
+
+@pytest.mark.gpu
+def test_single_precision_two_cell_boxes():
+    """tests/test_two_cell_boxes.py in the float build: every method, the forced legs, the lists over rebuilds, redistribution, the analyses and the multi-rank runs on
+    boxes with two link cells along an axis.  Its CPU tests assert the states' figures on the float checker first; none skipped."""
+    _run(["tests/test_two_cell_boxes.py"], None, "not gpu", 300)
+    out = _run(["tests/test_two_cell_boxes.py"], None, "gpu", 900)
+    passed = re.search(r"(\d+) passed", out)
+    assert passed and int(passed.group(1)) == TWO_CELL_GPU_CASE_COUNT and "skipped" not in out and "failed" not in out, out[-1500:]
 
 
 SPLINE_CASE = r"""
