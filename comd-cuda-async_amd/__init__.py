@@ -29,6 +29,8 @@ c_real_p = ctypes.POINTER(c_real)
 
 # structure types of Simulation.common_neighbor_analysis(): OVITO's numbers (3, BCC, is never returned)
 CNA_OTHER, CNA_FCC, CNA_HCP, CNA_ICO = 0, 1, 2, 4
+# GPa per eV/A^3: the unit of Simulation.pressure(), atomic_pressure(), von_mises() and stress_summary() into the one comd-hip prints
+GPA_PER_EV_A3 = 160.21766208
 
 
 class HostAtoms(ctypes.Structure):
@@ -144,6 +146,10 @@ def lib_host():
         lib.comdCentroSymmetry.restype = ctypes.c_int
         lib.comdCommonNeighbors.argtypes = [vp, c_int_p, ctypes.POINTER(ctypes.c_longlong)]
         lib.comdCommonNeighbors.restype = ctypes.c_int
+        lib.comdAtomStress.argtypes = [vp, ctypes.c_int, c_double_p]
+        lib.comdAtomStress.restype = ctypes.c_int
+        lib.comdStressSummary.argtypes = [vp, ctypes.c_int, c_double_p]
+        lib.comdStressSummary.restype = ctypes.c_int
         lib.comdDefaultCoordRadius.argtypes = [vp]
         lib.comdDefaultCoordRadius.restype = ctypes.c_double
         lib.comdLatticeConstant.argtypes = [vp]
@@ -525,6 +531,51 @@ class Simulation:
         """{"other", "fcc", "hcp", "ico"}: how many atoms common_neighbor_analysis() gives each type."""
         counts = self._cna("structure_counts")[1]
         return {"other": int(counts[CNA_OTHER]), "fcc": int(counts[CNA_FCC]), "hcp": int(counts[CNA_HCP]), "ico": int(counts[CNA_ICO])}
+
+    # --- per-atom stress (not in the reference: comd-hip --stress, --stressFile, --stressDump, --stressDumpMin) ---
+    @property
+    def atomic_volume(self):
+        """The uniform atomic volume V / N of the current box in Angstroms^3 (no Voronoi volumes)."""
+        return self.volume / self.n_global
+
+    def atomic_stress(self, kinetic=True):
+        """float64 (n_global, 6) keyed by gid: every atom's virial stress x volume in eV, tension positive, components xx yy zz yz xz xy,
+        s_i = -([kinetic] p_i p_i^T / m_i + 1/2 sum_j r_ij f_ij^T) over the neighbours inside the force cutoff, with the pair convention of virial():
+        the rows add up to -(K + W), or -W without the kinetic term.  Computed on the device by computeAtomStress, summed over the ranks (every
+        rank gets the global array); valid whenever virial() is."""
+        np = self._np
+        if self.host_only:
+            raise RuntimeError("atomic_stress: a host-only simulation has no device state")
+        n = self.n_global
+        out = np.zeros((max(n, 1), 6), dtype=np.float64)
+        if self.lib.comdAtomStress(self.ptr, 1 if kinetic else 0, out.ctypes.data_as(c_double_p)) != 0:
+            raise RuntimeError("atomic_stress: comdAtomStress failed")
+        return out[:n]
+
+    def atomic_pressure(self, kinetic=True):
+        """float64 (n_global,): the hydrostatic pressure -(s_xx + s_yy + s_zz) / (3 atomic_volume) of atomic_stress(), in eV/A^3 (x GPA_PER_EV_A3 = GPa)."""
+        s = self.atomic_stress(kinetic)
+        return -((s[:, 0] + s[:, 1]) + s[:, 2]) * ((1.0 / self.atomic_volume) / 3.0)
+
+    def von_mises(self, kinetic=True):
+        """float64 (n_global,): the von Mises stress sqrt(1/2 [(s_xx - s_yy)^2 + (s_yy - s_zz)^2 + (s_zz - s_xx)^2] + 3 (s_yz^2 + s_xz^2 + s_xy^2)) / atomic_volume
+        of atomic_stress(), in eV/A^3."""
+        np = self._np
+        s = self.atomic_stress(kinetic)
+        d0, d1, d2 = s[:, 0] - s[:, 1], s[:, 1] - s[:, 2], s[:, 2] - s[:, 0]
+        return np.sqrt(0.5 * ((d0 * d0 + d1 * d1) + d2 * d2) + 3.0 * ((s[:, 3] * s[:, 3] + s[:, 4] * s[:, 4]) + s[:, 5] * s[:, 5])) * (1.0 / self.atomic_volume)
+
+    def stress_summary(self, kinetic=True):
+        """{"mean_pressure", "min_pressure", "max_pressure", "mean_von_mises", "max_von_mises", "max_von_mises_gid", "n"}: the figures of atomic_pressure()
+        and von_mises() in eV/A^3, reduced on the device (computeAtomStressSummary: the per-atom planes never leave it) and over the ranks; the gid is the
+        lowest one that holds the maximum."""
+        if self.host_only:
+            raise RuntimeError("stress_summary: a host-only simulation has no device state")
+        out = (ctypes.c_double * 7)()
+        if self.lib.comdStressSummary(self.ptr, 1 if kinetic else 0, out) != 0:
+            raise RuntimeError("stress_summary: comdStressSummary failed")
+        return {"mean_pressure": out[0], "min_pressure": out[1], "max_pressure": out[2], "mean_von_mises": out[3], "max_von_mises": out[4],
+                "max_von_mises_gid": int(out[5]), "n": int(out[6])}
 
     # --- box deformation (not in the reference: comd-hip --erateX, --erateY, --erateZ, --deformStart, --deformFile) ---
     def _box6(self):

@@ -24,6 +24,7 @@
 #include "rdf_kernels.h"
 #include "csp_kernels.h"
 #include "cna_kernels.h"
+#include "stress_kernels.h"
 #include "langevin_kernels.h"
 #include "msd_kernels.h"
 #include "deform_kernels.h"
@@ -606,7 +607,7 @@ extern "C" void DestroyGpu(SimGpu* sim)
                     sim->boxes.boxIDLookUp, sim->boxes.boxIDLookUpReverse, sim->eam_pot.phiS.coefficients, sim->eam_pot.rhoS.coefficients,
                     sim->eam_pot.pairRows, sim->eam_pot.pairRowCount, sim->eam_pot.cellSel, sim->eam_pot.brickGroup, sim->eam_pot.brickList, sim->eam_pot.brickSel, sim->eam_pot.brickStats, sim->eam_pot.atomRows, sim->eam_pot.atomRowCount, sim->eam_pot.atomBrickSel,
                     sim->atoms.neighborList.brickRows, sim->atoms.neighborList.brickRowCount, sim->adapterScan, sim->lj_pot.waveCand, sim->lj_pot.waveCandCount, sim->lj_pot.packedR[0], sim->lj_pot.packedR[1], sim->lj_pot.packedF[0], sim->lj_pot.packedF[1],
-                    sim->lj_pot.lj_interpolation.values, sim->virialBuf, sim->pairHistBuf, sim->dispBuf, sim->dispSumBuf, sim->cspBuf, sim->cspCoordBuf, sim->cnaBuf };
+                    sim->lj_pot.lj_interpolation.values, sim->virialBuf, sim->pairHistBuf, sim->dispBuf, sim->dispSumBuf, sim->cspBuf, sim->cspCoordBuf, sim->cnaBuf, sim->stressBuf, sim->stressSumBuf };
    for (void* p : ptrs) if (p) HIP_CHECK(hipFree(p));
    if (sim->statusEvent) (void)hipEventDestroy((hipEvent_t)sim->statusEvent);
    if (sim->pinned) HIP_CHECK(hipHostFree(sim->pinned));
@@ -1301,6 +1302,64 @@ extern "C" void computeCommonNeighbors(SimGpu* sim, int* outTypeBySlot)
    hipLaunchKernelGGL(Cna_thread_atom, dim3(CNA_BLOCKS), dim3(256), 0, st, v);
    LAUNCH_CHECK();
    HIP_CHECK(hipMemcpyAsync(outTypeBySlot, sim->cnaBuf, nSlots * sizeof(int), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// Not in the reference: the per-atom virial stress (stress_kernels.h), one kernel instance per pair function of the force paths, as computeVirial.
+// The six planes and the rows of the summary are allocated by the first call.
+extern "C" void computeAtomStress(SimGpu* sim, int withKinetic, real_t* outBySlot6)
+{
+   hipStream_t st = analysisStream(sim);
+   const size_t nSlots = (size_t)sim->boxes.nLocalBoxes * sim->maxAtoms;
+   if (!sim->stressBuf) {
+      sim->stressBuf = dalloc<real_t>(6 * nSlots);
+      sim->stressSumBuf = dalloc<double>((size_t)(ATOMSTRESS_SUM_BLOCKS + 1) * ATOMSTRESS_SUM_N, false);
+   }
+   AtomStressArgs v;
+   fillStencilArgs(v, sim);
+   v.px = sim->atoms.p.x; v.py = sim->atoms.p.y; v.pz = sim->atoms.p.z;
+   v.iSpecies = sim->atoms.iSpecies; v.speciesMass = sim->species_mass;
+   v.withKinetic = withKinetic != 0;
+   v.plane = nSlots;
+   const dim3 grid(ATOMSTRESS_BLOCKS), block(256);
+   if (!sim->do_eam) {
+      const LjArgs a = makeLjArgs(sim, sim->boxes.nLocalBoxes, nullptr);
+      v.rc2 = a.rc2;
+      if (sim->lj_pot.lj_interpolation.values) {
+         VirialLjTable p; p.t = ljTableView(sim);
+         hipLaunchKernelGGL(AtomStress_thread_atom<VirialLjTable>, grid, block, 0, st, v, p, sim->stressBuf);
+      } else {
+         VirialLj p; p.a = a;
+         hipLaunchKernelGGL(AtomStress_thread_atom<VirialLj>, grid, block, 0, st, v, p, sim->stressBuf);
+      }
+   } else {
+      const EamPotentialGpu& e = sim->eam_pot;
+      v.rc2 = e.cutoff * e.cutoff;
+      if (e.phiS.coefficients && e.rhoS.coefficients) {
+         VirialEam<true> p; p.phi = e.phi; p.rho = e.rho; p.phiS = e.phiS; p.rhoS = e.rhoS; p.dfEmbed = e.dfEmbed; p.dfi = R(0.0);
+         hipLaunchKernelGGL(AtomStress_thread_atom<VirialEam<true>>, grid, block, 0, st, v, p, sim->stressBuf);
+      } else {
+         VirialEam<false> p; p.phi = e.phi; p.rho = e.rho; p.phiS = e.phiS; p.rhoS = e.rhoS; p.dfEmbed = e.dfEmbed; p.dfi = R(0.0);
+         hipLaunchKernelGGL(AtomStress_thread_atom<VirialEam<false>>, grid, block, 0, st, v, p, sim->stressBuf);
+      }
+   }
+   LAUNCH_CHECK();
+   if (outBySlot6) HIP_CHECK(hipMemcpyAsync(outBySlot6, sim->stressBuf, 6 * nSlots * sizeof(real_t), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// Not in the reference: the printed-step figures of the planes computeAtomStress has left on the device (stress_kernels.h): 7 doubles come back, not the planes
+extern "C" void computeAtomStressSummary(SimGpu* sim, double atomVolume, double* out)
+{
+   hipStream_t st = analysisStream(sim);
+   if (!sim->stressBuf) { fprintf(stderr, "computeAtomStressSummary: no computeAtomStress call before it\n"); exit(-1); }
+   const size_t nSlots = (size_t)sim->boxes.nLocalBoxes * sim->maxAtoms;
+   double* final = sim->stressSumBuf + (size_t)ATOMSTRESS_SUM_BLOCKS * ATOMSTRESS_SUM_N;
+   hipLaunchKernelGGL(AtomStress_Summary, dim3(ATOMSTRESS_SUM_BLOCKS), dim3(256), 0, st, sim->stressBuf, nSlots, sim->boxes.nAtoms, sim->atoms.gid, sim->maxAtoms,
+                      1.0 / atomVolume, sim->stressSumBuf);
+   hipLaunchKernelGGL(AtomStress_SummaryFinal, dim3(1), dim3(256), 0, st, sim->stressSumBuf, ATOMSTRESS_SUM_BLOCKS, final);
+   LAUNCH_CHECK();
+   HIP_CHECK(hipMemcpyAsync(out, final, ATOMSTRESS_SUM_N * sizeof(double), hipMemcpyDeviceToHost, st));
    HIP_CHECK(hipStreamSynchronize(st));
 }
 

@@ -16,7 +16,10 @@
  * --cna, --cnaFile PATH, --cnaDump PATH (adaptive common neighbour analysis: every atom is FCC, HCP, ICO or other, sampled at every printed step; a
  * NonFCC column, PATH gets the four counts per sample and the dump the non-FCC atoms of the last step as extended XYZ),
  * --erateX R, --erateY R, --erateZ R, --deformStart S, --deformFile PATH (box deformation: engineering strain rates in 1/ps applied from global step S on, the
- * positions remapped affinely at the top of every step; V/V0 and Sxx(GPa) columns, PATH gets strain, box and stress tensor per sample; the reference's box is fixed). */
+ * positions remapped affinely at the top of every step; V/V0 and Sxx(GPa) columns, PATH gets strain, box and stress tensor per sample; the reference's box is fixed),
+ * --stress, --stressFile PATH, --stressDump PATH, --stressDumpMin X (per-atom virial stress: hydrostatic pressure and von Mises stress of every atom with the
+ * uniform atomic volume V/N, reduced on the device at every printed step; a MaxVM(GPa) column, PATH gets a line per sample and the dump the tensors of the atoms
+ * of the last step whose von Mises stress is at least X GPa as extended XYZ; the reference has no stress output). */
 #include "comd_host.h"
 #include <getopt.h>
 #include <math.h>
@@ -54,6 +57,7 @@ Command parseCommandLine(int argc, char** argv)
    strcpy(cmd.cspFile, "csp.dat");
    strcpy(cmd.cnaFile, "cna.dat");
    strcpy(cmd.deformFile, "deform.dat");
+   strcpy(cmd.stressFile, "stress.dat");
    int help = 0;
 
    const ArgDef defs[] = {
@@ -111,6 +115,10 @@ Command parseCommandLine(int argc, char** argv)
       { "erateZ",        0,  1, 'd', &cmd.erate[2],       0, "engineering strain rate of the box along z in 1/ps" },
       { "deformStart",   0,  1, 'i', &cmd.deformStart,    0, "global step straining begins at (default 0)" },
       { "deformFile",    0,  1, 's', cmd.deformFile, sizeof cmd.deformFile, "file the stress-strain samples are written to (default deform.dat)" },
+      { "stress",        0,  0, 'i', &cmd.stress,         0, "per-atom virial stress: hydrostatic pressure and von Mises stress, sampled at every printed step (a MaxVM(GPa) column)" },
+      { "stressFile",    0,  1, 's', cmd.stressFile, sizeof cmd.stressFile, "file the samples are written to (default stress.dat)" },
+      { "stressDump",    0,  1, 's', cmd.stressDump, sizeof cmd.stressDump, "extended-XYZ file of the per-atom stress tensors (GPa) of the last step (default: none)" },
+      { "stressDumpMin", 0,  1, 'd', &cmd.stressDumpMin,  0, "only atoms with a von Mises stress of at least this many GPa are dumped (default 0: all atoms)" },
    };
    const int nDefs = (int)(sizeof defs / sizeof defs[0]);
 
@@ -190,6 +198,7 @@ void printCmdYaml(FILE* file, Command* cmd)
               cmd->langevinTemp, cmd->langevinDamp, (unsigned long long)cmd->seed);
    if (cmd->csp) fprintf(file, "  CSP file: %s\n", cmd->cspFile);
    if (cmd->cna) fprintf(file, "  CNA file: %s\n", cmd->cnaFile);
+   if (cmd->stress) fprintf(file, "  Stress file: %s\n", cmd->stressFile);
    if (cmd->msd) fprintf(file, "  MSD from step: %d\n  MSD file: %s\n", cmd->msdStart, cmd->msdFile);
    if (cmd->erate[0] != 0.0 || cmd->erate[1] != 0.0 || cmd->erate[2] != 0.0)
       fprintf(file, "  Strain rates: [ %g, %g, %g ] 1/ps\n  Deform from step: %d\n  Deform file: %s\n", cmd->erate[0], cmd->erate[1], cmd->erate[2], cmd->deformStart, cmd->deformFile);

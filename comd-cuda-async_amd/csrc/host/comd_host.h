@@ -66,6 +66,10 @@ typedef struct CommandSt {
    double erate[3];       /* extension: engineering strain rates of the box along x, y, z in 1/ps (1e9/s = 0.001), negative compresses; all 0 = a fixed box, as in the reference */
    int deformStart;       /* extension: the global step straining begins at (default 0) */
    char deformFile[1024]; /* extension: where the print rank writes the stress-strain samples (default deform.dat) */
+   int stress;            /* extension: per-atom virial stress, its hydrostatic pressure and von Mises stress reduced on the device at every printed step */
+   char stressFile[1024]; /* extension: where the print rank writes the samples (default stress.dat) */
+   char stressDump[1024]; /* extension: extended-XYZ file of the per-atom tensors of the last step; empty = none */
+   double stressDumpMin;  /* extension: only atoms with a von Mises stress of at least this many GPa are dumped; 0 = all */
 } Command;
 
 #define COMD_LANGEVIN_SEED 0x436f4d44ull     /* "CoMD" */
@@ -359,6 +363,14 @@ typedef struct SimFlatSt {
    char deformFile[1024];
    double* deformRows;              /* [deformSamples][15]: step, time (fs), strain (3), extents (3), volume, stress xx yy zz yz xz xy (GPa), temperature (K) */
    int deformSamples, deformCap;
+   int stress;                      /* --stress: comdMain samples the per-atom stress summary at every printed step */
+   char stressFile[1024], stressDump[1024];
+   double stressDumpMin;            /* GPa */
+   double* stressRows;              /* [stressSamples][8]: step, the seven values of comdStressSummary (eV/A^3) */
+   int stressSamples, stressCap;
+   double stressMaxVmNow;           /* the MaxVM(GPa) column of printThings: the last sample, in eV/A^3 */
+   void* stressStage;               /* comdAtomStress: host staging for the by-slot planes, the gids and the occupancies, kept between calls */
+   size_t stressStageBytes;
 } SimFlat;
 
 SimFlat* initSimulation(Command cmd);
@@ -410,6 +422,15 @@ double comdDefaultCoordRadius(SimFlat* s);              /* that default */
  * Collective.  Returns 0. */
 enum { COMD_CNA_OTHER = 0, COMD_CNA_FCC = 1, COMD_CNA_HCP = 2, COMD_CNA_BCC = 3, COMD_CNA_ICO = 4 };
 int comdCommonNeighbors(SimFlat* s, int* typeByGid, long long counts[5]);
+/* not in the reference: the per-atom virial stress of the current state (valid whenever computePressure is), keyed by gid: stressByGid[6 g + c], nGlobal x 6
+ * doubles in eV (stress x volume, tension positive), c = xx yy zz yz xz xy; withKinetic != 0 includes -p p^T / m.  Their sum over the atoms is -(W) or
+ * -(K + W) of computePressure.  Each rank fills the entries of its local atoms from computeAtomStress, the others stay 0, and the array is summed over the
+ * ranks: the same on every rank.  Collective.  -1 and nothing launched on a simulation without device state. */
+int comdAtomStress(SimFlat* s, int withKinetic, double* stressByGid);
+/* not in the reference: out7 = {mean p, min p, max p, mean sigma, max sigma, the gid that holds it (the lowest of equals), N} of the current state: hydrostatic
+ * pressure p and von Mises stress sigma of every atom's tensor over the uniform atomic volume V / N, in eV/A^3 (x eVperA3inGPa = GPa), reduced on the device
+ * (computeAtomStress without a copy, computeAtomStressSummary) and then over the ranks.  The same on every rank.  Collective.  -1 as comdAtomStress. */
+int comdStressSummary(SimFlat* s, int withKinetic, double* out7);
 /* not in the reference (its box is nx lat for the whole run): box deformation, LAMMPS's `fix deform ... remap x`.
  * comdSetBox: the global box becomes L[3] Angstroms (the origin stays at 0) and the positions of the local atoms are scaled with it, L_new / L_old per axis, by
  *    comdRemapBoxGpu.  Every copy of the geometry follows: Domain (the expressions of initDecomposition, so neighbouring ranks agree bit for bit on their shared
@@ -434,7 +455,7 @@ void ensureInteriorForceLaunched(SimFlat* sim);
 
 /* ---- performanceTimers.h ---- */
 enum TimerHandle { totalTimer, loopTimer, timestepTimer, positionTimer, velocityTimer, redistributeTimer, atomHaloTimer,
-                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, cspTimer, cnaTimer, deformTimer, numberOfTimers };
+                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, cspTimer, cnaTimer, deformTimer, stressTimer, numberOfTimers };
 void profileStart(enum TimerHandle handle);
 void profileStop(enum TimerHandle handle);
 double getElapsedTime(enum TimerHandle handle);

@@ -171,6 +171,10 @@ SimFlat* initSimulationHost(Command cmd)
    strcpy(sim->cspFile, cmd.cspFile); strcpy(sim->cspDump, cmd.cspDump);
    sim->cna = cmd.cna;
    strcpy(sim->cnaFile, cmd.cnaFile); strcpy(sim->cnaDump, cmd.cnaDump);
+   /* --stress (not in the reference): the dump threshold is a von Mises stress, which is never negative */
+   if (!(cmd.stressDumpMin >= 0.0)) { printf("Error: --stressDumpMin must be >= 0 GPa (got %g).\n", cmd.stressDumpMin); exit(-1); }
+   sim->stress = cmd.stress; sim->stressDumpMin = cmd.stressDumpMin;
+   strcpy(sim->stressFile, cmd.stressFile); strcpy(sim->stressDump, cmd.stressDump);
    /* --erateX/Y/Z (not in the reference): the box strains at constant engineering rates; profile mode never redistributes, which the remap needs */
    for (int a = 0; a < 3; ++a) if (!(fabs(cmd.erate[a]) < 1e300)) { printf("Error: --erate%c must be a finite rate in 1/ps (got %g).\n", 'X' + a, cmd.erate[a]); exit(-1); }
    sim->deform = cmd.erate[0] != 0.0 || cmd.erate[1] != 0.0 || cmd.erate[2] != 0.0;
@@ -285,6 +289,7 @@ void destroySimulation(SimFlat** ps)
    free(s->cspRows); free(s->cspLast); free(s->cspStage);
    free(s->cnaRows); free(s->cnaLast); free(s->cnaStage);
    free(s->deformRows);
+   free(s->stressRows); free(s->stressStage);
    free(s->species); free(s->domain); free(s);
    *ps = NULL;
 }
@@ -308,9 +313,9 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
       s->firstPrint = 0;
       fprintf(screenOut,
               "#                                                                                         Performance\n"
-              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms%s%s%s%s%s\n",
+              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms%s%s%s%s%s%s\n",
               s->pressure ? "    Pressure(GPa)" : "", s->msd ? "         MSD(A^2)" : "", s->csp ? "      Defects" : "", s->cna ? "       NonFCC" : "",
-              s->deformReport ? "           V/V0         Sxx(GPa)" : "");
+              s->deformReport ? "           V/V0         Sxx(GPa)" : "", s->stress ? "       MaxVM(GPa)" : "");
       fflush(screenOut);
    }
    real_t time = iStep * s->dt;
@@ -326,6 +331,7 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
    if (s->csp) fprintf(screenOut, " %12d", s->cspDefectsNow);
    if (s->cna) fprintf(screenOut, " %12lld", s->cnaNonFccNow);
    if (s->deformReport) fprintf(screenOut, " %14.10f %16.10f", (double)s->V / (s->box0[0] * s->box0[1] * s->box0[2]), -((double)s->K[0] + s->W[0]) / s->V * eVperA3inGPa);
+   if (s->stress) fprintf(screenOut, " %16.10f", s->stressMaxVmNow * eVperA3inGPa);
    fprintf(screenOut, "\n");
 }
 
@@ -631,6 +637,85 @@ static void writeDeform(FILE* yaml, SimFlat* s)
    fflush(yaml);
 }
 
+/* --stress: one more row {step, mean / min / max hydrostatic pressure, mean / max von Mises stress, the gid of the max, N} from the device reduction (eV/A^3) */
+static void sampleStress(SimFlat* s, int iStep)
+{
+   if (s->stressSamples == s->stressCap) { s->stressCap = s->stressCap ? 2 * s->stressCap : 64; s->stressRows = (double*)realloc(s->stressRows, (size_t)s->stressCap * 8 * sizeof(double)); }
+   double* row = s->stressRows + 8 * (size_t)s->stressSamples++;
+   row[0] = (double)iStep;
+   if (comdStressSummary(s, 1, row + 1) != 0) { printf("Error: --stress needs the device state.\n"); exit(-1); }
+   s->stressMaxVmNow = row[5];
+}
+
+/* --stress: the file: a header line, then the rows of sampleStress in GPa.  --stressDump: the tensors of the last step as extended XYZ, Cu x y z sxx syy szz syz
+ * sxz sxy vm gid in GPa (the tensor over the uniform atomic volume), the atoms whose von Mises stress is at least --stressDumpMin; the positions gathered by gid
+ * over the ranks as the tensors are.  The YAML block names the file and gives the last sample's mean pressure and mean and max von Mises stress. */
+static void writeStress(FILE* yaml, SimFlat* s, int iStep)
+{
+   const size_t n = (size_t)s->atoms->nGlobal;
+   const double omega = (double)s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2] / (n ? (double)n : 1.0);
+   double *pos = NULL, *ten = NULL;
+   if (s->stressDump[0]) {          /* collective: before the other ranks leave */
+      double* mine = (double*)calloc(n ? 3 * n : 1, sizeof(double));
+      pos = (double*)malloc((n ? 3 * n : 1) * sizeof(double));
+      ten = (double*)malloc((n ? 6 * n : 1) * sizeof(double));
+      comdGatherByGid(s, 0, mine);
+      const size_t chunk = (size_t)1 << 28;
+      for (size_t o = 0; o < 3 * n; o += chunk) addDoubleParallel(mine + o, pos + o, (int)(3 * n - o < chunk ? 3 * n - o : chunk));
+      free(mine);
+      if (comdAtomStress(s, 1, ten) != 0) { printf("Error: --stressDump needs the device state.\n"); exit(-1); }
+   }
+   if (!printRank()) { free(pos); free(ten); return; }
+   const int samples = s->stressSamples;
+   FILE* f = fopen(s->stressFile, "w");
+   if (!f) { printf("Error: cannot write %s\n", s->stressFile); exit(-1); }
+   fprintf(f, "# Stress: N %d atomic volume %.17g A^3 (V / N of the last sample) samples %d | columns: step, mean / min / max hydrostatic pressure (GPa), "
+              "mean / max von Mises stress (GPa), gid of the max\n", s->atoms->nGlobal, omega, samples);
+   const double* last = NULL;
+   for (int k = 0; k < samples; ++k) {
+      last = s->stressRows + 8 * (size_t)k;
+      fprintf(f, "%.0f %.17g %.17g %.17g %.17g %.17g %.0f\n", last[0], last[1] * eVperA3inGPa, last[2] * eVperA3inGPa, last[3] * eVperA3inGPa,
+              last[4] * eVperA3inGPa, last[5] * eVperA3inGPa, last[6]);
+   }
+   fclose(f);
+   if (pos && ten) {
+      f = fopen(s->stressDump, "w");
+      if (!f) { printf("Error: cannot write %s\n", s->stressDump); exit(-1); }
+      const real_t* L = s->domain->globalExtent;
+      const double toGPa = eVperA3inGPa / omega;
+      double* vm = (double*)malloc((n ? n : 1) * sizeof(double));
+      size_t kept = 0;
+      for (size_t g = 0; g < n; ++g) {
+         const double* t = ten + 6 * g;
+         const double d0 = t[0] - t[1], d1 = t[1] - t[2], d2 = t[2] - t[0];
+         vm[g] = sqrt(0.5 * ((d0 * d0 + d1 * d1) + d2 * d2) + 3.0 * ((t[3] * t[3] + t[4] * t[4]) + t[5] * t[5])) * toGPa;
+         if (vm[g] >= s->stressDumpMin) kept++;
+      }
+      fprintf(f, "%zu\n", kept);
+      fprintf(f, "Lattice=\"%.17g 0 0 0 %.17g 0 0 0 %.17g\" Properties=species:S:1:pos:R:3:stress:R:6:vm:R:1:gid:I:1 step=%d units=GPa atomicVolume=%.17g minVM=%.17g\n",
+              (double)L[0], (double)L[1], (double)L[2], iStep, omega, s->stressDumpMin);
+      for (size_t g = 0; g < n; ++g)
+         if (vm[g] >= s->stressDumpMin) {
+            const double* t = ten + 6 * g;
+            fprintf(f, "Cu %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %zu\n", pos[3 * g], pos[3 * g + 1], pos[3 * g + 2],
+                    t[0] * toGPa, t[1] * toGPa, t[2] * toGPa, t[3] * toGPa, t[4] * toGPa, t[5] * toGPa, vm[g], g);
+         }
+      free(vm);
+      fclose(f);
+   }
+   free(pos); free(ten);
+   if (!yaml) return;
+   fprintf(yaml, "Stress:\n");
+   fprintf(yaml, "  Units: GPa\n");
+   fprintf(yaml, "  samples: %d\n", samples);
+   fprintf(yaml, "  file: %s\n", s->stressFile);
+   fprintf(yaml, "  finalMeanPressure: %.12e\n", last ? last[1] * eVperA3inGPa : 0.0);
+   fprintf(yaml, "  finalMeanVonMises: %.12e\n", last ? last[4] * eVperA3inGPa : 0.0);
+   fprintf(yaml, "  finalMaxVonMises: %.12e\n", last ? last[5] * eVperA3inGPa : 0.0);
+   fprintf(yaml, "\n");
+   fflush(yaml);
+}
+
 Validate* initValidate(SimFlat* sim)
 {
    sumAtoms(sim);
@@ -733,6 +818,7 @@ int comdMain(int argc, char** argv)
       if (sim->msd && iStep >= sim->msdStart) { startTimer(msdTimer); if (iStep == sim->msdStart) startMsd(sim); sampleMsd(sim, iStep); stopTimer(msdTimer); }
       if (sim->csp) { startTimer(cspTimer); sampleCsp(sim, iStep); stopTimer(cspTimer); }
       if (sim->cna) { startTimer(cnaTimer); sampleCna(sim, iStep); stopTimer(cnaTimer); }
+      if (sim->stress) { startTimer(stressTimer); sampleStress(sim, iStep); stopTimer(stressTimer); }
       printThings(sim, iStep, getElapsedTime(timestepTimer));
       /* --msdStart between two printed steps: the interval is taken as two timestep() calls (which give the bits of one) with the origin in between */
       const int toOrigin = sim->msd && sim->msdStart > iStep && sim->msdStart < iStep + printRate ? sim->msdStart - iStep : 0;
@@ -750,6 +836,7 @@ int comdMain(int argc, char** argv)
    if (sim->msd && iStep >= sim->msdStart) { startTimer(msdTimer); if (iStep == sim->msdStart) startMsd(sim); sampleMsd(sim, iStep); stopTimer(msdTimer); }
    if (sim->csp) { startTimer(cspTimer); sampleCsp(sim, iStep); stopTimer(cspTimer); }
    if (sim->cna) { startTimer(cnaTimer); sampleCna(sim, iStep); stopTimer(cnaTimer); }
+   if (sim->stress) { startTimer(stressTimer); sampleStress(sim, iStep); stopTimer(stressTimer); }
    printThings(sim, iStep, getElapsedTime(timestepTimer));
    timestampBarrier("Ending simulation\n");
    if (sim->pressure) printPressureYaml(yamlFile, sim);
@@ -758,6 +845,7 @@ int comdMain(int argc, char** argv)
    if (sim->csp) writeCsp(yamlFile, sim);
    if (sim->cna) writeCna(yamlFile, sim);
    if (sim->deformReport) writeDeform(yamlFile, sim);
+   if (sim->stress) { startTimer(stressTimer); writeStress(yamlFile, sim, iStep); stopTimer(stressTimer); }
 
    validateResult(validate, sim);
    profileStop(totalTimer);

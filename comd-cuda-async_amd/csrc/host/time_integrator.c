@@ -313,6 +313,76 @@ int comdCommonNeighbors(SimFlat* s, int* typeByGid, long long counts[5])
    return 0;
 }
 
+/* ---- per-atom virial stress (not in the reference; comd_host.h) ---- */
+int comdAtomStress(SimFlat* s, int withKinetic, double* stressByGid)
+{
+   if (!s->gpu.boxes.nAtoms) return -1;
+   const int cap = s->boxes->maxAtoms, nLocalBoxes = s->boxes->nLocalBoxes;
+   const size_t nSlots = (size_t)nLocalBoxes * cap, n = (size_t)s->atoms->nGlobal;
+   /* staging for the by-slot planes, kept with the simulation as comdCentroSymmetry's */
+   const size_t need = (6 * nSlots + 1) * sizeof(real_t) + (nSlots + 1 + (size_t)nLocalBoxes + 1) * sizeof(int);
+   if (need > s->stressStageBytes) { free(s->stressStage); s->stressStage = malloc(need); s->stressStageBytes = need; }
+   real_t* planes = (real_t*)s->stressStage;
+   int* gid = (int*)(planes + 6 * nSlots + 1);
+   int* nAtoms = gid + nSlots + 1;
+   computeAtomStress(&s->gpu, withKinetic, planes);          /* blocks: the stream is drained, the two copies below see the same state */
+   comdMemcpyDtoH(gid, s->gpu.atoms.gid, (long)(nSlots * sizeof(int)));
+   comdMemcpyDtoH(nAtoms, s->gpu.boxes.nAtoms, (long)((size_t)nLocalBoxes * sizeof(int)));
+   const int one = getNRanks() == 1;
+   double* mine = one ? stressByGid : (double*)malloc((n ? 6 * n : 1) * sizeof(double));
+   memset(mine, 0, 6 * n * sizeof(double));
+   for (int b = 0; b < nLocalBoxes; ++b)
+      for (size_t o = (size_t)b * cap, e = o + (size_t)nAtoms[b]; o < e; ++o) {
+         const size_t g = (size_t)gid[o];
+         if (g < n) for (int c = 0; c < 6; ++c) mine[6 * g + c] = (double)planes[(size_t)c * nSlots + o];
+      }
+   if (!one) {
+      /* every other rank holds 0 for a gid; in chunks whose count fits addDoubleParallel's int */
+      const size_t chunk = (size_t)1 << 28;
+      startTimer(commReduceTimer);
+      for (size_t o = 0; o < 6 * n; o += chunk) addDoubleParallel(mine + o, stressByGid + o, (int)(6 * n - o < chunk ? 6 * n - o : chunk));
+      stopTimer(commReduceTimer);
+      free(mine);
+   }
+   return 0;
+}
+
+int comdStressSummary(SimFlat* s, int withKinetic, double* out7)
+{
+   if (!s->gpu.boxes.nAtoms) return -1;
+   const double n = (double)s->atoms->nGlobal;
+   const double omega = (double)s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2] / (n > 0.0 ? n : 1.0);
+   double local[7];
+   computeAtomStress(&s->gpu, withKinetic, NULL);
+   computeAtomStressSummary(&s->gpu, omega, local);
+   const int nRanks = getNRanks(), me = getMyRank();
+   if (nRanks > 1) {
+      /* the sums add; the extremes and the gid go through one slot per rank of a summed vector (no MIN/MAX of doubles in the transport), taken in rank order */
+      double* mine = (double*)calloc(2 * (size_t)(3 + 4 * nRanks), sizeof(double));
+      double* all = mine + 3 + 4 * (size_t)nRanks;
+      mine[0] = local[0]; mine[1] = local[3]; mine[2] = local[6];
+      if (local[6] > 0.0) { double* slot = mine + 3 + 4 * (size_t)me; slot[0] = local[1]; slot[1] = local[2]; slot[2] = local[4]; slot[3] = local[5] + 1.0; }
+      startTimer(commReduceTimer);
+      addDoubleParallel(mine, all, 3 + 4 * nRanks);
+      stopTimer(commReduceTimer);
+      local[0] = all[0]; local[3] = all[1]; local[6] = all[2];
+      local[1] = INFINITY; local[2] = -INFINITY; local[4] = -INFINITY; local[5] = -1.0;
+      for (int r = 0; r < nRanks; ++r) {
+         const double* slot = all + 3 + 4 * (size_t)r;
+         if (slot[3] == 0.0) continue;          /* a rank without atoms */
+         const double g = slot[3] - 1.0;
+         if (slot[0] < local[1]) local[1] = slot[0];
+         if (slot[1] > local[2]) local[2] = slot[1];
+         if (local[5] < 0.0 || slot[2] > local[4] || (slot[2] == local[4] && g < local[5])) { local[4] = slot[2]; local[5] = g; }
+      }
+      free(mine);
+   }
+   const double N = local[6];
+   out7[0] = N > 0.0 ? local[0] / N : 0.0; out7[1] = local[1]; out7[2] = local[2];
+   out7[3] = N > 0.0 ? local[3] / N : 0.0; out7[4] = local[4]; out7[5] = local[5]; out7[6] = N;
+   return 0;
+}
+
 /* ---- displacement tracking (not in the reference; comd_host.h) ---- */
 int comdTrackDisplacement(SimFlat* s, int on)
 {

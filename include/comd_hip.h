@@ -248,6 +248,8 @@ typedef struct SimGpuSt {
    int*         cnaBuf;                /* device [nLocalBoxes*maxAtoms]: the structure types of computeCommonNeighbors, allocated by its first call */
    void*        legs;                  /* private to the device library: what the last force launches of this simulation ran (hip/comd_device.hip ForceLegs, comdForceLegReport) */
    double       cellVolume0;           /* host: volume of a link cell at AllocateGpu, in A^3: the occupancy estimates behind row, image and LDS sizes keep it when comdRemapBoxGpu changes the box */
+   real_t*      stressBuf;             /* device [6][nLocalBoxes*maxAtoms]: the planes xx yy zz yz xz xy of computeAtomStress, allocated by its first call */
+   double*      stressSumBuf;          /* device: the workgroups' rows for computeAtomStressSummary, allocated with stressBuf */
 } SimGpu;
 
 /* Everything AllocateGpu needs to know about the rank's geometry and potential.
@@ -486,6 +488,23 @@ void computeCentroSymmetry(SimGpu* sim, real_t rCoord, real_t* outCspBySlot, int
  * stream, no atomics, bit-reproducible; reads r and the cell tables, writes only its own buffer (allocated by the first call, freed by DestroyGpu).
  * Blocks until the result is on the host. */
 void computeCommonNeighbors(SimGpu* sim, int* outTypeBySlot);
+/* Not in the reference (CoMD has no stress output): the virial stress of every one of THIS rank's local atoms (hip/stress_kernels.h).  For the atom in local
+ * slot o = cell * maxAtoms + index, with its neighbours j (local or halo image) at 0 < |r_ij|^2 <= cutoff^2,
+ *   s_ab = -( [withKinetic] p_a p_b / m + 1/2 sum_j r_ij,a f_ij,b ),  r_ij = r_i - r_j, f_ij the force on i due to j,
+ * in eV (stress x volume, tension positive), ab = xx yy zz yz xz xy: the pair convention, the pair functions and the acceptance test of computeVirial, so
+ * that the sum over all atoms of all ranks is -(W) or -(K + W) of computeVirial.  outBySlot6[c * nLocalBoxes * maxAtoms + o] is component c, six planes in
+ * host memory; entries of empty slots mean nothing.  outBySlot6 == NULL: the planes stay on the device for computeAtomStressSummary, nothing is copied.
+ * Valid when computeVirial is: after a complete force evaluation (timestep, computeForce), any method.  Launched on the stream computeEnergy uses, after the
+ * force work of both streams of the overlap mode; no atomics, bit-reproducible; reads r, p, dfEmbed and the cell tables, writes only its own planes
+ * (6 sizeof(real_t) bytes per local slot, allocated by the first call, freed by DestroyGpu).  Blocks until the kernel is done (and the copy, when asked for). */
+void computeAtomStress(SimGpu* sim, int withKinetic, real_t* outBySlot6);
+/* Not in the reference: the printed-step figures of the planes the last computeAtomStress call of this simulation left on the device, with the uniform atomic
+ * volume atomVolume (A^3): p = -(s_xx + s_yy + s_zz) / (3 atomVolume), sigma = the von Mises stress of s / atomVolume, both in eV/A^3, formed in double.
+ *   out[0] sum of p, out[1] min p, out[2] max p, out[3] sum of sigma, out[4] max sigma, out[5] the gid that holds it (the lowest one of equals),
+ *   out[6] the number of local atoms -- over THIS rank's atoms; without atoms +inf, -inf, -inf and gid -1.
+ * Seven doubles are copied, never the planes.  Same stream; deterministic two-stage reduction.  A call without a computeAtomStress before it ends the run.
+ * Blocks until the result is on the host. */
+void computeAtomStressSummary(SimGpu* sim, double atomVolume, double* out);
 /* Not in the reference: unwrapped displacements since an origin, for the mean-squared displacement (hip/msd_kernels.h).  on != 0: allocate and zero
  * one 32-byte record {dx, dy, dz, spare} per global atom id, signed 64-bit fixed point in units of 2^-32 Angstroms; from then on the drift kernels
  * of this simulation (advancePositionGpu and the fused forms, plain and Langevin) add dt p/m of every local atom into the record of its gid.  Already
