@@ -150,6 +150,14 @@ def lib_host():
         lib.comdAtomStress.restype = ctypes.c_int
         lib.comdStressSummary.argtypes = [vp, ctypes.c_int, c_double_p]
         lib.comdStressSummary.restype = ctypes.c_int
+        lib.comdStrainReference.argtypes = [vp, ctypes.c_int]
+        lib.comdStrainReference.restype = ctypes.c_int
+        lib.comdAtomStrain.argtypes = [vp, ctypes.c_double, c_double_p, c_int_p]
+        lib.comdAtomStrain.restype = ctypes.c_int
+        lib.comdStrainSummary.argtypes = [vp, ctypes.c_double, ctypes.c_double, c_double_p]
+        lib.comdStrainSummary.restype = ctypes.c_int
+        lib.comdStrainReferenceBox.argtypes = [vp, c_double_p]
+        lib.comdStrainReferenceBox.restype = ctypes.c_int
         lib.comdDefaultCoordRadius.argtypes = [vp]
         lib.comdDefaultCoordRadius.restype = ctypes.c_double
         lib.comdLatticeConstant.argtypes = [vp]
@@ -576,6 +584,78 @@ class Simulation:
             raise RuntimeError("stress_summary: comdStressSummary failed")
         return {"mean_pressure": out[0], "min_pressure": out[1], "max_pressure": out[2], "mean_von_mises": out[3], "max_von_mises": out[4],
                 "max_von_mises_gid": int(out[5]), "n": int(out[6])}
+
+    # --- per-atom strain (not in the reference: comd-hip --strain, --strainRef, --strainCutoff, --strainThreshold, --strainFile, --strainDump, --strainDumpMin) ---
+    def set_strain_reference(self, on=True):
+        """Take the current state as the reference of atomic_strain(): every atom's position, keyed by gid, in a table of doubles on every rank's device
+        (32 bytes per global atom), and the current box.  Already set: the reference moves to the current state.  on=False drops it and frees the device
+        memory.  Every rank of a multi-rank run makes the call.  RuntimeError when the device refuses the memory."""
+        if self.host_only:
+            raise RuntimeError("set_strain_reference: a host-only simulation has no device state")
+        if self.lib.comdStrainReference(self.ptr, 1 if on else 0) != 0:
+            raise RuntimeError(f"set_strain_reference: no device memory for the reference positions of {self.n_global} atoms")
+
+    @property
+    def strain_reference_box(self):
+        """float64 (3,): the extents of the global box when set_strain_reference() was called.  ValueError without a reference."""
+        out = (ctypes.c_double * 3)()
+        if self.lib.comdStrainReferenceBox(self.ptr, out) != 0:
+            raise ValueError("strain_reference_box: no reference (call set_strain_reference() first)")
+        return self._np.array(out[0:3], dtype=self._np.float64)
+
+    def _strain_cutoff(self, what, cutoff):
+        """the radius handed to the host (0 = its default), after the refusals that come before any launch"""
+        if self.host_only:
+            raise RuntimeError(f"{what}: a host-only simulation has no device state")
+        if self.lib.comdStrainReferenceBox(self.ptr, (ctypes.c_double * 3)()) != 0:
+            raise ValueError(f"{what}: no reference (call set_strain_reference() first)")
+        if cutoff is not None and not (0.0 < float(cutoff) <= self.cutoff):
+            raise ValueError(f"{what}: need 0 < cutoff <= the force cutoff {self.cutoff} (got {cutoff})")
+        return 0.0 if cutoff is None else float(cutoff)
+
+    def atomic_strain(self, cutoff=None):
+        """(E float64 (n_global, 6), d2min float64 (n_global,), neighbours int32 (n_global,)) of the current state against the reference, keyed by gid.
+        For atom i with its neighbours j within `cutoff` Angstroms in the CURRENT configuration (None: halfway between the first two FCC shells, as
+        centro_symmetry's r_coord; at most the force cutoff), d = x_j - x_i now and d0 the same separation in the reference (minimum image of the reference
+        box): F = (sum d d0^T)(sum d0 d0^T)^-1 is the best affine map d ~ F d0, E = 1/2 (F^T F - I) the Green-Lagrange strain, components xx yy zz yz xz xy,
+        and d2min = sum_j |d - F d0|^2 in Angstroms^2 the non-affine residue (Falk and Langer's D^2min, not divided by the neighbour count).  An atom with
+        fewer than 3 neighbours or a singular sum d0 d0^T has NaN in E and d2min.  Computed on the device by computeAtomStrain, summed over the ranks (every
+        rank gets the global arrays).  ValueError, before anything is launched, without a reference or for a cutoff outside (0, force cutoff]."""
+        np = self._np
+        r = self._strain_cutoff("atomic_strain", cutoff)
+        n = self.n_global
+        out, count = np.zeros((max(n, 1), 7), dtype=np.float64), np.zeros(max(n, 1), dtype=np.int32)
+        if self.lib.comdAtomStrain(self.ptr, r, out.ctypes.data_as(c_double_p), count.ctypes.data_as(c_int_p)) != 0:
+            raise RuntimeError("atomic_strain: comdAtomStrain failed")
+        return out[:n, :6].copy(), out[:n, 6].copy(), count[:n]
+
+    @staticmethod
+    def _shear_of(np, e):
+        d0, d1, d2 = e[:, 0] - e[:, 1], e[:, 1] - e[:, 2], e[:, 2] - e[:, 0]
+        return np.sqrt(((e[:, 3] * e[:, 3] + e[:, 4] * e[:, 4]) + e[:, 5] * e[:, 5]) + ((d0 * d0 + d1 * d1) + d2 * d2) / 6.0)
+
+    def shear_strain(self, cutoff=None):
+        """float64 (n_global,): the shear invariant sqrt(E_yz^2 + E_xz^2 + E_xy^2 + [(E_xx - E_yy)^2 + (E_yy - E_zz)^2 + (E_zz - E_xx)^2] / 6) of atomic_strain()."""
+        return self._shear_of(self._np, self.atomic_strain(cutoff)[0])
+
+    def volumetric_strain(self, cutoff=None):
+        """float64 (n_global,): tr(E) / 3 of atomic_strain()."""
+        e = self.atomic_strain(cutoff)[0]
+        return ((e[:, 0] + e[:, 1]) + e[:, 2]) / 3.0
+
+    def strain_summary(self, cutoff=None, threshold=None):
+        """{"n", "invalid", "mean_shear", "max_shear", "max_shear_gid", "mean_volumetric", "mean_d2min", "max_d2min", "above_threshold"}: the figures of
+        shear_strain(), volumetric_strain() and d2min, reduced on the device (computeAtomStrainSummary: the per-atom planes never leave it) and over the
+        ranks.  Invalid atoms are counted and left out of means and extremes; the gid is the lowest one that holds the maximum; above_threshold counts
+        the atoms with a shear strain >= threshold (None: 0.1).  ValueError as atomic_strain, or for a threshold that is not > 0."""
+        r = self._strain_cutoff("strain_summary", cutoff)
+        if threshold is not None and not float(threshold) > 0.0:
+            raise ValueError(f"strain_summary: need threshold > 0 (got {threshold})")
+        out = (ctypes.c_double * 9)()
+        if self.lib.comdStrainSummary(self.ptr, r, 0.1 if threshold is None else float(threshold), out) != 0:
+            raise RuntimeError("strain_summary: comdStrainSummary failed")
+        return {"n": int(out[0]), "invalid": int(out[1]), "mean_shear": out[2], "max_shear": out[3], "max_shear_gid": int(out[4]),
+                "mean_volumetric": out[5], "mean_d2min": out[6], "max_d2min": out[7], "above_threshold": int(out[8])}
 
     # --- box deformation (not in the reference: comd-hip --erateX, --erateY, --erateZ, --deformStart, --deformFile) ---
     def _box6(self):

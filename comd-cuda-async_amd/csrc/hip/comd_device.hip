@@ -25,6 +25,7 @@
 #include "csp_kernels.h"
 #include "cna_kernels.h"
 #include "stress_kernels.h"
+#include "strain_kernels.h"
 #include "langevin_kernels.h"
 #include "msd_kernels.h"
 #include "deform_kernels.h"
@@ -607,7 +608,8 @@ extern "C" void DestroyGpu(SimGpu* sim)
                     sim->boxes.boxIDLookUp, sim->boxes.boxIDLookUpReverse, sim->eam_pot.phiS.coefficients, sim->eam_pot.rhoS.coefficients,
                     sim->eam_pot.pairRows, sim->eam_pot.pairRowCount, sim->eam_pot.cellSel, sim->eam_pot.brickGroup, sim->eam_pot.brickList, sim->eam_pot.brickSel, sim->eam_pot.brickStats, sim->eam_pot.atomRows, sim->eam_pot.atomRowCount, sim->eam_pot.atomBrickSel,
                     sim->atoms.neighborList.brickRows, sim->atoms.neighborList.brickRowCount, sim->adapterScan, sim->lj_pot.waveCand, sim->lj_pot.waveCandCount, sim->lj_pot.packedR[0], sim->lj_pot.packedR[1], sim->lj_pot.packedF[0], sim->lj_pot.packedF[1],
-                    sim->lj_pot.lj_interpolation.values, sim->virialBuf, sim->pairHistBuf, sim->dispBuf, sim->dispSumBuf, sim->cspBuf, sim->cspCoordBuf, sim->cnaBuf, sim->stressBuf, sim->stressSumBuf };
+                    sim->lj_pot.lj_interpolation.values, sim->virialBuf, sim->pairHistBuf, sim->dispBuf, sim->dispSumBuf, sim->cspBuf, sim->cspCoordBuf, sim->cnaBuf, sim->stressBuf, sim->stressSumBuf,
+                    sim->strainRefBuf, sim->strainBuf, sim->strainCountBuf, sim->strainSumBuf };
    for (void* p : ptrs) if (p) HIP_CHECK(hipFree(p));
    if (sim->statusEvent) (void)hipEventDestroy((hipEvent_t)sim->statusEvent);
    if (sim->pinned) HIP_CHECK(hipHostFree(sim->pinned));
@@ -1360,6 +1362,88 @@ extern "C" void computeAtomStressSummary(SimGpu* sim, double atomVolume, double*
    hipLaunchKernelGGL(AtomStress_SummaryFinal, dim3(1), dim3(256), 0, st, sim->stressSumBuf, ATOMSTRESS_SUM_BLOCKS, final);
    LAUNCH_CHECK();
    HIP_CHECK(hipMemcpyAsync(out, final, ATOMSTRESS_SUM_N * sizeof(double), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// Not in the reference: the reference snapshot of the per-atom strain (strain_kernels.h).  on: one 32-byte record of doubles per global atom id, zeroed, then
+// the positions of this rank's local atoms at their gids (taken again when it is already on); the host adds the ranks' tables and uploads the sum into
+// strainRefBuf.  off: the table and the planes of computeAtomStrain are freed.  1 and no reference when the device cannot give the memory.
+static void freeStrainPlanes(SimGpu* sim)
+{
+   if (sim->strainBuf) { HIP_CHECK(hipFree(sim->strainBuf)); HIP_CHECK(hipFree(sim->strainCountBuf)); HIP_CHECK(hipFree(sim->strainSumBuf)); }
+   sim->strainBuf = nullptr; sim->strainCountBuf = nullptr; sim->strainSumBuf = nullptr;
+}
+
+extern "C" int comdStrainReferenceGpu(SimGpu* sim, int nGlobal, int on)
+{
+   hipStream_t st = analysisStream(sim);
+   if (!on || nGlobal != sim->strainRefN) {
+      if (sim->strainRefBuf || sim->strainBuf) HIP_CHECK(hipStreamSynchronize(st));
+      if (sim->strainRefBuf) HIP_CHECK(hipFree(sim->strainRefBuf));
+      sim->strainRefBuf = nullptr; sim->strainRefN = 0;
+      freeStrainPlanes(sim);
+      if (!on) return 0;
+   }
+   if (nGlobal < 1) return 1;
+   if (!sim->strainRefBuf) {
+      void* d = nullptr;
+      if (hipMalloc(&d, (size_t)nGlobal * 4 * sizeof(double)) != hipSuccess) {
+         (void)hipGetLastError();
+         fprintf(stderr, "comdStrainReferenceGpu: rank %d: no device memory for %d records of 32 bytes (%.1f MB): no reference\n",
+                 g_rank, nGlobal, nGlobal * 32.0 / 1048576.0);
+         return 1;
+      }
+      sim->strainRefBuf = (double*)d; sim->strainRefN = nGlobal;
+   }
+   const size_t nSlots = (size_t)sim->boxes.nLocalBoxes * sim->maxAtoms;
+   HIP_CHECK(hipMemsetAsync(sim->strainRefBuf, 0, (size_t)nGlobal * 4 * sizeof(double), st));
+   const size_t blocks = (nSlots + 255) / 256;
+   hipLaunchKernelGGL(StrainReference_Store, dim3((unsigned)(blocks < 4096 ? (blocks ? blocks : 1) : 4096)), dim3(256), 0, st, sim->atoms.r.x, sim->atoms.r.y, sim->atoms.r.z,
+                      sim->boxes.nAtoms, sim->atoms.gid, sim->maxAtoms, nSlots, nGlobal, sim->strainRefBuf);
+   LAUNCH_CHECK();
+   HIP_CHECK(hipStreamSynchronize(st));
+   return 0;
+}
+
+// Not in the reference: the per-atom strain tensor and D^2min against the reference table (strain_kernels.h).  One instance for every potential and
+// method: it reads positions, gids and cells only.  The planes and the rows of the summary are allocated by the first call.
+extern "C" void computeAtomStrain(SimGpu* sim, real_t rCut, real_t* outBySlot7, int* outCountBySlot)
+{
+   hipStream_t st = analysisStream(sim);
+   const real_t cutoff = sim->do_eam ? sim->eam_pot.cutoff : sim->lj_pot.cutoff;
+   if (!sim->strainRefBuf) { fprintf(stderr, "computeAtomStrain: no reference (comdStrainReferenceGpu)\n"); exit(-1); }
+   if (!(rCut > R(0.0)) || rCut > cutoff) { fprintf(stderr, "computeAtomStrain: rCut %g outside (0, cutoff = %g]\n", (double)rCut, (double)cutoff); exit(-1); }
+   const size_t nSlots = (size_t)sim->boxes.nLocalBoxes * sim->maxAtoms;
+   if (!sim->strainBuf) {
+      sim->strainBuf = dalloc<real_t>(ATOMSTRAIN_PLANES * nSlots);
+      sim->strainCountBuf = dalloc<int>(nSlots);
+      sim->strainSumBuf = dalloc<double>((size_t)(ATOMSTRAIN_SUM_BLOCKS + 1) * ATOMSTRAIN_SUM_N, false);
+   }
+   AtomStrainArgs v;
+   fillStencilArgs(v, sim);
+   v.gid = sim->atoms.gid; v.ref = sim->strainRefBuf; v.nRef = sim->strainRefN;
+   v.rs2 = rCut * rCut;
+   v.L0x = sim->strainL0[0]; v.L0y = sim->strainL0[1]; v.L0z = sim->strainL0[2];
+   v.plane = nSlots;
+   hipLaunchKernelGGL(AtomStrain_thread_atom, dim3(ATOMSTRAIN_BLOCKS), dim3(256), 0, st, v, sim->strainBuf, sim->strainCountBuf);
+   LAUNCH_CHECK();
+   if (outBySlot7) HIP_CHECK(hipMemcpyAsync(outBySlot7, sim->strainBuf, ATOMSTRAIN_PLANES * nSlots * sizeof(real_t), hipMemcpyDeviceToHost, st));
+   if (outCountBySlot) HIP_CHECK(hipMemcpyAsync(outCountBySlot, sim->strainCountBuf, nSlots * sizeof(int), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// Not in the reference: the printed-step figures of the planes computeAtomStrain has left on the device (strain_kernels.h): 9 doubles come back, not the planes
+extern "C" void computeAtomStrainSummary(SimGpu* sim, double threshold, double* out)
+{
+   hipStream_t st = analysisStream(sim);
+   if (!sim->strainBuf) { fprintf(stderr, "computeAtomStrainSummary: no computeAtomStrain call before it\n"); exit(-1); }
+   const size_t nSlots = (size_t)sim->boxes.nLocalBoxes * sim->maxAtoms;
+   double* final = sim->strainSumBuf + (size_t)ATOMSTRAIN_SUM_BLOCKS * ATOMSTRAIN_SUM_N;
+   hipLaunchKernelGGL(AtomStrain_Summary, dim3(ATOMSTRAIN_SUM_BLOCKS), dim3(256), 0, st, sim->strainBuf, nSlots, sim->boxes.nAtoms, sim->atoms.gid, sim->maxAtoms,
+                      threshold, sim->strainSumBuf);
+   hipLaunchKernelGGL(AtomStrain_SummaryFinal, dim3(1), dim3(256), 0, st, sim->strainSumBuf, ATOMSTRAIN_SUM_BLOCKS, final);
+   LAUNCH_CHECK();
+   HIP_CHECK(hipMemcpyAsync(out, final, ATOMSTRAIN_SUM_N * sizeof(double), hipMemcpyDeviceToHost, st));
    HIP_CHECK(hipStreamSynchronize(st));
 }
 

@@ -19,7 +19,11 @@
  * positions remapped affinely at the top of every step; V/V0 and Sxx(GPa) columns, PATH gets strain, box and stress tensor per sample; the reference's box is fixed),
  * --stress, --stressFile PATH, --stressDump PATH, --stressDumpMin X (per-atom virial stress: hydrostatic pressure and von Mises stress of every atom with the
  * uniform atomic volume V/N, reduced on the device at every printed step; a MaxVM(GPa) column, PATH gets a line per sample and the dump the tensors of the atoms
- * of the last step whose von Mises stress is at least X GPa as extended XYZ; the reference has no stress output). */
+ * of the last step whose von Mises stress is at least X GPa as extended XYZ; the reference has no stress output),
+ * --strain, --strainRef S, --strainCutoff R, --strainThreshold X, --strainFile PATH, --strainDump PATH, --strainDumpMin X (per-atom strain against the state at
+ * the end of global step S: the Green-Lagrange tensor of the best affine map of every atom's neighbourhood within R, its shear invariant and the non-affine
+ * residue D^2min, reduced on the device at every printed step; a MaxShear column, PATH gets a line per sample and the dump the tensors of the atoms of the last
+ * step whose shear strain is at least X as extended XYZ). */
 #include "comd_host.h"
 #include <getopt.h>
 #include <math.h>
@@ -58,6 +62,8 @@ Command parseCommandLine(int argc, char** argv)
    strcpy(cmd.cnaFile, "cna.dat");
    strcpy(cmd.deformFile, "deform.dat");
    strcpy(cmd.stressFile, "stress.dat");
+   strcpy(cmd.strainFile, "strain.dat");
+   cmd.strainThreshold = 0.1;
    int help = 0;
 
    const ArgDef defs[] = {
@@ -119,6 +125,13 @@ Command parseCommandLine(int argc, char** argv)
       { "stressFile",    0,  1, 's', cmd.stressFile, sizeof cmd.stressFile, "file the samples are written to (default stress.dat)" },
       { "stressDump",    0,  1, 's', cmd.stressDump, sizeof cmd.stressDump, "extended-XYZ file of the per-atom stress tensors (GPa) of the last step (default: none)" },
       { "stressDumpMin", 0,  1, 'd', &cmd.stressDumpMin,  0, "only atoms with a von Mises stress of at least this many GPa are dumped (default 0: all atoms)" },
+      { "strain",        0,  0, 'i', &cmd.strain,         0, "per-atom strain tensor, shear strain and D^2min against a reference snapshot, sampled at every printed step (a MaxShear column)" },
+      { "strainRef",     0,  1, 'i', &cmd.strainRef,      0, "global step at whose end the reference is taken (0..nSteps; default 0)" },
+      { "strainCutoff",  0,  1, 'd', &cmd.strainCutoff,   0, "neighbour radius of the strain fit in Angstroms (default (1/sqrt 2 + 1) lat / 2; at most the force cutoff)" },
+      { "strainThreshold", 0, 1, 'd', &cmd.strainThreshold, 0, "atoms with a shear strain of at least this are counted (default 0.1)" },
+      { "strainFile",    0,  1, 's', cmd.strainFile, sizeof cmd.strainFile, "file the samples are written to (default strain.dat)" },
+      { "strainDump",    0,  1, 's', cmd.strainDump, sizeof cmd.strainDump, "extended-XYZ file of the per-atom strain tensors, shear strain and D^2min of the last step (default: none)" },
+      { "strainDumpMin", 0,  1, 'd', &cmd.strainDumpMin,  0, "only atoms with a shear strain of at least this are dumped (default 0: all atoms)" },
    };
    const int nDefs = (int)(sizeof defs / sizeof defs[0]);
 
@@ -145,6 +158,7 @@ Command parseCommandLine(int argc, char** argv)
          case 'd': *(double*)d->ptr = atof(optarg);
                    if (d->ptr == &cmd.cspThreshold) cmd.cspThresholdSet = 1;
                    if (d->ptr == &cmd.cspCoord) cmd.cspCoordSet = 1;
+                   if (d->ptr == &cmd.strainCutoff) cmd.strainCutoffSet = 1;
                    break;
          case 'u': *(uint64_t*)d->ptr = strtoull(optarg, NULL, 0); break;
          case 's': strncpy((char*)d->ptr, optarg, (size_t)d->size - 1); ((char*)d->ptr)[d->size - 1] = '\0'; break;
@@ -199,6 +213,7 @@ void printCmdYaml(FILE* file, Command* cmd)
    if (cmd->csp) fprintf(file, "  CSP file: %s\n", cmd->cspFile);
    if (cmd->cna) fprintf(file, "  CNA file: %s\n", cmd->cnaFile);
    if (cmd->stress) fprintf(file, "  Stress file: %s\n", cmd->stressFile);
+   if (cmd->strain) fprintf(file, "  Strain reference step: %d\n  Strain file: %s\n", cmd->strainRef, cmd->strainFile);
    if (cmd->msd) fprintf(file, "  MSD from step: %d\n  MSD file: %s\n", cmd->msdStart, cmd->msdFile);
    if (cmd->erate[0] != 0.0 || cmd->erate[1] != 0.0 || cmd->erate[2] != 0.0)
       fprintf(file, "  Strain rates: [ %g, %g, %g ] 1/ps\n  Deform from step: %d\n  Deform file: %s\n", cmd->erate[0], cmd->erate[1], cmd->erate[2], cmd->deformStart, cmd->deformFile);

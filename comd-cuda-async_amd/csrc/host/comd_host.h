@@ -70,6 +70,14 @@ typedef struct CommandSt {
    char stressFile[1024]; /* extension: where the print rank writes the samples (default stress.dat) */
    char stressDump[1024]; /* extension: extended-XYZ file of the per-atom tensors of the last step; empty = none */
    double stressDumpMin;  /* extension: only atoms with a von Mises stress of at least this many GPa are dumped; 0 = all */
+   int strain;            /* extension: per-atom strain tensor, shear strain and D^2min against a reference snapshot, reduced on the device at every printed step */
+   int strainRef;         /* extension: the global step the reference is taken at, 0..nSteps (default 0) */
+   double strainCutoff;   /* extension: the neighbour radius r_s in Angstroms; absent = that of --cspCoord, halfway between the first two FCC shells */
+   int strainCutoffSet;   /* the value was given (a given 0 is refused, an absent one means the default) */
+   double strainThreshold;/* extension: atoms with a shear strain of at least this are counted (default 0.1) */
+   char strainFile[1024]; /* extension: where the print rank writes the samples (default strain.dat) */
+   char strainDump[1024]; /* extension: extended-XYZ file of the per-atom tensors of the last step; empty = none */
+   double strainDumpMin;  /* extension: only atoms with a shear strain of at least this are dumped; 0 = all */
 } Command;
 
 #define COMD_LANGEVIN_SEED 0x436f4d44ull     /* "CoMD" */
@@ -371,6 +379,16 @@ typedef struct SimFlatSt {
    double stressMaxVmNow;           /* the MaxVM(GPa) column of printThings: the last sample, in eV/A^3 */
    void* stressStage;               /* comdAtomStress: host staging for the by-slot planes, the gids and the occupancies, kept between calls */
    size_t stressStageBytes;
+   int strainHasRef;                /* comdStrainReference: the device holds a reference table */
+   double strainL0[3];              /* the global box when the reference was taken */
+   int strain, strainRef;           /* --strain: comdMain takes the reference at global step strainRef and samples the summary at every printed step from then on */
+   double strainCutoff, strainThreshold, strainDumpMin;      /* r_s (A, default resolved), the shear-strain threshold of the count, that of the dump */
+   char strainFile[1024], strainDump[1024];
+   double* strainRows;              /* [strainSamples][10]: step, the nine values of comdStrainSummary */
+   int strainSamples, strainCap;
+   double strainMaxShearNow;        /* the MaxShear column of printThings: the last sample, 0 before the reference */
+   void* strainStage;               /* comdAtomStrain: host staging for the by-slot planes, the counts, the gids and the occupancies, kept between calls */
+   size_t strainStageBytes;
 } SimFlat;
 
 SimFlat* initSimulation(Command cmd);
@@ -431,6 +449,24 @@ int comdAtomStress(SimFlat* s, int withKinetic, double* stressByGid);
  * pressure p and von Mises stress sigma of every atom's tensor over the uniform atomic volume V / N, in eV/A^3 (x eVperA3inGPa = GPa), reduced on the device
  * (computeAtomStress without a copy, computeAtomStressSummary) and then over the ranks.  The same on every rank.  Collective.  -1 as comdAtomStress. */
 int comdStressSummary(SimFlat* s, int withKinetic, double* out7);
+/* not in the reference: the reference snapshot of the per-atom strain.  on != 0: the current positions of all atoms become x0, keyed by gid, in a table of
+ * doubles replicated on every rank's device (32 bytes per global atom: each rank stores its local atoms, the tables are summed over the ranks -- every other
+ * rank holds 0 for a gid -- and uploaded), and the current global box becomes L0; already on: the reference moves to the current state.  on == 0: it is
+ * dropped and the device memory freed.  All ranks or none.  Collective.  Returns 1 when a device refused the memory, -1 without device state, else 0. */
+int comdStrainReference(SimFlat* s, int on);
+int comdStrainReferenceBox(SimFlat* s, double* L0);      /* L0[3] of the reference; -1 and nothing written without one */
+/* not in the reference: the Green-Lagrange strain E = 1/2 (F^T F - I) and the non-affine displacement D^2min of every atom of the current state against the
+ * reference (computeAtomStrain, comd_hip.h, says how F is fitted), keyed by gid: strainByGid7[7 g + c], c = 0..5 E xx yy zz yz xz xy, c = 6 D^2 in A^2, and
+ * countByGid[g] the neighbours within rCut of the current configuration; NaN in all seven for an invalid atom (fewer than 3 neighbours or a singular V).
+ * rCut <= 0: the default, comdDefaultCoordRadius.  Each rank fills the entries of its local atoms, the others stay 0, and the arrays are summed over the
+ * ranks (NaN + 0 stays NaN): the same on every rank.  Collective.  -1 and nothing launched without device state, without a reference or for rCut above the
+ * force cutoff. */
+int comdAtomStrain(SimFlat* s, double rCut, double* strainByGid7, int* countByGid);
+/* not in the reference: out9 = {atoms, invalid atoms, mean gamma, max gamma, the gid that holds it (the lowest of equals, -1 without a valid atom), mean
+ * tr E / 3, mean D^2, max D^2, atoms with gamma >= threshold} of the current state, gamma the shear invariant of E (computeAtomStrainSummary, comd_hip.h);
+ * means and extremes over the valid atoms (0 without any).  Reduced on the device and then over the ranks.  The same on every rank.  Collective.  -1 as
+ * comdAtomStrain, or for a threshold that is not > 0. */
+int comdStrainSummary(SimFlat* s, double rCut, double threshold, double* out9);
 /* not in the reference (its box is nx lat for the whole run): box deformation, LAMMPS's `fix deform ... remap x`.
  * comdSetBox: the global box becomes L[3] Angstroms (the origin stays at 0) and the positions of the local atoms are scaled with it, L_new / L_old per axis, by
  *    comdRemapBoxGpu.  Every copy of the geometry follows: Domain (the expressions of initDecomposition, so neighbouring ranks agree bit for bit on their shared
@@ -455,7 +491,7 @@ void ensureInteriorForceLaunched(SimFlat* sim);
 
 /* ---- performanceTimers.h ---- */
 enum TimerHandle { totalTimer, loopTimer, timestepTimer, positionTimer, velocityTimer, redistributeTimer, atomHaloTimer,
-                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, cspTimer, cnaTimer, deformTimer, stressTimer, numberOfTimers };
+                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, cspTimer, cnaTimer, deformTimer, stressTimer, strainTimer, numberOfTimers };
 void profileStart(enum TimerHandle handle);
 void profileStop(enum TimerHandle handle);
 double getElapsedTime(enum TimerHandle handle);

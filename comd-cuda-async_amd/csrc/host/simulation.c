@@ -175,6 +175,18 @@ SimFlat* initSimulationHost(Command cmd)
    if (!(cmd.stressDumpMin >= 0.0)) { printf("Error: --stressDumpMin must be >= 0 GPa (got %g).\n", cmd.stressDumpMin); exit(-1); }
    sim->stress = cmd.stress; sim->stressDumpMin = cmd.stressDumpMin;
    strcpy(sim->stressFile, cmd.stressFile); strcpy(sim->stressDump, cmd.stressDump);
+   /* --strain (not in the reference): the reference is a global step of this run; the radius cannot exceed the force cutoff (the 27-cell walk of the kernel sees
+    * no further) and defaults to that of --cspCoord; the thresholds are shear strains */
+   if (cmd.strainRef < 0 || cmd.strainRef > cmd.nSteps) { printf("Error: --strainRef must lie in 0..nSteps = 0..%d (got %d).\n", cmd.nSteps, cmd.strainRef); exit(-1); }
+   if (cmd.strainCutoffSet && !(cmd.strainCutoff > 0.0 && cmd.strainCutoff <= sim->pot->cutoff)) {
+      printf("Error: --strainCutoff must lie in (0, the force cutoff of %g Angstroms] (got %g).\n", (double)sim->pot->cutoff, cmd.strainCutoff); exit(-1);
+   }
+   if (!(cmd.strainThreshold > 0.0)) { printf("Error: --strainThreshold must be > 0 (got %g).\n", cmd.strainThreshold); exit(-1); }
+   if (!(cmd.strainDumpMin >= 0.0)) { printf("Error: --strainDumpMin must be >= 0 (got %g).\n", cmd.strainDumpMin); exit(-1); }
+   sim->strain = cmd.strain; sim->strainRef = cmd.strainRef;
+   sim->strainCutoff = cmd.strainCutoffSet ? cmd.strainCutoff : comdDefaultCoordRadius(sim);
+   sim->strainThreshold = cmd.strainThreshold; sim->strainDumpMin = cmd.strainDumpMin;
+   strcpy(sim->strainFile, cmd.strainFile); strcpy(sim->strainDump, cmd.strainDump);
    /* --erateX/Y/Z (not in the reference): the box strains at constant engineering rates; profile mode never redistributes, which the remap needs */
    for (int a = 0; a < 3; ++a) if (!(fabs(cmd.erate[a]) < 1e300)) { printf("Error: --erate%c must be a finite rate in 1/ps (got %g).\n", 'X' + a, cmd.erate[a]); exit(-1); }
    sim->deform = cmd.erate[0] != 0.0 || cmd.erate[1] != 0.0 || cmd.erate[2] != 0.0;
@@ -290,6 +302,7 @@ void destroySimulation(SimFlat** ps)
    free(s->cnaRows); free(s->cnaLast); free(s->cnaStage);
    free(s->deformRows);
    free(s->stressRows); free(s->stressStage);
+   free(s->strainRows); free(s->strainStage);
    free(s->species); free(s->domain); free(s);
    *ps = NULL;
 }
@@ -313,9 +326,10 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
       s->firstPrint = 0;
       fprintf(screenOut,
               "#                                                                                         Performance\n"
-              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms%s%s%s%s%s%s\n",
+              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms%s%s%s%s%s%s%s\n",
               s->pressure ? "    Pressure(GPa)" : "", s->msd ? "         MSD(A^2)" : "", s->csp ? "      Defects" : "", s->cna ? "       NonFCC" : "",
-              s->deformReport ? "           V/V0         Sxx(GPa)" : "", s->stress ? "       MaxVM(GPa)" : "");
+              s->deformReport ? "           V/V0         Sxx(GPa)" : "", s->stress ? "       MaxVM(GPa)" : "",
+              s->strain ? "         MaxShear" : "");
       fflush(screenOut);
    }
    real_t time = iStep * s->dt;
@@ -332,6 +346,7 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
    if (s->cna) fprintf(screenOut, " %12lld", s->cnaNonFccNow);
    if (s->deformReport) fprintf(screenOut, " %14.10f %16.10f", (double)s->V / (s->box0[0] * s->box0[1] * s->box0[2]), -((double)s->K[0] + s->W[0]) / s->V * eVperA3inGPa);
    if (s->stress) fprintf(screenOut, " %16.10f", s->stressMaxVmNow * eVperA3inGPa);
+   if (s->strain) fprintf(screenOut, " %16.10f", s->strainMaxShearNow);
    fprintf(screenOut, "\n");
 }
 
@@ -716,6 +731,101 @@ static void writeStress(FILE* yaml, SimFlat* s, int iStep)
    fflush(yaml);
 }
 
+/* --strain: the state at the end of global step strainRef becomes the reference */
+static void startStrain(SimFlat* s)
+{
+   const int rc = comdStrainReference(s, 1);
+   if (rc < 0) { printf("Error: --strain needs the device state.\n"); exit(-1); }
+   if (rc > 0) { printf("Error: --strain: no device memory for the reference positions of %d atoms.\n", s->atoms->nGlobal); exit(-1); }
+}
+
+/* --strain: one more row {step, atoms, invalid atoms, mean / max shear strain, the gid of the max, mean volumetric strain, mean / max D^2min, atoms at or above
+ * the threshold} from the device reduction */
+static void sampleStrain(SimFlat* s, int iStep)
+{
+   if (s->strainSamples == s->strainCap) { s->strainCap = s->strainCap ? 2 * s->strainCap : 64; s->strainRows = (double*)realloc(s->strainRows, (size_t)s->strainCap * 10 * sizeof(double)); }
+   double* row = s->strainRows + 10 * (size_t)s->strainSamples++;
+   row[0] = (double)iStep;
+   if (comdStrainSummary(s, s->strainCutoff, s->strainThreshold, row + 1) != 0) { printf("Error: --strain needs the device state and a reference.\n"); exit(-1); }
+   s->strainMaxShearNow = row[4];
+}
+
+static double shearOf(const double* e)
+{
+   const double d0 = e[0] - e[1], d1 = e[1] - e[2], d2 = e[2] - e[0];
+   return sqrt(((e[3] * e[3] + e[4] * e[4]) + e[5] * e[5]) + ((d0 * d0 + d1 * d1) + d2 * d2) / 6.0);
+}
+
+/* --strain: the file: a header line, then the rows of sampleStrain.  --strainDump: the tensors of the last step as extended XYZ, Cu x y z exx eyy ezz eyz exz
+ * exy shear vol d2min n gid, the atoms whose shear strain is at least --strainDumpMin (0: all atoms, the invalid ones with their NaNs included); the positions
+ * gathered by gid over the ranks as the tensors are.  The YAML block names the file and gives the last sample. */
+static void writeStrain(FILE* yaml, SimFlat* s, int iStep)
+{
+   const size_t n = (size_t)s->atoms->nGlobal;
+   double *pos = NULL, *ten = NULL;
+   int* cnt = NULL;
+   if (s->strainDump[0]) {          /* collective: before the other ranks leave */
+      double* mine = (double*)calloc(n ? 3 * n : 1, sizeof(double));
+      pos = (double*)malloc((n ? 3 * n : 1) * sizeof(double));
+      ten = (double*)malloc((n ? 7 * n : 1) * sizeof(double));
+      cnt = (int*)malloc((n ? n : 1) * sizeof(int));
+      comdGatherByGid(s, 0, mine);
+      const size_t chunk = (size_t)1 << 28;
+      for (size_t o = 0; o < 3 * n; o += chunk) addDoubleParallel(mine + o, pos + o, (int)(3 * n - o < chunk ? 3 * n - o : chunk));
+      free(mine);
+      if (comdAtomStrain(s, s->strainCutoff, ten, cnt) != 0) { printf("Error: --strainDump needs the device state and a reference.\n"); exit(-1); }
+   }
+   if (!printRank()) { free(pos); free(ten); free(cnt); return; }
+   const int samples = s->strainSamples;
+   FILE* f = fopen(s->strainFile, "w");
+   if (!f) { printf("Error: cannot write %s\n", s->strainFile); exit(-1); }
+   fprintf(f, "# Strain: N %d L0 %.17g %.17g %.17g reference step %d cutoff %.17g A threshold %.17g samples %d | columns: step, mean / max shear strain, "
+              "gid of the max, mean volumetric strain, mean / max D2min (A^2), atoms at or above the threshold, invalid atoms\n",
+           s->atoms->nGlobal, s->strainL0[0], s->strainL0[1], s->strainL0[2], s->strainRef, s->strainCutoff, s->strainThreshold, samples);
+   const double* last = NULL;
+   for (int k = 0; k < samples; ++k) {
+      last = s->strainRows + 10 * (size_t)k;
+      fprintf(f, "%.0f %.17g %.17g %.0f %.17g %.17g %.17g %.0f %.0f\n", last[0], last[3], last[4], last[5], last[6], last[7], last[8], last[9], last[2]);
+   }
+   fclose(f);
+   if (pos && ten) {
+      f = fopen(s->strainDump, "w");
+      if (!f) { printf("Error: cannot write %s\n", s->strainDump); exit(-1); }
+      const real_t* L = s->domain->globalExtent;
+      const int all = !(s->strainDumpMin > 0.0);
+      size_t kept = 0;
+      for (size_t g = 0; g < n; ++g) if (all || shearOf(ten + 7 * g) >= s->strainDumpMin) kept++;
+      fprintf(f, "%zu\n", kept);
+      fprintf(f, "Lattice=\"%.17g 0 0 0 %.17g 0 0 0 %.17g\" Properties=species:S:1:pos:R:3:strain:R:6:shear:R:1:vol:R:1:d2min:R:1:n:I:1:gid:I:1 step=%d "
+                 "referenceStep=%d cutoff=%.17g minShear=%.17g\n", (double)L[0], (double)L[1], (double)L[2], iStep, s->strainRef, s->strainCutoff, s->strainDumpMin);
+      for (size_t g = 0; g < n; ++g) {
+         const double* t = ten + 7 * g;
+         const double shear = shearOf(t);
+         if (all || shear >= s->strainDumpMin)
+            fprintf(f, "Cu %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %d %zu\n", pos[3 * g], pos[3 * g + 1], pos[3 * g + 2],
+                    t[0], t[1], t[2], t[3], t[4], t[5], shear, ((t[0] + t[1]) + t[2]) / 3.0, t[6], cnt[g], g);
+      }
+      fclose(f);
+   }
+   free(pos); free(ten); free(cnt);
+   if (!yaml) return;
+   fprintf(yaml, "Strain:\n");
+   fprintf(yaml, "  referenceStep: %d\n", s->strainRef);
+   fprintf(yaml, "  cutoff: %.12e\n", s->strainCutoff);
+   fprintf(yaml, "  threshold: %.12e\n", s->strainThreshold);
+   fprintf(yaml, "  samples: %d\n", samples);
+   fprintf(yaml, "  file: %s\n", s->strainFile);
+   fprintf(yaml, "  finalMeanShear: %.12e\n", last ? last[3] : 0.0);
+   fprintf(yaml, "  finalMaxShear: %.12e\n", last ? last[4] : 0.0);
+   fprintf(yaml, "  finalMeanVolumetric: %.12e\n", last ? last[6] : 0.0);
+   fprintf(yaml, "  finalMeanD2min: %.12e\n", last ? last[7] : 0.0);
+   fprintf(yaml, "  finalMaxD2min: %.12e\n", last ? last[8] : 0.0);
+   fprintf(yaml, "  finalAboveThreshold: %.0f\n", last ? last[9] : 0.0);
+   fprintf(yaml, "  finalInvalid: %.0f\n", last ? last[2] : 0.0);
+   fprintf(yaml, "\n");
+   fflush(yaml);
+}
+
 Validate* initValidate(SimFlat* sim)
 {
    sumAtoms(sim);
@@ -819,12 +929,22 @@ int comdMain(int argc, char** argv)
       if (sim->csp) { startTimer(cspTimer); sampleCsp(sim, iStep); stopTimer(cspTimer); }
       if (sim->cna) { startTimer(cnaTimer); sampleCna(sim, iStep); stopTimer(cnaTimer); }
       if (sim->stress) { startTimer(stressTimer); sampleStress(sim, iStep); stopTimer(stressTimer); }
+      if (sim->strain && iStep >= sim->strainRef) { startTimer(strainTimer); if (iStep == sim->strainRef) startStrain(sim); sampleStrain(sim, iStep); stopTimer(strainTimer); }
       printThings(sim, iStep, getElapsedTime(timestepTimer));
       /* --msdStart between two printed steps: the interval is taken as two timestep() calls (which give the bits of one) with the origin in between */
       const int toOrigin = sim->msd && sim->msdStart > iStep && sim->msdStart < iStep + printRate ? sim->msdStart - iStep : 0;
+      /* --strainRef between two printed steps: the same, the reference taken in between */
+      const int toRef = sim->strain && sim->strainRef > iStep && sim->strainRef < iStep + printRate ? sim->strainRef - iStep : 0;
       startTimer(timestepTimer);
-      if (toOrigin) { timestep(sim, toOrigin, sim->dt); startMsd(sim); }
-      timestep(sim, printRate - toOrigin, sim->dt);
+      for (int done = 0; done < printRate;) {
+         int next = printRate;
+         if (toOrigin > done && toOrigin < next) next = toOrigin;
+         if (toRef > done && toRef < next) next = toRef;
+         timestep(sim, next - done, sim->dt);
+         done = next;
+         if (done == toOrigin) startMsd(sim);
+         if (done == toRef) startStrain(sim);
+      }
       stopTimer(timestepTimer);
       iStep += printRate;
    }
@@ -837,6 +957,7 @@ int comdMain(int argc, char** argv)
    if (sim->csp) { startTimer(cspTimer); sampleCsp(sim, iStep); stopTimer(cspTimer); }
    if (sim->cna) { startTimer(cnaTimer); sampleCna(sim, iStep); stopTimer(cnaTimer); }
    if (sim->stress) { startTimer(stressTimer); sampleStress(sim, iStep); stopTimer(stressTimer); }
+   if (sim->strain && iStep >= sim->strainRef) { startTimer(strainTimer); if (iStep == sim->strainRef) startStrain(sim); sampleStrain(sim, iStep); stopTimer(strainTimer); }
    printThings(sim, iStep, getElapsedTime(timestepTimer));
    timestampBarrier("Ending simulation\n");
    if (sim->pressure) printPressureYaml(yamlFile, sim);
@@ -846,6 +967,7 @@ int comdMain(int argc, char** argv)
    if (sim->cna) writeCna(yamlFile, sim);
    if (sim->deformReport) writeDeform(yamlFile, sim);
    if (sim->stress) { startTimer(stressTimer); writeStress(yamlFile, sim, iStep); stopTimer(stressTimer); }
+   if (sim->strain) { startTimer(strainTimer); writeStrain(yamlFile, sim, iStep); stopTimer(strainTimer); }
 
    validateResult(validate, sim);
    profileStop(totalTimer);

@@ -383,6 +383,120 @@ int comdStressSummary(SimFlat* s, int withKinetic, double* out7)
    return 0;
 }
 
+/* ---- per-atom strain and D^2min (not in the reference; comd_host.h) ---- */
+int comdStrainReference(SimFlat* s, int on)
+{
+   if (!s->gpu.boxes.nAtoms) return -1;
+   const int nGlobal = s->atoms->nGlobal;
+   int fail = comdStrainReferenceGpu(&s->gpu, nGlobal, on), anyFail = 0;
+   maxIntParallel(&fail, &anyFail, 1);
+   if (anyFail && !fail) comdStrainReferenceGpu(&s->gpu, nGlobal, 0);      /* all ranks or none */
+   s->strainHasRef = on != 0 && !anyFail;
+   if (!s->strainHasRef) return anyFail;
+   for (int a = 0; a < 3; ++a) s->strainL0[a] = s->gpu.strainL0[a] = (double)s->domain->globalExtent[a];
+   if (getNRanks() > 1) {
+      /* halo neighbours need the records of the other ranks' atoms: every other rank holds 0 for a gid; in chunks whose count fits addDoubleParallel's int */
+      const size_t n = 4 * (size_t)nGlobal, chunk = (size_t)1 << 28;
+      double* mine = (double*)malloc(2 * n * sizeof(double));
+      double* all = mine + n;
+      comdMemcpyDtoH(mine, s->gpu.strainRefBuf, (long)(n * sizeof(double)));
+      startTimer(commReduceTimer);
+      for (size_t o = 0; o < n; o += chunk) addDoubleParallel(mine + o, all + o, (int)(n - o < chunk ? n - o : chunk));
+      stopTimer(commReduceTimer);
+      comdMemcpyHtoD(s->gpu.strainRefBuf, all, (long)(n * sizeof(double)));
+      free(mine);
+   }
+   return 0;
+}
+
+int comdStrainReferenceBox(SimFlat* s, double* L0)
+{
+   if (!s->strainHasRef) return -1;
+   for (int a = 0; a < 3; ++a) L0[a] = s->strainL0[a];
+   return 0;
+}
+
+/* the radius the two entries launch with: the default for rCut <= 0; 0 when the entry has to refuse */
+static double strainRadius(SimFlat* s, double rCut)
+{
+   if (!s->gpu.boxes.nAtoms || !s->strainHasRef) return 0.0;
+   if (rCut <= 0.0) rCut = comdDefaultCoordRadius(s);
+   return rCut <= s->pot->cutoff ? rCut : 0.0;
+}
+
+int comdAtomStrain(SimFlat* s, double rCut, double* strainByGid7, int* countByGid)
+{
+   rCut = strainRadius(s, rCut);
+   if (!(rCut > 0.0)) return -1;
+   const int cap = s->boxes->maxAtoms, nLocalBoxes = s->boxes->nLocalBoxes;
+   const size_t nSlots = (size_t)nLocalBoxes * cap, n = (size_t)s->atoms->nGlobal;
+   /* staging for the by-slot planes, kept with the simulation as comdCentroSymmetry's */
+   const size_t need = (7 * nSlots + 1) * sizeof(real_t) + (2 * (nSlots + 1) + (size_t)nLocalBoxes + 1) * sizeof(int);
+   if (need > s->strainStageBytes) { free(s->strainStage); s->strainStage = malloc(need); s->strainStageBytes = need; }
+   real_t* planes = (real_t*)s->strainStage;
+   int* count = (int*)(planes + 7 * nSlots + 1);
+   int* gid = count + nSlots + 1;
+   int* nAtoms = gid + nSlots + 1;
+   computeAtomStrain(&s->gpu, (real_t)rCut, planes, count);          /* blocks: the stream is drained, the two copies below see the same state */
+   comdMemcpyDtoH(gid, s->gpu.atoms.gid, (long)(nSlots * sizeof(int)));
+   comdMemcpyDtoH(nAtoms, s->gpu.boxes.nAtoms, (long)((size_t)nLocalBoxes * sizeof(int)));
+   const int one = getNRanks() == 1;
+   double* mine = one ? strainByGid7 : (double*)malloc((n ? 7 * n : 1) * sizeof(double));
+   int* mineN = one ? countByGid : (int*)malloc((n ? n : 1) * sizeof(int));
+   memset(mine, 0, 7 * n * sizeof(double));
+   memset(mineN, 0, n * sizeof(int));
+   for (int b = 0; b < nLocalBoxes; ++b)
+      for (size_t o = (size_t)b * cap, e = o + (size_t)nAtoms[b]; o < e; ++o) {
+         const size_t g = (size_t)gid[o];
+         if (g < n) { for (int c = 0; c < 7; ++c) mine[7 * g + c] = (double)planes[(size_t)c * nSlots + o]; mineN[g] = count[o]; }
+      }
+   if (!one) {
+      /* every other rank holds 0 for a gid (and NaN + 0 = NaN, an invalid atom stays one); in chunks whose count fits the int of the sums */
+      const size_t chunk = (size_t)1 << 28;
+      startTimer(commReduceTimer);
+      for (size_t o = 0; o < 7 * n; o += chunk) addDoubleParallel(mine + o, strainByGid7 + o, (int)(7 * n - o < chunk ? 7 * n - o : chunk));
+      for (size_t o = 0; o < n; o += chunk) addIntParallel(mineN + o, countByGid + o, (int)(n - o < chunk ? n - o : chunk));
+      stopTimer(commReduceTimer);
+      free(mine); free(mineN);
+   }
+   return 0;
+}
+
+int comdStrainSummary(SimFlat* s, double rCut, double threshold, double* out9)
+{
+   rCut = strainRadius(s, rCut);
+   if (!(rCut > 0.0) || !(threshold > 0.0)) return -1;
+   double local[9];          /* sum gamma, max gamma, gid, sum vol, sum D^2, max D^2, valid, invalid, above (computeAtomStrainSummary) */
+   computeAtomStrain(&s->gpu, (real_t)rCut, NULL, NULL);
+   computeAtomStrainSummary(&s->gpu, threshold, local);
+   const int nRanks = getNRanks(), me = getMyRank();
+   if (nRanks > 1) {
+      /* the sums add; the extremes and the gid go through one slot per rank of a summed vector (no MAX of doubles in the transport), taken in rank order */
+      double* mine = (double*)calloc(2 * (size_t)(6 + 3 * nRanks), sizeof(double));
+      double* all = mine + 6 + 3 * (size_t)nRanks;
+      mine[0] = local[0]; mine[1] = local[3]; mine[2] = local[4]; mine[3] = local[6]; mine[4] = local[7]; mine[5] = local[8];
+      if (local[6] > 0.0) { double* slot = mine + 6 + 3 * (size_t)me; slot[0] = local[1]; slot[1] = local[2] + 1.0; slot[2] = local[5]; }
+      startTimer(commReduceTimer);
+      addDoubleParallel(mine, all, 6 + 3 * nRanks);
+      stopTimer(commReduceTimer);
+      local[0] = all[0]; local[3] = all[1]; local[4] = all[2]; local[6] = all[3]; local[7] = all[4]; local[8] = all[5];
+      local[1] = -INFINITY; local[2] = -1.0; local[5] = -INFINITY;
+      for (int r = 0; r < nRanks; ++r) {
+         const double* slot = all + 6 + 3 * (size_t)r;
+         if (slot[1] == 0.0) continue;          /* a rank without valid atoms */
+         const double g = slot[1] - 1.0;
+         if (local[2] < 0.0 || slot[0] > local[1] || (slot[0] == local[1] && g < local[2])) { local[1] = slot[0]; local[2] = g; }
+         if (slot[2] > local[5]) local[5] = slot[2];
+      }
+      free(mine);
+   }
+   const double N = local[6];
+   out9[0] = N + local[7]; out9[1] = local[7];
+   out9[2] = N > 0.0 ? local[0] / N : 0.0; out9[3] = N > 0.0 ? local[1] : 0.0; out9[4] = local[2];
+   out9[5] = N > 0.0 ? local[3] / N : 0.0; out9[6] = N > 0.0 ? local[4] / N : 0.0; out9[7] = N > 0.0 ? local[5] : 0.0; out9[8] = local[8];
+   return 0;
+}
+
 /* ---- displacement tracking (not in the reference; comd_host.h) ---- */
 int comdTrackDisplacement(SimFlat* s, int on)
 {

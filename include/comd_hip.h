@@ -250,6 +250,12 @@ typedef struct SimGpuSt {
    double       cellVolume0;           /* host: volume of a link cell at AllocateGpu, in A^3: the occupancy estimates behind row, image and LDS sizes keep it when comdRemapBoxGpu changes the box */
    real_t*      stressBuf;             /* device [6][nLocalBoxes*maxAtoms]: the planes xx yy zz yz xz xy of computeAtomStress, allocated by its first call */
    double*      stressSumBuf;          /* device: the workgroups' rows for computeAtomStressSummary, allocated with stressBuf */
+   double*      strainRefBuf;          /* device [strainRefN][4]: the reference positions by gid of comdStrainReferenceGpu, all ranks' atoms, NULL = no reference */
+   int          strainRefN;            /* records strainRefBuf holds = nGlobal */
+   double       strainL0[3];           /* host: the global box when the reference was taken, in A; the host library sets it with the table */
+   real_t*      strainBuf;             /* device [7][nLocalBoxes*maxAtoms]: the planes E xx yy zz yz xz xy and D^2 of computeAtomStrain, allocated by its first call */
+   int*         strainCountBuf;        /* device [nLocalBoxes*maxAtoms]: its neighbour counts, allocated with strainBuf */
+   double*      strainSumBuf;          /* device: the workgroups' rows for computeAtomStrainSummary, allocated with strainBuf */
 } SimGpu;
 
 /* Everything AllocateGpu needs to know about the rank's geometry and potential.
@@ -505,6 +511,30 @@ void computeAtomStress(SimGpu* sim, int withKinetic, real_t* outBySlot6);
  * Seven doubles are copied, never the planes.  Same stream; deterministic two-stage reduction.  A call without a computeAtomStress before it ends the run.
  * Blocks until the result is on the host. */
 void computeAtomStressSummary(SimGpu* sim, double atomVolume, double* out);
+/* Not in the reference (CoMD has no strain output): the reference snapshot of the per-atom strain (hip/strain_kernels.h).  on != 0: allocate and zero one
+ * 32-byte record {x, y, z, spare} of doubles (in both precision builds) per global atom id and store the current position of every one of THIS rank's local
+ * atoms at its gid, with plain vector stores (already on: the table is zeroed and filled again).  Halo neighbours need the records of other ranks' atoms: with
+ * several ranks the host adds the ranks' tables (every other rank holds 0 for a gid) and copies the sum back into sim->strainRefBuf; it also sets
+ * sim->strainL0 to the box of that moment.  on == 0: the table and the planes of computeAtomStrain are freed.  Returns non-zero, with a message and no
+ * reference, when the device cannot give the memory.  Blocks. */
+int comdStrainReferenceGpu(SimGpu* sim, int nGlobal, int on);
+/* Not in the reference: the Green-Lagrange strain and the non-affine displacement D^2min (Falk and Langer) of every one of THIS rank's local atoms against
+ * the reference table.  For the atom in local slot o = cell * maxAtoms + index, with its neighbours j (local or halo image) at 0 < |d|^2 <= rCut^2 in the
+ * CURRENT configuration, d = x_j - x_i, and d0 = x0[gid_j] - x0[gid_i] reduced per axis to the minimum image of strainL0:
+ *   V = sum d0 d0^T, A = sum d d0^T, S = sum |d|^2 (doubles in both builds), F = A V^-1, E = 1/2 (F^T F - I), D^2 = max(0, S - F:A) = sum |d - F d0|^2.
+ * outBySlot7[c * nLocalBoxes * maxAtoms + o]: c = 0..5 E xx yy zz yz xz xy, c = 6 D^2 in A^2; outCountBySlot[o]: the neighbours n.  An atom with n < 3 or
+ * det V <= 1e-9 (tr V / 3)^3 has NaN in all seven planes and its n.  Entries of empty slots mean nothing.  NULL output pointers: the planes stay on the device
+ * for computeAtomStrainSummary, nothing is copied.  0 < rCut <= the force cutoff (anything else ends the run: the 27-cell walk sees no further), any method.
+ * Same stream as computeAtomStress; no atomics, bit-reproducible; reads r, gid, the table and the cell tables, writes only its own planes (allocated by
+ * the first call, freed by DestroyGpu and with the reference).  A call without a reference ends the run.  Blocks. */
+void computeAtomStrain(SimGpu* sim, real_t rCut, real_t* outBySlot7, int* outCountBySlot);
+/* Not in the reference: the printed-step figures of the planes the last computeAtomStrain call left on the device, formed in double: the shear invariant
+ * gamma = sqrt(E_yz^2 + E_xz^2 + E_xy^2 + [(E_xx - E_yy)^2 + (E_yy - E_zz)^2 + (E_zz - E_xx)^2] / 6) and the volumetric strain tr E / 3.
+ *   out[0] sum of gamma, out[1] max gamma, out[2] the gid that holds it (the lowest one of equals; -1 without a valid atom), out[3] sum of tr E / 3,
+ *   out[4] sum of D^2, out[5] max D^2, out[6] valid atoms, out[7] invalid atoms (left out of the sums and extremes), out[8] atoms with gamma >= threshold
+ * -- over THIS rank's atoms; without valid atoms the extremes are -inf.  Nine doubles are copied, never the planes.  Deterministic two-stage reduction.
+ * A call without a computeAtomStrain before it ends the run.  Blocks until the result is on the host. */
+void computeAtomStrainSummary(SimGpu* sim, double threshold, double* out);
 /* Not in the reference: unwrapped displacements since an origin, for the mean-squared displacement (hip/msd_kernels.h).  on != 0: allocate and zero
  * one 32-byte record {dx, dy, dz, spare} per global atom id, signed 64-bit fixed point in units of 2^-32 Angstroms; from then on the drift kernels
  * of this simulation (advancePositionGpu and the fused forms, plain and Langevin) add dt p/m of every local atom into the record of its gid.  Already
