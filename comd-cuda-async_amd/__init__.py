@@ -647,7 +647,8 @@ class Simulation:
         """{"n", "invalid", "mean_shear", "max_shear", "max_shear_gid", "mean_volumetric", "mean_d2min", "max_d2min", "above_threshold"}: the figures of
         shear_strain(), volumetric_strain() and d2min, reduced on the device (computeAtomStrainSummary: the per-atom planes never leave it) and over the
         ranks.  Invalid atoms are counted and left out of means and extremes; the gid is the lowest one that holds the maximum; above_threshold counts
-        the atoms with a shear strain >= threshold (None: 0.1).  ValueError as atomic_strain, or for a threshold that is not > 0."""
+        the atoms with a shear strain >= threshold (None: 0.1).  With no valid atom at all (a gas: every atom has fewer than 3 neighbours) invalid == n, the means
+        and extremes are 0 and max_shear_gid is -1: that is what comdStrainSummary writes for N = 0.  ValueError as atomic_strain, or for a threshold that is not > 0."""
         r = self._strain_cutoff("strain_summary", cutoff)
         if threshold is not None and not float(threshold) > 0.0:
             raise ValueError(f"strain_summary: need threshold > 0 (got {threshold})")

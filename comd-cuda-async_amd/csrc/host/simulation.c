@@ -148,6 +148,14 @@ SimFlat* initSimulationHost(Command cmd)
    if (sim->spline) eamUseSplines(sim->pot);
    /* --rdf (not in the reference): the range defaults to the force cutoff and cannot exceed it (the 27-cell walk of the histogram kernel sees no further) */
    if (cmd.rdf < 0 || cmd.rdf > COMD_RDF_MAX_BINS) { printf("Error: --rdf takes 0 (off) to %d bins (got %d).\n", COMD_RDF_MAX_BINS, cmd.rdf); exit(-1); }
+   /* a radius given in decimal that names the force cutoff is the force cutoff: an EAM cutoff comes out of the table arithmetic a few ulps off the decimal of the
+    * file (Cu_u6.eam: 4.949999999999989 for 4.95), and the float build holds it rounded to real_t */
+   {
+      const double cutoff = (double)sim->pot->cutoff, slack = 64.0 * (sizeof(real_t) == sizeof(float) ? 1.1920929e-7 : 2.220446049250313e-16) * cutoff;
+      if (cmd.rdfMax > cutoff && cmd.rdfMax <= cutoff + slack) cmd.rdfMax = cutoff;
+      if (cmd.cspCoord > cutoff && cmd.cspCoord <= cutoff + slack) cmd.cspCoord = cutoff;
+      if (cmd.strainCutoff > cutoff && cmd.strainCutoff <= cutoff + slack) cmd.strainCutoff = cutoff;
+   }
    if (cmd.rdf && cmd.rdfMax > sim->pot->cutoff) { printf("Error: --rdfMax must not exceed the force cutoff of %g Angstroms (got %g).\n", (double)sim->pot->cutoff, cmd.rdfMax); exit(-1); }
    sim->rdfBins = cmd.rdf; sim->rdfMax = cmd.rdfMax > 0.0 ? cmd.rdfMax : (double)sim->pot->cutoff;
    strcpy(sim->rdfFile, cmd.rdfFile);

@@ -1,9 +1,10 @@
 """Worker of tests/test_atom_stress.py::test_ranks_give_the_one_rank_array: one rank of a multi-process run on the shared device.
 
-    python stress_worker.py <rank> <world> <port> <px> <py> <pz> <output directory> <json list of CLI flags>
+    python stress_worker.py <rank> <world> <port> <px> <py> <pz> <output directory> <json list of CLI flags> [<kinetic: 1 (default) or 0>]
 
 Every rank drives the HIP path on device 0 with the gloo transport (as tests/pressure_worker.py does) and saves the global array
-Simulation.atomic_stress() returns at step 0 as <output directory>/stress_rank<rank>.npy, and the summary as stress_rank<rank>.json.
+Simulation.atomic_stress() returns at step 0 as <output directory>/stress_rank<rank>.npy, and the summary as stress_rank<rank>.json; with kinetic 0
+both leave out the kinetic term (tests/test_analysis_regimes.py: a gas without pairs, where every von Mises stress is then 0 on every rank).
 """
 import json
 import os
@@ -20,6 +21,7 @@ def main():
     grid = [int(v) for v in sys.argv[4:7]]
     out_dir = sys.argv[7]
     args = json.loads(sys.argv[8]) + ["-i", grid[0], "-j", grid[1], "-k", grid[2]]
+    kinetic = len(sys.argv) < 10 or sys.argv[9] != "0"
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=port, RANK=str(rank), WORLD_SIZE=str(world))
     import torch.distributed as dist
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -28,9 +30,9 @@ def main():
     transport = pkg.GlooTransport(dist)
     pkg.init_parallel(rank, world, transport.struct)
     sim = pkg.Simulation(args)
-    np.save(os.path.join(out_dir, f"stress_rank{rank}.npy"), sim.atomic_stress())
+    np.save(os.path.join(out_dir, f"stress_rank{rank}.npy"), sim.atomic_stress(kinetic=kinetic))
     with open(os.path.join(out_dir, f"stress_rank{rank}.json"), "w") as f:
-        json.dump(sim.stress_summary(), f)
+        json.dump(sim.stress_summary(kinetic=kinetic), f)
     print("STRESS saved")
     sys.stdout.flush()
     sim.close()

@@ -14,6 +14,7 @@ import sys
 import numpy as np
 import pytest
 
+from test_analysis_regimes import GPU_CASE_COUNT as ANALYSIS_REGIMES_GPU_CASE_COUNT
 from test_capacities import GPU_CASE_COUNT
 from test_kernel_legs import FAMILY_LEG_COUNT
 from test_two_cell_boxes import GPU_CASE_COUNT as TWO_CELL_GPU_CASE_COUNT
@@ -93,6 +94,17 @@ def test_single_precision_two_cell_boxes():
     out = _run(["tests/test_two_cell_boxes.py"], None, "gpu", 900)
     passed = re.search(r"(\d+) passed", out)
     assert passed and int(passed.group(1)) == TWO_CELL_GPU_CASE_COUNT and "skipped" not in out and "failed" not in out, out[-1500:]
+
+
+@pytest.mark.gpu
+def test_single_precision_analysis_regimes():
+    """tests/test_analysis_regimes.py in the float build: the virial, g(r), CSP, CNA, per-atom stress and strain in the void, sparse, dilute and dense regimes, the layouts,
+    the message halo, two ranks, the executable and the singular strain reference, each under its module's float rule.  Its CPU tests assert the regimes' figures and the float
+    caps on the float checker first (and name the legs whose reference alone exceeds a cap); none skipped."""
+    _run(["tests/test_analysis_regimes.py"], None, "not gpu", 900)
+    out = _run(["tests/test_analysis_regimes.py"], None, "gpu", 900)
+    passed = re.search(r"(\d+) passed", out)
+    assert passed and int(passed.group(1)) == ANALYSIS_REGIMES_GPU_CASE_COUNT and "skipped" not in out and "failed" not in out, out[-1500:]
 
 
 SPLINE_CASE = r"""
