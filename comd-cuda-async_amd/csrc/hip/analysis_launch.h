@@ -1,0 +1,315 @@
+// analysis_launch.h -- the launch layer of the analyses, computeVirial ... comdCopyDisplacementsGpu (comd_hip.h): none of them is in the reference.  Host code,
+// part of comd_device.hip's translation unit (it uses HIP_CHECK, LAUNCH_CHECK, S, dalloc, allowDynamicLds, ceilDiv, makeLjArgs and ljTableView of that file).
+#pragma once
+
+// The entry points of the chunk walk (stencil_walk.h) share their prologue and the fields of the walk.
+// They run on the boundary stream; -a 1: the interior cells' force work is done first
+static hipStream_t analysisStream(SimGpu* sim)
+{
+   if (sim->interior_stream) HIP_CHECK(hipStreamSynchronize(S(sim->interior_stream)));
+   return S(sim->boundary_stream);
+}
+
+static void fillStencilArgs(StencilArgs& v, const SimGpu* sim)
+{
+   v.rx = sim->atoms.r.x; v.ry = sim->atoms.r.y; v.rz = sim->atoms.r.z;
+   v.nAtoms = sim->boxes.nAtoms; v.nbr = sim->neighbor_cells;
+   v.nLocalBoxes = sim->boxes.nLocalBoxes; v.cap = sim->maxAtoms; v.chunks = ceilDiv(sim->maxAtoms, WAVE);
+}
+
+// the slots of the local cells: the length of a by-slot plane
+static size_t localSlots(const SimGpu* sim) { return (size_t)sim->boxes.nLocalBoxes * sim->maxAtoms; }
+
+// the cutoff of the potential: the largest radius the 27-cell walk is good for
+static real_t pairCutoff(const SimGpu* sim) { return sim->do_eam ? sim->eam_pot.cutoff : sim->lj_pot.cutoff; }
+
+// the kernels of nearest12_walk.h compute slots in int
+static void refuseSlotsBeyondInt(const SimGpu* sim, const char* who)
+{
+   if ((double)sim->boxes.nTotalBoxes * sim->maxAtoms >= 2147483648.0) { fprintf(stderr, "%s: more than 2^31 slots\n", who); exit(-1); }
+}
+
+// fn(pair, rc2) with the pair function of the simulation's force path (virial_kernels.h) and its squared cutoff: one kernel instance per functor type
+template <class FN>
+static void withPairFunction(SimGpu* sim, FN fn)
+{
+   if (!sim->do_eam) {
+      const LjArgs a = makeLjArgs(sim, sim->boxes.nLocalBoxes, nullptr);
+      if (sim->lj_pot.lj_interpolation.values) { VirialLjTable p; p.t = ljTableView(sim); fn(p, a.rc2); }
+      else { VirialLj p; p.a = a; fn(p, a.rc2); }
+   } else {
+      const EamPotentialGpu& e = sim->eam_pot;
+      auto eam = [&](auto p) { p.phi = e.phi; p.rho = e.rho; p.phiS = e.phiS; p.rhoS = e.rhoS; p.dfEmbed = e.dfEmbed; p.dfi = R(0.0); fn(p, (real_t)(e.cutoff * e.cutoff)); };
+      if (e.phiS.coefficients && e.rhoS.coefficients) eam(VirialEam<true>()); else eam(VirialEam<false>());
+   }
+}
+
+// Not in the reference: the pair virial and the kinetic tensor (virial_kernels.h), one kernel instance per pair function of the force paths
+extern "C" void computeVirial(SimGpu* sim, real_t* out12)
+{
+   hipStream_t st = analysisStream(sim);
+   if (!sim->virialBuf) sim->virialBuf = dalloc<double>((size_t)(VIRIAL_BLOCKS + 1) * VIRIAL_N, false);
+   VirialArgs v;
+   fillStencilArgs(v, sim);
+   v.px = sim->atoms.p.x; v.py = sim->atoms.p.y; v.pz = sim->atoms.p.z;
+   v.iSpecies = sim->atoms.iSpecies; v.speciesMass = sim->species_mass;
+   v.partial = sim->virialBuf;
+   double* out = sim->virialBuf + (size_t)VIRIAL_BLOCKS * VIRIAL_N;
+   withPairFunction(sim, [&](auto p, real_t rc2) {
+      v.rc2 = rc2;
+      hipLaunchKernelGGL(Virial_thread_atom<decltype(p)>, dim3(VIRIAL_BLOCKS), dim3(256), 0, st, v, p);
+   });
+   hipLaunchKernelGGL(Virial_Final, dim3(1), dim3(256), 0, st, sim->virialBuf, VIRIAL_BLOCKS, out);
+   LAUNCH_CHECK();
+   double h[VIRIAL_N];
+   HIP_CHECK(hipMemcpyAsync(h, out, sizeof h, hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+   for (int c = 0; c < VIRIAL_N; ++c) out12[c] = (real_t)h[c];
+}
+
+// Not in the reference: the pair-distance histogram (rdf_kernels.h).  One instance for every potential and method: it reads positions and cells only
+extern "C" void computePairHistogram(SimGpu* sim, int nBins, real_t rMax, uint64_t* outCounts)
+{
+   hipStream_t st = analysisStream(sim);
+   if (nBins < 1 || nBins > PAIRHIST_MAX_BINS) { fprintf(stderr, "computePairHistogram: %d bins (1..%d)\n", nBins, PAIRHIST_MAX_BINS); exit(-1); }
+   if (nBins > sim->pairHistCap) {
+      if (sim->pairHistBuf) { HIP_CHECK(hipStreamSynchronize(st)); HIP_CHECK(hipFree(sim->pairHistBuf)); }
+      sim->pairHistBuf = dalloc<unsigned long long>((size_t)nBins, false);
+      sim->pairHistCap = nBins;
+   }
+   PairHistArgs v;
+   fillStencilArgs(v, sim);
+   v.nBins = nBins; v.rMax2 = rMax * rMax; v.invDr = (real_t)nBins / rMax;
+   v.counts = sim->pairHistBuf;
+   const size_t lds = (size_t)4 * nBins * sizeof(unsigned);      // one copy per wave
+   // what a workgroup can add to one 32-bit LDS counter stays below 2^32 (rdf_kernels.h); the grid does not show in a sum of integers
+   const long nWork = (long)v.nLocalBoxes * v.chunks;
+   int grid = PAIRHIST_BLOCKS;
+   while ((double)((nWork + grid - 1) / grid) * WAVE * 27.0 * v.cap >= 4.0e9) grid *= 2;
+   allowDynamicLds((const void*)PairHist_thread_atom, lds);
+   HIP_CHECK(hipMemsetAsync(sim->pairHistBuf, 0, (size_t)nBins * sizeof(unsigned long long), st));
+   hipLaunchKernelGGL(PairHist_thread_atom, dim3(grid), dim3(256), lds, st, v);
+   LAUNCH_CHECK();
+   HIP_CHECK(hipMemcpyAsync(outCounts, sim->pairHistBuf, (size_t)nBins * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// Not in the reference: the centro-symmetry parameter and the coordination number of every local atom (csp_kernels.h).  One instance for every
+// potential and method: it reads positions and cells only.  The two per-slot buffers are allocated by the first call.
+extern "C" void computeCentroSymmetry(SimGpu* sim, real_t rCoord, real_t* outCspBySlot, int* outCoordBySlot)
+{
+   hipStream_t st = analysisStream(sim);
+   const real_t cutoff = pairCutoff(sim);
+   if (!(rCoord > R(0.0)) || rCoord > cutoff) { fprintf(stderr, "computeCentroSymmetry: rCoord %g outside (0, cutoff = %g]\n", (double)rCoord, (double)cutoff); exit(-1); }
+   refuseSlotsBeyondInt(sim, "computeCentroSymmetry");
+   const size_t nSlots = localSlots(sim);
+   if (!sim->cspBuf) {
+      sim->cspBuf = dalloc<real_t>(nSlots);
+      sim->cspCoordBuf = dalloc<int>(nSlots);
+   }
+   CentroSymArgs v;
+   fillStencilArgs(v, sim);
+   v.rc2 = cutoff * cutoff; v.rCoord2 = rCoord * rCoord;
+   v.csp = sim->cspBuf; v.coord = sim->cspCoordBuf;
+   hipLaunchKernelGGL(CentroSym_thread_atom, dim3(CSP_BLOCKS), dim3(256), 0, st, v);
+   LAUNCH_CHECK();
+   HIP_CHECK(hipMemcpyAsync(outCspBySlot, sim->cspBuf, nSlots * sizeof(real_t), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipMemcpyAsync(outCoordBySlot, sim->cspCoordBuf, nSlots * sizeof(int), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// Not in the reference: adaptive common neighbour analysis, the structure type of every local atom (cna_kernels.h).  One instance for every potential
+// and method, as computeCentroSymmetry, whose walk it shares.  The per-slot buffer is allocated by the first call.
+extern "C" void computeCommonNeighbors(SimGpu* sim, int* outTypeBySlot)
+{
+   hipStream_t st = analysisStream(sim);
+   const real_t cutoff = pairCutoff(sim);
+   refuseSlotsBeyondInt(sim, "computeCommonNeighbors");
+   const size_t nSlots = localSlots(sim);
+   if (!sim->cnaBuf) sim->cnaBuf = dalloc<int>(nSlots);
+   CnaArgs v;
+   fillStencilArgs(v, sim);
+   v.rc2 = cutoff * cutoff;
+   v.type = sim->cnaBuf;
+   hipLaunchKernelGGL(Cna_thread_atom, dim3(CNA_BLOCKS), dim3(256), 0, st, v);
+   LAUNCH_CHECK();
+   HIP_CHECK(hipMemcpyAsync(outTypeBySlot, sim->cnaBuf, nSlots * sizeof(int), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// Not in the reference: the per-atom virial stress (stress_kernels.h), one kernel instance per pair function of the force paths, as computeVirial.
+// The six planes and the rows of the summary are allocated by the first call.
+extern "C" void computeAtomStress(SimGpu* sim, int withKinetic, real_t* outBySlot6)
+{
+   hipStream_t st = analysisStream(sim);
+   const size_t nSlots = localSlots(sim);
+   if (!sim->stressBuf) {
+      sim->stressBuf = dalloc<real_t>(6 * nSlots);
+      sim->stressSumBuf = dalloc<double>((size_t)(ATOMSTRESS_SUM_BLOCKS + 1) * ATOMSTRESS_SUM_N, false);
+   }
+   AtomStressArgs v;
+   fillStencilArgs(v, sim);
+   v.px = sim->atoms.p.x; v.py = sim->atoms.p.y; v.pz = sim->atoms.p.z;
+   v.iSpecies = sim->atoms.iSpecies; v.speciesMass = sim->species_mass;
+   v.withKinetic = withKinetic != 0;
+   v.plane = nSlots;
+   withPairFunction(sim, [&](auto p, real_t rc2) {
+      v.rc2 = rc2;
+      hipLaunchKernelGGL(AtomStress_thread_atom<decltype(p)>, dim3(ATOMSTRESS_BLOCKS), dim3(256), 0, st, v, p, sim->stressBuf);
+   });
+   LAUNCH_CHECK();
+   if (outBySlot6) HIP_CHECK(hipMemcpyAsync(outBySlot6, sim->stressBuf, 6 * nSlots * sizeof(real_t), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// The two stages of a summary (slot_summary.h) over the planes a compute... call has left on the device: stage 1 into the nRows rows of `rows`, stage 2
+// into the row behind them, whose n doubles come back, not the planes
+typedef void (*SummaryStage1)(const real_t*, size_t, const int*, const int*, int, double, double*);
+typedef void (*SummaryStage2)(const double*, int, double*);
+static void launchSummary(SimGpu* sim, SummaryStage1 stage1, SummaryStage2 stage2, const real_t* planes, double param, double* rows, int nRows, int n, double* out)
+{
+   hipStream_t st = analysisStream(sim);
+   double* final = rows + (size_t)nRows * n;
+   hipLaunchKernelGGL(stage1, dim3(nRows), dim3(256), 0, st, planes, localSlots(sim), sim->boxes.nAtoms, sim->atoms.gid, sim->maxAtoms, param, rows);
+   hipLaunchKernelGGL(stage2, dim3(1), dim3(256), 0, st, rows, nRows, final);
+   LAUNCH_CHECK();
+   HIP_CHECK(hipMemcpyAsync(out, final, n * sizeof(double), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// Not in the reference: the printed-step figures of the planes computeAtomStress has left on the device (stress_kernels.h): 7 doubles
+extern "C" void computeAtomStressSummary(SimGpu* sim, double atomVolume, double* out)
+{
+   if (!sim->stressBuf) { fprintf(stderr, "computeAtomStressSummary: no computeAtomStress call before it\n"); exit(-1); }
+   launchSummary(sim, AtomStress_Summary, AtomStress_SummaryFinal, sim->stressBuf, 1.0 / atomVolume, sim->stressSumBuf, ATOMSTRESS_SUM_BLOCKS, ATOMSTRESS_SUM_N, out);
+}
+
+// Not in the reference: the reference snapshot of the per-atom strain (strain_kernels.h).  on: one 32-byte record of doubles per global atom id, zeroed, then
+// the positions of this rank's local atoms at their gids (taken again when it is already on); the host adds the ranks' tables and uploads the sum into
+// strainRefBuf.  off: the table and the planes of computeAtomStrain are freed.  1 and no reference when the device cannot give the memory.
+static void freeStrainPlanes(SimGpu* sim)
+{
+   if (sim->strainBuf) { HIP_CHECK(hipFree(sim->strainBuf)); HIP_CHECK(hipFree(sim->strainCountBuf)); HIP_CHECK(hipFree(sim->strainSumBuf)); }
+   sim->strainBuf = nullptr; sim->strainCountBuf = nullptr; sim->strainSumBuf = nullptr;
+}
+
+extern "C" int comdStrainReferenceGpu(SimGpu* sim, int nGlobal, int on)
+{
+   hipStream_t st = analysisStream(sim);
+   if (!on || nGlobal != sim->strainRefN) {
+      if (sim->strainRefBuf || sim->strainBuf) HIP_CHECK(hipStreamSynchronize(st));
+      if (sim->strainRefBuf) HIP_CHECK(hipFree(sim->strainRefBuf));
+      sim->strainRefBuf = nullptr; sim->strainRefN = 0;
+      freeStrainPlanes(sim);
+      if (!on) return 0;
+   }
+   if (nGlobal < 1) return 1;
+   if (!sim->strainRefBuf) {
+      void* d = nullptr;
+      if (hipMalloc(&d, (size_t)nGlobal * 4 * sizeof(double)) != hipSuccess) {
+         (void)hipGetLastError();
+         fprintf(stderr, "comdStrainReferenceGpu: rank %d: no device memory for %d records of 32 bytes (%.1f MB): no reference\n",
+                 g_rank, nGlobal, nGlobal * 32.0 / 1048576.0);
+         return 1;
+      }
+      sim->strainRefBuf = (double*)d; sim->strainRefN = nGlobal;
+   }
+   const size_t nSlots = localSlots(sim);
+   HIP_CHECK(hipMemsetAsync(sim->strainRefBuf, 0, (size_t)nGlobal * 4 * sizeof(double), st));
+   const size_t blocks = (nSlots + 255) / 256;
+   hipLaunchKernelGGL(StrainReference_Store, dim3((unsigned)(blocks < 4096 ? (blocks ? blocks : 1) : 4096)), dim3(256), 0, st, sim->atoms.r.x, sim->atoms.r.y, sim->atoms.r.z,
+                      sim->boxes.nAtoms, sim->atoms.gid, sim->maxAtoms, nSlots, nGlobal, sim->strainRefBuf);
+   LAUNCH_CHECK();
+   HIP_CHECK(hipStreamSynchronize(st));
+   return 0;
+}
+
+// Not in the reference: the per-atom strain tensor and D^2min against the reference table (strain_kernels.h).  One instance for every potential and
+// method: it reads positions, gids and cells only.  The planes and the rows of the summary are allocated by the first call.
+extern "C" void computeAtomStrain(SimGpu* sim, real_t rCut, real_t* outBySlot7, int* outCountBySlot)
+{
+   hipStream_t st = analysisStream(sim);
+   const real_t cutoff = pairCutoff(sim);
+   if (!sim->strainRefBuf) { fprintf(stderr, "computeAtomStrain: no reference (comdStrainReferenceGpu)\n"); exit(-1); }
+   if (!(rCut > R(0.0)) || rCut > cutoff) { fprintf(stderr, "computeAtomStrain: rCut %g outside (0, cutoff = %g]\n", (double)rCut, (double)cutoff); exit(-1); }
+   const size_t nSlots = localSlots(sim);
+   if (!sim->strainBuf) {
+      sim->strainBuf = dalloc<real_t>(ATOMSTRAIN_PLANES * nSlots);
+      sim->strainCountBuf = dalloc<int>(nSlots);
+      sim->strainSumBuf = dalloc<double>((size_t)(ATOMSTRAIN_SUM_BLOCKS + 1) * ATOMSTRAIN_SUM_N, false);
+   }
+   AtomStrainArgs v;
+   fillStencilArgs(v, sim);
+   v.gid = sim->atoms.gid; v.ref = sim->strainRefBuf; v.nRef = sim->strainRefN;
+   v.rs2 = rCut * rCut;
+   v.L0x = sim->strainL0[0]; v.L0y = sim->strainL0[1]; v.L0z = sim->strainL0[2];
+   v.plane = nSlots;
+   hipLaunchKernelGGL(AtomStrain_thread_atom, dim3(ATOMSTRAIN_BLOCKS), dim3(256), 0, st, v, sim->strainBuf, sim->strainCountBuf);
+   LAUNCH_CHECK();
+   if (outBySlot7) HIP_CHECK(hipMemcpyAsync(outBySlot7, sim->strainBuf, ATOMSTRAIN_PLANES * nSlots * sizeof(real_t), hipMemcpyDeviceToHost, st));
+   if (outCountBySlot) HIP_CHECK(hipMemcpyAsync(outCountBySlot, sim->strainCountBuf, nSlots * sizeof(int), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// Not in the reference: the printed-step figures of the planes computeAtomStrain has left on the device (strain_kernels.h): 9 doubles
+extern "C" void computeAtomStrainSummary(SimGpu* sim, double threshold, double* out)
+{
+   if (!sim->strainBuf) { fprintf(stderr, "computeAtomStrainSummary: no computeAtomStrain call before it\n"); exit(-1); }
+   launchSummary(sim, AtomStrain_Summary, AtomStrain_SummaryFinal, sim->strainBuf, threshold, sim->strainSumBuf, ATOMSTRAIN_SUM_BLOCKS, ATOMSTRAIN_SUM_N, out);
+}
+
+// Not in the reference: displacement tracking for the mean-squared displacement (msd_kernels.h).  on: one zeroed 32-byte record per global atom id,
+// which the drift kernels of this simulation add into from now on (already on: zeroed again, the origin becomes "now"); off: the memory is
+// freed.  1 and nothing tracked when the device cannot give the memory.
+extern "C" int comdTrackDisplacementGpu(SimGpu* sim, int nGlobal, int on)
+{
+   hipStream_t st = S(sim->boundary_stream);
+   if (!on || nGlobal != sim->dispN) {
+      if (sim->dispBuf) {
+         HIP_CHECK(hipStreamSynchronize(st));               // the last drift kernel has written its records
+         HIP_CHECK(hipFree(sim->dispBuf)); HIP_CHECK(hipFree(sim->dispSumBuf));
+      }
+      sim->dispBuf = nullptr; sim->dispSumBuf = nullptr; sim->dispN = 0;
+      if (!on) return 0;
+   }
+   if (nGlobal < 1) return 1;
+   if (!sim->dispBuf) {
+      void *d = nullptr, *p = nullptr;
+      if (hipMalloc(&d, (size_t)nGlobal * 4 * sizeof(long long)) != hipSuccess
+          || hipMalloc(&p, (size_t)(MSD_BLOCKS + 1) * MSD_N * sizeof(double)) != hipSuccess) {
+         (void)hipGetLastError();
+         if (d) (void)hipFree(d);
+         fprintf(stderr, "comdTrackDisplacementGpu: rank %d: no device memory for %d records of 32 bytes (%.1f MB): not tracking\n",
+                 g_rank, nGlobal, nGlobal * 32.0 / 1048576.0);
+         return 1;
+      }
+      sim->dispBuf = (int64_t*)d; sim->dispSumBuf = (double*)p; sim->dispN = nGlobal;
+   }
+   HIP_CHECK(hipMemsetAsync(sim->dispBuf, 0, (size_t)nGlobal * 4 * sizeof(long long), st));      // behind the drifts already launched
+   HIP_CHECK(hipStreamSynchronize(st));
+   return 0;
+}
+
+// Not in the reference: {sum dx, dy, dz, sum dx^2, dy^2, dz^2} (Angstroms, double in both builds) over THIS rank's records
+extern "C" void computeDisplacementSums(SimGpu* sim, double* out6)
+{
+   hipStream_t st = S(sim->boundary_stream);
+   if (!sim->dispBuf) { fprintf(stderr, "computeDisplacementSums: displacements are not tracked\n"); exit(-1); }
+   int blocks = ceilDiv(sim->dispN, 256);
+   if (blocks > MSD_BLOCKS) blocks = MSD_BLOCKS;
+   double* out = sim->dispSumBuf + (size_t)MSD_BLOCKS * MSD_N;
+   hipLaunchKernelGGL(ReduceDisplacementPartial, dim3(blocks), dim3(256), 0, st, (const long long*)sim->dispBuf, sim->dispN, sim->dispSumBuf);
+   hipLaunchKernelGGL(ReduceDisplacementFinal, dim3(1), dim3(256), 0, st, sim->dispSumBuf, blocks, out);
+   LAUNCH_CHECK();
+   HIP_CHECK(hipMemcpyAsync(out6, out, MSD_N * sizeof(double), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// Not in the reference: THIS rank's raw records, [nGlobal][4] int64 {dx, dy, dz, spare} in units of 2^-32 Angstroms
+extern "C" void comdCopyDisplacementsGpu(SimGpu* sim, int64_t* out)
+{
+   hipStream_t st = S(sim->boundary_stream);
+   if (!sim->dispBuf) { fprintf(stderr, "comdCopyDisplacementsGpu: displacements are not tracked\n"); exit(-1); }
+   HIP_CHECK(hipMemcpyAsync(out, sim->dispBuf, (size_t)sim->dispN * 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+}

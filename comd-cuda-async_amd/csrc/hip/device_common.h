@@ -94,6 +94,7 @@ __device__ __forceinline__ float bpermuteAddrR(float v, int addr)
 {
    return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v)));
 }
+__device__ __forceinline__ int bpermuteAddrR(int v, int addr) { return __builtin_amdgcn_ds_bpermute(addr, v); }
 
 // butterfly sum over the 64 lanes; every lane ends with the total, in a fixed order
 __device__ __forceinline__ real_t waveSum(real_t v)
@@ -101,6 +102,24 @@ __device__ __forceinline__ real_t waveSum(real_t v)
 #pragma unroll
    for (int m = 32; m >= 1; m >>= 1) v += bpermuteR(v, laneId() ^ m);
    return v;
+}
+
+// out[c] = the sum of acc[c] over the 256 threads of the workgroup, in double in both builds and in a fixed order: the butterfly over the lanes
+// (m = 32 ... 1), one row per wave through LDS, then (wave 0 + wave 1) + (wave 2 + wave 3) by the threads below N
+template <int N>
+__device__ __forceinline__ void blockSumD(double (&acc)[N], double* __restrict__ out)
+{
+   __shared__ double sAcc[4][N];
+   const int lane = laneId(), wave = (int)threadIdx.x >> 6;
+#pragma unroll
+   for (int c = 0; c < N; ++c) {
+      double s = acc[c];
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) s += bpermuteR(s, lane ^ m);
+      if (lane == 0) sAcc[wave][c] = s;
+   }
+   __syncthreads();
+   if (threadIdx.x < N) out[threadIdx.x] = (sAcc[0][threadIdx.x] + sAcc[1][threadIdx.x]) + (sAcc[2][threadIdx.x] + sAcc[3][threadIdx.x]);
 }
 
 // ---- DPP / permlane reductions: pure VALU, no trip through the LDS crossbar --------------------------------------

@@ -33,26 +33,6 @@ __device__ __forceinline__ void dispAdd(const DispTrack& t, int g, real_t ix, re
 #define MSD_BLOCKS 1024
 #define MSD_N 6
 
-__device__ __forceinline__ double msdWaveSum(double v)
-{
-#pragma unroll
-   for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-   return v;
-}
-
-__device__ __forceinline__ void msdBlockSum(double (&acc)[MSD_N], double* __restrict__ out)
-{
-   __shared__ double sAcc[4][MSD_N];
-   const int wave = (int)threadIdx.x >> 6;
-#pragma unroll
-   for (int c = 0; c < MSD_N; ++c) {
-      const double s = msdWaveSum(acc[c]);
-      if ((threadIdx.x & 63) == 0) sAcc[wave][c] = s;
-   }
-   __syncthreads();
-   if (threadIdx.x < MSD_N) out[threadIdx.x] = (sAcc[0][threadIdx.x] + sAcc[1][threadIdx.x]) + (sAcc[2][threadIdx.x] + sAcc[3][threadIdx.x]);
-}
-
 __global__ __launch_bounds__(256)
 void ReduceDisplacementPartial(const long long* __restrict__ d, int n, double* __restrict__ partial)
 {
@@ -66,7 +46,7 @@ void ReduceDisplacementPartial(const long long* __restrict__ d, int n, double* _
       acc[0] += x; acc[1] += y; acc[2] += z;
       acc[3] += x * x; acc[4] += y * y; acc[5] += z * z;
    }
-   msdBlockSum(acc, partial + (size_t)MSD_N * blockIdx.x);
+   blockSumD(acc, partial + (size_t)MSD_N * blockIdx.x);
 }
 
 __global__ __launch_bounds__(256)
@@ -78,5 +58,5 @@ void ReduceDisplacementFinal(const double* __restrict__ partial, int nPartial, d
    for (int i = threadIdx.x; i < nPartial; i += blockDim.x)
 #pragma unroll
       for (int c = 0; c < MSD_N; ++c) acc[c] += partial[(size_t)MSD_N * i + c];
-   msdBlockSum(acc, out);
+   blockSumD(acc, out);
 }

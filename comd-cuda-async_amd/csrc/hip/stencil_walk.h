@@ -52,6 +52,18 @@ __device__ __forceinline__ void forEachChunk(const StencilArgs& v, int lane, int
    }
 }
 
+// The shares of the copies of a replicated chunk into one, for sums and counts (real_t, double or int): after the doubling over s every lane holds the
+// sum over the copies lane ^ s, lane ^ 2s, ... as well.  a + b is what both lanes of a pair compute, so every copy ends with the same bits, in an
+// order that depends on reps alone.  One loop over s with all values inside it: one address serves them all.
+template <class... T>
+__device__ __forceinline__ void sumOverCopies(int lane, int span, T&... x)
+{
+   for (int s = span; s < WAVE; s <<= 1) {
+      const int addr = (lane ^ s) << 2;
+      ((x += bpermuteAddrR(x, addr)), ...);
+   }
+}
+
 // test(xj, yj, zj, slot) for the slots of the stencil cells of iBox: copy q's share of them when the chunk is replicated, else all 27 with the
 // neighbour wave-uniform.  IDX: the type slots are computed in (size_t, or int where the host has checked that they fit)
 template <class IDX, class TEST>

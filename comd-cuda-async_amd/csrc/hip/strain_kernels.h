@@ -28,6 +28,7 @@
 // workgroup combines in a fixed order and writes one row; the second stage combines the rows in a fixed order.
 #pragma once
 #include "stencil_walk.h"
+#include "slot_summary.h"
 
 #define ATOMSTRAIN_BLOCKS 2048         // the grid of the walk, as ATOMSTRESS_BLOCKS
 #define ATOMSTRAIN_SUM_BLOCKS 512      // rows of the summary: fixed, so the order of the sums does not depend on the system
@@ -97,19 +98,7 @@ void AtomStrain_thread_atom(AtomStrainArgs v, real_t* __restrict__ out, int* __r
          }
       };
       stencilWalk<size_t>(v, iBox, reps, q, test);
-      if (reps > 1) {
-         // the copies' shares into one: after the doubling over s every lane holds the sum over the copies lane ^ s, lane ^ 2s, ... as well
-         for (int s = span; s < WAVE; s <<= 1) {
-            const int addr = (lane ^ s) << 2;
-            vxx += bpermuteAddrR(vxx, addr); vyy += bpermuteAddrR(vyy, addr); vzz += bpermuteAddrR(vzz, addr);
-            vyz += bpermuteAddrR(vyz, addr); vxz += bpermuteAddrR(vxz, addr); vxy += bpermuteAddrR(vxy, addr);
-            axx += bpermuteAddrR(axx, addr); axy += bpermuteAddrR(axy, addr); axz += bpermuteAddrR(axz, addr);
-            ayx += bpermuteAddrR(ayx, addr); ayy += bpermuteAddrR(ayy, addr); ayz += bpermuteAddrR(ayz, addr);
-            azx += bpermuteAddrR(azx, addr); azy += bpermuteAddrR(azy, addr); azz += bpermuteAddrR(azz, addr);
-            ss += bpermuteAddrR(ss, addr);
-            n += __builtin_amdgcn_ds_bpermute(addr, n);
-         }
-      }
+      if (reps > 1) sumOverCopies(lane, span, vxx, vyy, vzz, vyz, vxz, vxy, axx, axy, axz, ayx, ayy, ayz, azx, azy, azz, ss, n);
       if (active && q == 0) {
          // the adjugate of V and its determinant
          const double c00 = vyy * vzz - vyz * vyz, c01 = vxz * vyz - vxy * vzz, c02 = vxy * vyz - vxz * vyy;
@@ -140,104 +129,54 @@ void AtomStrain_thread_atom(AtomStrainArgs v, real_t* __restrict__ out, int* __r
    });
 }
 
-// one candidate of the summary: the sums and the counts add, the extremes compare; of two equal gamma the lower gid stays
+// one candidate of the summary (slot_summary.h): the sums and the counts add, the extremes compare; of two equal gamma the lower gid stays
 struct AtomStrainSum {
    double sumG, maxG, sumV, sumD, maxD;
    int gid, n, bad, above;
+   static constexpr int N = ATOMSTRAIN_SUM_N;
+
+   __device__ static AtomStrainSum empty() { return AtomStrainSum{ 0.0, -__builtin_huge_val(), 0.0, 0.0, -__builtin_huge_val(), -1, 0, 0, 0 }; }
+   __device__ void join(const AtomStrainSum& b)
+   {
+      sumG += b.sumG; sumV += b.sumV; sumD += b.sumD; n += b.n; bad += b.bad; above += b.above;
+      maxD = b.maxD > maxD ? b.maxD : maxD;
+      const bool take = b.gid >= 0 && (gid < 0 || b.maxG > maxG || (b.maxG == maxG && b.gid < gid));
+      maxG = take ? b.maxG : maxG; gid = take ? b.gid : gid;
+   }
+   __device__ void toRow(double* __restrict__ row) const
+   {
+      row[0] = sumG; row[1] = maxG; row[2] = (double)gid; row[3] = sumV; row[4] = sumD; row[5] = maxD;
+      row[6] = (double)n; row[7] = (double)bad; row[8] = (double)above;
+   }
+   __device__ static AtomStrainSum fromRow(const double* __restrict__ row)
+   {
+      return AtomStrainSum{ row[0], row[1], row[3], row[4], row[5], (int)row[2], (int)row[6], (int)row[7], (int)row[8] };
+   }
 };
 
-__device__ __forceinline__ void atomStrainJoin(AtomStrainSum& a, const AtomStrainSum& b)
-{
-   a.sumG += b.sumG; a.sumV += b.sumV; a.sumD += b.sumD; a.n += b.n; a.bad += b.bad; a.above += b.above;
-   a.maxD = b.maxD > a.maxD ? b.maxD : a.maxD;
-   const bool take = b.gid >= 0 && (a.gid < 0 || b.maxG > a.maxG || (b.maxG == a.maxG && b.gid < a.gid));
-   a.maxG = take ? b.maxG : a.maxG; a.gid = take ? b.gid : a.gid;
-}
-
-// over the 64 lanes, then over the 4 waves, in a fixed order; thread 0 ends with the workgroup's candidate
-__device__ __forceinline__ void atomStrainBlockJoin(AtomStrainSum& a, double (*sD)[5], int (*sI)[4])
-{
-   const int lane = laneId(), wave = (int)threadIdx.x >> 6;
-#pragma unroll
-   for (int m = 32; m >= 1; m >>= 1) {
-      const int src = lane ^ m;
-      AtomStrainSum b;
-      b.sumG = bpermuteR(a.sumG, src); b.maxG = bpermuteR(a.maxG, src); b.sumV = bpermuteR(a.sumV, src);
-      b.sumD = bpermuteR(a.sumD, src); b.maxD = bpermuteR(a.maxD, src);
-      b.gid = __builtin_amdgcn_ds_bpermute(src << 2, a.gid); b.n = __builtin_amdgcn_ds_bpermute(src << 2, a.n);
-      b.bad = __builtin_amdgcn_ds_bpermute(src << 2, a.bad); b.above = __builtin_amdgcn_ds_bpermute(src << 2, a.above);
-      atomStrainJoin(a, b);      // symmetric in its operands (a + b, the extremes, the lower gid): both lanes of a pair end with the same bits
-   }
-   if (lane == 0) {
-      sD[wave][0] = a.sumG; sD[wave][1] = a.maxG; sD[wave][2] = a.sumV; sD[wave][3] = a.sumD; sD[wave][4] = a.maxD;
-      sI[wave][0] = a.gid; sI[wave][1] = a.n; sI[wave][2] = a.bad; sI[wave][3] = a.above;
-   }
-   __syncthreads();
-   if (threadIdx.x == 0) {
-      for (int w = 1; w < 4; ++w) {
-         AtomStrainSum b;
-         b.sumG = sD[w][0]; b.maxG = sD[w][1]; b.sumV = sD[w][2]; b.sumD = sD[w][3]; b.maxD = sD[w][4];
-         b.gid = sI[w][0]; b.n = sI[w][1]; b.bad = sI[w][2]; b.above = sI[w][3];
-         atomStrainJoin(a, b);
-      }
-   }
-}
-
-__device__ __forceinline__ AtomStrainSum atomStrainEmpty()
-{
-   AtomStrainSum a;
-   a.sumG = 0.0; a.maxG = -__builtin_huge_val(); a.sumV = 0.0; a.sumD = 0.0; a.maxD = -__builtin_huge_val();
-   a.gid = -1; a.n = 0; a.bad = 0; a.above = 0;
-   return a;
-}
-
-__device__ __forceinline__ void atomStrainRow(const AtomStrainSum& a, double* __restrict__ row)
-{
-   row[0] = a.sumG; row[1] = a.maxG; row[2] = (double)a.gid; row[3] = a.sumV; row[4] = a.sumD; row[5] = a.maxD;
-   row[6] = (double)a.n; row[7] = (double)a.bad; row[8] = (double)a.above;
-}
-
-// stage 1: the occupied slots of the planes -> one row per workgroup, partial[blockIdx.x][ATOMSTRAIN_SUM_N] (gid and counts as doubles: exact)
+// stage 1: gamma, vol and D^2 of the occupied slots of the planes; an invalid atom counts and stays out of the rest
 __global__ __launch_bounds__(256)
 void AtomStrain_Summary(const real_t* __restrict__ planes, size_t plane, const int* __restrict__ nAtoms, const int* __restrict__ gid, int cap,
                         double threshold, double* __restrict__ partial)
 {
-   __shared__ double sD[4][5];
-   __shared__ int sI[4][4];
-   AtomStrainSum a = atomStrainEmpty();
-   for (size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x; o < plane; o += (size_t)gridDim.x * blockDim.x) {
-      const size_t b = o / (size_t)cap;
-      if ((int)(o - b * (size_t)cap) >= nAtoms[b]) continue;
+   summaryOfSlots<AtomStrainSum>(plane, nAtoms, cap, partial, [&](size_t o) {
       const double xx = (double)planes[o], yy = (double)planes[plane + o], zz = (double)planes[2 * plane + o];
       const double yz = (double)planes[3 * plane + o], xz = (double)planes[4 * plane + o], xy = (double)planes[5 * plane + o];
       const double d2 = (double)planes[6 * plane + o];
-      AtomStrainSum c = atomStrainEmpty();
+      AtomStrainSum c = AtomStrainSum::empty();
       if (xx != xx) c.bad = 1;
       else {
          const double d0 = xx - yy, d1 = yy - zz, d2e = zz - xx;
          const double g = __builtin_sqrt(((yz * yz + xz * xz) + xy * xy) + ((d0 * d0 + d1 * d1) + d2e * d2e) / 6.0);
          c.sumG = g; c.maxG = g; c.sumV = ((xx + yy) + zz) / 3.0; c.sumD = d2; c.maxD = d2; c.gid = gid[o]; c.n = 1; c.above = g >= threshold ? 1 : 0;
       }
-      atomStrainJoin(a, c);
-   }
-   atomStrainBlockJoin(a, sD, sI);
-   if (threadIdx.x == 0) atomStrainRow(a, partial + (size_t)blockIdx.x * ATOMSTRAIN_SUM_N);
+      return c;
+   });
 }
 
-// stage 2: the rows -> out[ATOMSTRAIN_SUM_N], in a fixed order
+// stage 2: the rows -> out[ATOMSTRAIN_SUM_N]
 __global__ __launch_bounds__(256)
 void AtomStrain_SummaryFinal(const double* __restrict__ partial, int nPartial, double* __restrict__ out)
 {
-   __shared__ double sD[4][5];
-   __shared__ int sI[4][4];
-   AtomStrainSum a = atomStrainEmpty();
-   for (int i = threadIdx.x; i < nPartial; i += blockDim.x) {
-      const double* row = partial + (size_t)i * ATOMSTRAIN_SUM_N;
-      AtomStrainSum c;
-      c.sumG = row[0]; c.maxG = row[1]; c.gid = (int)row[2]; c.sumV = row[3]; c.sumD = row[4]; c.maxD = row[5];
-      c.n = (int)row[6]; c.bad = (int)row[7]; c.above = (int)row[8];
-      atomStrainJoin(a, c);
-   }
-   atomStrainBlockJoin(a, sD, sI);
-   if (threadIdx.x == 0) atomStrainRow(a, out);
+   summaryOfRows<AtomStrainSum>(partial, nPartial, out);
 }

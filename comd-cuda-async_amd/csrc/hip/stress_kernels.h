@@ -20,6 +20,7 @@
 // the slots with a fixed stride, the workgroup combines in a fixed order and writes one row; the second stage combines the rows in a fixed order.
 #pragma once
 #include "virial_kernels.h"
+#include "slot_summary.h"
 
 #define ATOMSTRESS_BLOCKS 2048         // the grid of the walk, as VIRIAL_BLOCKS
 #define ATOMSTRESS_SUM_BLOCKS 512      // rows of the summary: fixed, so the order of the sums does not depend on the system
@@ -58,14 +59,7 @@ void AtomStress_thread_atom(AtomStressArgs v, PAIR pair, real_t* __restrict__ ou
          }
       };
       stencilWalk<size_t>(v, iBox, reps, q, test);
-      if (reps > 1) {
-         // the copies' shares into one: after the doubling over s every lane holds the sum over the copies lane ^ s, lane ^ 2s, ... as well
-         for (int s = span; s < WAVE; s <<= 1) {
-            const int addr = (lane ^ s) << 2;
-            wxx += bpermuteAddrR(wxx, addr); wyy += bpermuteAddrR(wyy, addr); wzz += bpermuteAddrR(wzz, addr);
-            wyz += bpermuteAddrR(wyz, addr); wxz += bpermuteAddrR(wxz, addr); wxy += bpermuteAddrR(wxy, addr);
-         }
-      }
+      if (reps > 1) sumOverCopies(lane, span, wxx, wyy, wzz, wyz, wxz, wxy);
       if (active && q == 0) {
          const real_t h = R(0.5) * pair.scale();
          real_t kxx = R(0.0), kyy = R(0.0), kzz = R(0.0), kyz = R(0.0), kxz = R(0.0), kxy = R(0.0);
@@ -82,96 +76,47 @@ void AtomStress_thread_atom(AtomStressArgs v, PAIR pair, real_t* __restrict__ ou
    });
 }
 
-// one candidate of the summary: the two sums and the count add, the extremes compare; of two equal sigma the lower gid stays
+// one candidate of the summary (slot_summary.h): the two sums and the count add, the extremes compare; of two equal sigma the lower gid stays
 struct AtomStressSum {
    double sumP, minP, maxP, sumS, maxS;
    int gid, n;
+   static constexpr int N = ATOMSTRESS_SUM_N;
+
+   __device__ static AtomStressSum empty() { return AtomStressSum{ 0.0, __builtin_huge_val(), -__builtin_huge_val(), 0.0, -__builtin_huge_val(), -1, 0 }; }
+   __device__ void join(const AtomStressSum& b)
+   {
+      sumP += b.sumP; sumS += b.sumS; n += b.n;
+      minP = b.minP < minP ? b.minP : minP;
+      maxP = b.maxP > maxP ? b.maxP : maxP;
+      const bool take = b.gid >= 0 && (gid < 0 || b.maxS > maxS || (b.maxS == maxS && b.gid < gid));
+      maxS = take ? b.maxS : maxS; gid = take ? b.gid : gid;
+   }
+   __device__ void toRow(double* __restrict__ row) const
+   {
+      row[0] = sumP; row[1] = minP; row[2] = maxP; row[3] = sumS; row[4] = maxS; row[5] = (double)gid; row[6] = (double)n;
+   }
+   __device__ static AtomStressSum fromRow(const double* __restrict__ row) { return AtomStressSum{ row[0], row[1], row[2], row[3], row[4], (int)row[5], (int)row[6] }; }
 };
 
-__device__ __forceinline__ void atomStressJoin(AtomStressSum& a, const AtomStressSum& b)
-{
-   a.sumP += b.sumP; a.sumS += b.sumS; a.n += b.n;
-   a.minP = b.minP < a.minP ? b.minP : a.minP;
-   a.maxP = b.maxP > a.maxP ? b.maxP : a.maxP;
-   const bool take = b.gid >= 0 && (a.gid < 0 || b.maxS > a.maxS || (b.maxS == a.maxS && b.gid < a.gid));
-   a.maxS = take ? b.maxS : a.maxS; a.gid = take ? b.gid : a.gid;
-}
-
-// over the 64 lanes, then over the 4 waves, in a fixed order; thread 0 ends with the workgroup's candidate
-__device__ __forceinline__ void atomStressBlockJoin(AtomStressSum& a, double (*sD)[5], int (*sI)[2])
-{
-   const int lane = laneId(), wave = (int)threadIdx.x >> 6;
-#pragma unroll
-   for (int m = 32; m >= 1; m >>= 1) {
-      const int src = lane ^ m;
-      AtomStressSum b;
-      b.sumP = bpermuteR(a.sumP, src); b.minP = bpermuteR(a.minP, src); b.maxP = bpermuteR(a.maxP, src);
-      b.sumS = bpermuteR(a.sumS, src); b.maxS = bpermuteR(a.maxS, src);
-      b.gid = __builtin_amdgcn_ds_bpermute(src << 2, a.gid); b.n = __builtin_amdgcn_ds_bpermute(src << 2, a.n);
-      atomStressJoin(a, b);      // symmetric in its operands (a + b, the extremes, the lower gid): both lanes of a pair end with the same bits
-   }
-   if (lane == 0) { sD[wave][0] = a.sumP; sD[wave][1] = a.minP; sD[wave][2] = a.maxP; sD[wave][3] = a.sumS; sD[wave][4] = a.maxS; sI[wave][0] = a.gid; sI[wave][1] = a.n; }
-   __syncthreads();
-   if (threadIdx.x == 0) {
-      for (int w = 1; w < 4; ++w) {
-         AtomStressSum b;
-         b.sumP = sD[w][0]; b.minP = sD[w][1]; b.maxP = sD[w][2]; b.sumS = sD[w][3]; b.maxS = sD[w][4]; b.gid = sI[w][0]; b.n = sI[w][1];
-         atomStressJoin(a, b);
-      }
-   }
-}
-
-__device__ __forceinline__ AtomStressSum atomStressEmpty()
-{
-   AtomStressSum a;
-   a.sumP = 0.0; a.minP = __builtin_huge_val(); a.maxP = -__builtin_huge_val(); a.sumS = 0.0; a.maxS = -__builtin_huge_val();
-   a.gid = -1; a.n = 0;
-   return a;
-}
-
-// stage 1: the occupied slots of the planes -> one row per workgroup, partial[blockIdx.x][ATOMSTRESS_SUM_N] (gid and count as doubles: exact)
+// stage 1: p and sigma of the occupied slots of the planes
 __global__ __launch_bounds__(256)
 void AtomStress_Summary(const real_t* __restrict__ planes, size_t plane, const int* __restrict__ nAtoms, const int* __restrict__ gid, int cap,
                         double invOmega, double* __restrict__ partial)
 {
-   __shared__ double sD[4][5];
-   __shared__ int sI[4][2];
-   AtomStressSum a = atomStressEmpty();
    const double third = invOmega / 3.0;
-   for (size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x; o < plane; o += (size_t)gridDim.x * blockDim.x) {
-      const size_t b = o / (size_t)cap;
-      if ((int)(o - b * (size_t)cap) >= nAtoms[b]) continue;
+   summaryOfSlots<AtomStressSum>(plane, nAtoms, cap, partial, [&](size_t o) {
       const double xx = (double)planes[o], yy = (double)planes[plane + o], zz = (double)planes[2 * plane + o];
       const double yz = (double)planes[3 * plane + o], xz = (double)planes[4 * plane + o], xy = (double)planes[5 * plane + o];
       const double p = -((xx + yy) + zz) * third;
       const double d0 = xx - yy, d1 = yy - zz, d2 = zz - xx;
       const double s = __builtin_sqrt(0.5 * ((d0 * d0 + d1 * d1) + d2 * d2) + 3.0 * ((yz * yz + xz * xz) + xy * xy)) * invOmega;
-      AtomStressSum c;
-      c.sumP = p; c.minP = p; c.maxP = p; c.sumS = s; c.maxS = s; c.gid = gid[o]; c.n = 1;
-      atomStressJoin(a, c);
-   }
-   atomStressBlockJoin(a, sD, sI);
-   if (threadIdx.x == 0) {
-      double* row = partial + (size_t)blockIdx.x * ATOMSTRESS_SUM_N;
-      row[0] = a.sumP; row[1] = a.minP; row[2] = a.maxP; row[3] = a.sumS; row[4] = a.maxS; row[5] = (double)a.gid; row[6] = (double)a.n;
-   }
+      return AtomStressSum{ p, p, p, s, s, gid[o], 1 };
+   });
 }
 
-// stage 2: the rows -> out[ATOMSTRESS_SUM_N], in a fixed order
+// stage 2: the rows -> out[ATOMSTRESS_SUM_N]
 __global__ __launch_bounds__(256)
 void AtomStress_SummaryFinal(const double* __restrict__ partial, int nPartial, double* __restrict__ out)
 {
-   __shared__ double sD[4][5];
-   __shared__ int sI[4][2];
-   AtomStressSum a = atomStressEmpty();
-   for (int i = threadIdx.x; i < nPartial; i += blockDim.x) {
-      const double* row = partial + (size_t)i * ATOMSTRESS_SUM_N;
-      AtomStressSum c;
-      c.sumP = row[0]; c.minP = row[1]; c.maxP = row[2]; c.sumS = row[3]; c.maxS = row[4]; c.gid = (int)row[5]; c.n = (int)row[6];
-      atomStressJoin(a, c);
-   }
-   atomStressBlockJoin(a, sD, sI);
-   if (threadIdx.x == 0) {
-      out[0] = a.sumP; out[1] = a.minP; out[2] = a.maxP; out[3] = a.sumS; out[4] = a.maxS; out[5] = (double)a.gid; out[6] = (double)a.n;
-   }
+   summaryOfRows<AtomStressSum>(partial, nPartial, out);
 }

@@ -79,19 +79,10 @@ struct VirialEam {
    }
 };
 
-// sum over the 64 lanes in double, in a fixed order
-__device__ __forceinline__ double waveSumD(double v)
-{
-#pragma unroll
-   for (int m = 32; m >= 1; m >>= 1) v += bpermuteR(v, laneId() ^ m);
-   return v;
-}
-
 template <class PAIR>
 __global__ __launch_bounds__(256)
 void Virial_thread_atom(VirialArgs v, PAIR pair)
 {
-   __shared__ double sAcc[4][VIRIAL_N];
    const int lane = laneId(), wave = (int)threadIdx.x >> 6;
    real_t acc[VIRIAL_N];
 #pragma unroll
@@ -125,33 +116,21 @@ void Virial_thread_atom(VirialArgs v, PAIR pair)
          acc[9] = fmaR(qy * qz, invMass, acc[9]); acc[10] = fmaR(qx * qz, invMass, acc[10]); acc[11] = fmaR(qx * qy, invMass, acc[11]);
       }
    });
+   double sum[VIRIAL_N];
 #pragma unroll
-   for (int c = 0; c < VIRIAL_N; ++c) {
-      const double s = waveSumD((double)acc[c]);
-      if (lane == 0) sAcc[wave][c] = s;
-   }
-   __syncthreads();
-   if (threadIdx.x < VIRIAL_N) {
-      const int c = threadIdx.x;
-      v.partial[(size_t)blockIdx.x * VIRIAL_N + c] = (sAcc[0][c] + sAcc[1][c]) + (sAcc[2][c] + sAcc[3][c]);
-   }
+   for (int c = 0; c < VIRIAL_N; ++c) sum[c] = (double)acc[c];
+   blockSumD(sum, v.partial + (size_t)blockIdx.x * VIRIAL_N);
 }
 
 // the rows of partials -> out[VIRIAL_N], in a fixed order
 __global__ __launch_bounds__(256)
 void Virial_Final(const double* __restrict__ partial, int nPartial, double* __restrict__ out)
 {
-   __shared__ double sAcc[4][VIRIAL_N];
-   const int lane = laneId(), wave = (int)threadIdx.x >> 6;
-   for (int c = 0; c < VIRIAL_N; ++c) {
-      double a = 0.0;
-      for (int i = threadIdx.x; i < nPartial; i += blockDim.x) a += partial[(size_t)i * VIRIAL_N + c];
-      a = waveSumD(a);
-      if (lane == 0) sAcc[wave][c] = a;
-   }
-   __syncthreads();
-   if (threadIdx.x < VIRIAL_N) {
-      const int c = threadIdx.x;
-      out[c] = (sAcc[0][c] + sAcc[1][c]) + (sAcc[2][c] + sAcc[3][c]);
-   }
+   double acc[VIRIAL_N];
+#pragma unroll
+   for (int c = 0; c < VIRIAL_N; ++c) acc[c] = 0.0;
+   for (int i = threadIdx.x; i < nPartial; i += blockDim.x)
+#pragma unroll
+      for (int c = 0; c < VIRIAL_N; ++c) acc[c] += partial[(size_t)i * VIRIAL_N + c];
+   blockSumD(acc, out);
 }

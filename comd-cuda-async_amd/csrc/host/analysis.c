@@ -1,0 +1,309 @@
+/* analysis.c -- the host entries of the analyses (not in the reference; comd_host.h): pressure, g(r), centro-symmetry, common neighbour analysis, per-atom
+ * stress and strain, displacements.  Each is a call into include/comd_hip.h for this rank's share and a sum over the ranks. */
+#include "comd_host.h"
+#include "slot_gather.h"
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+void computePressure(SimFlat* s)
+{
+   real_t local[12], sum[12];
+   computeVirial(&s->gpu, local);
+   addRealParallel(local, sum, 12);
+   for (int c = 0; c < 6; ++c) { s->W[c] = sum[c]; s->K[c] = sum[6 + c]; }
+   s->V = s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2];
+}
+
+int comdPairHistogram(SimFlat* s, int nBins, double rMax, double* outCounts)
+{
+   const double cutoff = s->pot->cutoff;
+   if (rMax <= 0.0) rMax = cutoff;
+   if (nBins < 1 || nBins > COMD_RDF_MAX_BINS || !(rMax <= cutoff)) return -1;
+   uint64_t* local = (uint64_t*)malloc((size_t)nBins * sizeof(uint64_t));
+   double* mine = (double*)malloc((size_t)nBins * sizeof(double));
+   computePairHistogram(&s->gpu, nBins, (real_t)rMax, local);
+   for (int k = 0; k < nBins; ++k) mine[k] = (double)local[k];
+   addDoubleParallel(mine, outCounts, nBins);
+   for (int k = 0; k < nBins; ++k) outCounts[k] *= 0.5;
+   free(local); free(mine);
+   return 0;
+}
+
+/* ---- centro-symmetry and coordination (not in the reference; comd_host.h) ---- */
+double comdDefaultCoordRadius(SimFlat* s)
+{
+   const double r = 0.5 * (M_SQRT1_2 + 1.0) * s->lat, cutoff = s->pot->cutoff;
+   return r < cutoff ? r : cutoff;
+}
+
+/* ---- the by-gid gather of comdCentroSymmetry, comdCommonNeighbors, comdAtomStress and comdAtomStrain ----
+ * An output is out[nGlobal][width], filled from `width` consecutive by-slot planes of one kind (slot_gather.h); the real_t outputs come first.  `run` launches the
+ * kernel and copies its planes into plane[k], one pointer per output. */
+typedef struct { void* out; int kind, width; } GidOutput;
+typedef void (*SlotKernel)(SimFlat* s, void* const* plane, const void* arg);
+
+static void gatherByGid(SimFlat* s, SlotKernel run, const void* arg, const GidOutput* out, int nOut)
+{
+   const int cap = s->boxes->maxAtoms, nLocalBoxes = s->boxes->nLocalBoxes;
+   const size_t nSlots = (size_t)nLocalBoxes * cap, n = (size_t)s->atoms->nGlobal;
+   /* staging for the by-slot arrays, kept with the simulation: fresh pages for 64 MB at 80^3 would cost more than the kernel */
+   size_t need = (nSlots + 1 + (size_t)nLocalBoxes + 1) * sizeof(int), bytes[2];
+   for (int k = 0; k < nOut; ++k) need += bytes[k] = ((size_t)out[k].width * nSlots + 1) * (out[k].kind == SLOT_REAL ? sizeof(real_t) : sizeof(int));
+   if (need > s->analysisStageBytes) { free(s->analysisStage); s->analysisStage = malloc(need); s->analysisStageBytes = need; }
+   char* at = (char*)s->analysisStage;
+   void* plane[2];
+   for (int k = 0; k < nOut; ++k) { plane[k] = at; at += bytes[k]; }
+   int* gid = (int*)at;
+   int* nAtoms = gid + nSlots + 1;
+   run(s, plane, arg);          /* blocks: the stream is drained, the two copies below see the same state */
+   comdMemcpyDtoH(gid, s->gpu.atoms.gid, (long)(nSlots * sizeof(int)));
+   comdMemcpyDtoH(nAtoms, s->gpu.boxes.nAtoms, (long)((size_t)nLocalBoxes * sizeof(int)));
+   /* one rank writes straight into the caller's arrays */
+   const int one = getNRanks() == 1;
+   void* mine[2];
+   SlotPlane planes[8];
+   int nPlanes = 0;
+   for (int k = 0; k < nOut; ++k) {
+      const size_t len = (size_t)out[k].width * n;
+      mine[k] = one ? out[k].out : malloc((len ? len : 1) * (out[k].kind == SLOT_INT ? sizeof(int) : sizeof(double)));
+      for (int c = 0; c < out[k].width; ++c) {
+         const size_t from = (size_t)c * nSlots * (out[k].kind == SLOT_REAL ? sizeof(real_t) : sizeof(int));
+         planes[nPlanes++] = (SlotPlane){ (const char*)plane[k] + from, out[k].kind, mine[k], (size_t)out[k].width, (size_t)c };
+      }
+   }
+   slotGather(nAtoms, gid, nLocalBoxes, cap, n, planes, nPlanes);
+   if (one) return;
+   /* every other rank holds 0 for a gid (and inf + 0 = inf, NaN + 0 = NaN: an atom without a value stays one) */
+   startTimer(commReduceTimer);
+   for (int k = 0; k < nOut; ++k) {
+      if (out[k].kind == SLOT_INT) addIntParallelLong((int*)mine[k], (int*)out[k].out, (size_t)out[k].width * n);
+      else addDoubleParallelLong((double*)mine[k], (double*)out[k].out, (size_t)out[k].width * n);
+   }
+   stopTimer(commReduceTimer);
+   for (int k = 0; k < nOut; ++k) free(mine[k]);
+}
+
+static void runCentroSymmetry(SimFlat* s, void* const* plane, const void* rCoord)
+{
+   computeCentroSymmetry(&s->gpu, *(const real_t*)rCoord, (real_t*)plane[0], (int*)plane[1]);
+}
+
+int comdCentroSymmetry(SimFlat* s, double rCoord, double* cspByGid, double* coordByGid)
+{
+   if (rCoord <= 0.0) rCoord = comdDefaultCoordRadius(s);
+   if (!(rCoord <= s->pot->cutoff)) return -1;
+   const real_t r = (real_t)rCoord;
+   const GidOutput out[2] = { { cspByGid, SLOT_REAL, 1 }, { coordByGid, SLOT_INT_AS_DOUBLE, 1 } };
+   gatherByGid(s, runCentroSymmetry, &r, out, 2);
+   return 0;
+}
+
+/* ---- adaptive common neighbour analysis (not in the reference; comd_host.h) ---- */
+static void runCommonNeighbors(SimFlat* s, void* const* plane, const void* none) { computeCommonNeighbors(&s->gpu, (int*)plane[0]); }
+
+int comdCommonNeighbors(SimFlat* s, int* typeByGid, long long counts[5])
+{
+   const size_t n = (size_t)s->atoms->nGlobal;
+   const GidOutput out = { typeByGid, SLOT_INT, 1 };
+   gatherByGid(s, runCommonNeighbors, NULL, &out, 1);
+   for (int t = 0; t < 5; ++t) counts[t] = 0;
+   for (size_t g = 0; g < n; ++g) { const int t = typeByGid[g]; counts[t >= 0 && t <= 4 ? t : 0] += 1; }
+   return 0;
+}
+
+/* ---- per-atom virial stress (not in the reference; comd_host.h) ---- */
+static void runAtomStress(SimFlat* s, void* const* plane, const void* withKinetic) { computeAtomStress(&s->gpu, *(const int*)withKinetic, (real_t*)plane[0]); }
+
+int comdAtomStress(SimFlat* s, int withKinetic, double* stressByGid)
+{
+   if (!s->gpu.boxes.nAtoms) return -1;
+   const GidOutput out = { stressByGid, SLOT_REAL, 6 };
+   gatherByGid(s, runAtomStress, &withKinetic, &out, 1);
+   return 0;
+}
+
+int comdStressSummary(SimFlat* s, int withKinetic, double* out7)
+{
+   if (!s->gpu.boxes.nAtoms) return -1;
+   const double n = (double)s->atoms->nGlobal;
+   const double omega = (double)s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2] / (n > 0.0 ? n : 1.0);
+   double local[7];
+   computeAtomStress(&s->gpu, withKinetic, NULL);
+   computeAtomStressSummary(&s->gpu, omega, local);
+   const int nRanks = getNRanks(), me = getMyRank();
+   if (nRanks > 1) {
+      /* the sums add; the extremes and the gid go through one slot per rank of a summed vector (no MIN/MAX of doubles in the transport), taken in rank order */
+      double* mine = (double*)calloc(2 * (size_t)(3 + 4 * nRanks), sizeof(double));
+      double* all = mine + 3 + 4 * (size_t)nRanks;
+      mine[0] = local[0]; mine[1] = local[3]; mine[2] = local[6];
+      if (local[6] > 0.0) { double* slot = mine + 3 + 4 * (size_t)me; slot[0] = local[1]; slot[1] = local[2]; slot[2] = local[4]; slot[3] = local[5] + 1.0; }
+      startTimer(commReduceTimer);
+      addDoubleParallel(mine, all, 3 + 4 * nRanks);
+      stopTimer(commReduceTimer);
+      local[0] = all[0]; local[3] = all[1]; local[6] = all[2];
+      local[1] = INFINITY; local[2] = -INFINITY; local[4] = -INFINITY; local[5] = -1.0;
+      for (int r = 0; r < nRanks; ++r) {
+         const double* slot = all + 3 + 4 * (size_t)r;
+         if (slot[3] == 0.0) continue;          /* a rank without atoms */
+         const double g = slot[3] - 1.0;
+         if (slot[0] < local[1]) local[1] = slot[0];
+         if (slot[1] > local[2]) local[2] = slot[1];
+         if (local[5] < 0.0 || slot[2] > local[4] || (slot[2] == local[4] && g < local[5])) { local[4] = slot[2]; local[5] = g; }
+      }
+      free(mine);
+   }
+   const double N = local[6];
+   out7[0] = N > 0.0 ? local[0] / N : 0.0; out7[1] = local[1]; out7[2] = local[2];
+   out7[3] = N > 0.0 ? local[3] / N : 0.0; out7[4] = local[4]; out7[5] = local[5]; out7[6] = N;
+   return 0;
+}
+
+/* ---- per-atom strain and D^2min (not in the reference; comd_host.h) ---- */
+int comdStrainReference(SimFlat* s, int on)
+{
+   if (!s->gpu.boxes.nAtoms) return -1;
+   const int nGlobal = s->atoms->nGlobal;
+   int fail = comdStrainReferenceGpu(&s->gpu, nGlobal, on), anyFail = 0;
+   maxIntParallel(&fail, &anyFail, 1);
+   if (anyFail && !fail) comdStrainReferenceGpu(&s->gpu, nGlobal, 0);      /* all ranks or none */
+   s->strainHasRef = on != 0 && !anyFail;
+   if (!s->strainHasRef) return anyFail;
+   for (int a = 0; a < 3; ++a) s->strainL0[a] = s->gpu.strainL0[a] = (double)s->domain->globalExtent[a];
+   if (getNRanks() > 1) {
+      /* halo neighbours need the records of the other ranks' atoms: every other rank holds 0 for a gid */
+      const size_t n = 4 * (size_t)nGlobal;
+      double* mine = (double*)malloc(2 * n * sizeof(double));
+      double* all = mine + n;
+      comdMemcpyDtoH(mine, s->gpu.strainRefBuf, (long)(n * sizeof(double)));
+      startTimer(commReduceTimer);
+      addDoubleParallelLong(mine, all, n);
+      stopTimer(commReduceTimer);
+      comdMemcpyHtoD(s->gpu.strainRefBuf, all, (long)(n * sizeof(double)));
+      free(mine);
+   }
+   return 0;
+}
+
+int comdStrainReferenceBox(SimFlat* s, double* L0)
+{
+   if (!s->strainHasRef) return -1;
+   for (int a = 0; a < 3; ++a) L0[a] = s->strainL0[a];
+   return 0;
+}
+
+/* the radius the two entries launch with: the default for rCut <= 0; 0 when the entry has to refuse */
+static double strainRadius(SimFlat* s, double rCut)
+{
+   if (!s->gpu.boxes.nAtoms || !s->strainHasRef) return 0.0;
+   if (rCut <= 0.0) rCut = comdDefaultCoordRadius(s);
+   return rCut <= s->pot->cutoff ? rCut : 0.0;
+}
+
+static void runAtomStrain(SimFlat* s, void* const* plane, const void* rCut) { computeAtomStrain(&s->gpu, *(const real_t*)rCut, (real_t*)plane[0], (int*)plane[1]); }
+
+int comdAtomStrain(SimFlat* s, double rCut, double* strainByGid7, int* countByGid)
+{
+   rCut = strainRadius(s, rCut);
+   if (!(rCut > 0.0)) return -1;
+   const real_t r = (real_t)rCut;
+   const GidOutput out[2] = { { strainByGid7, SLOT_REAL, 7 }, { countByGid, SLOT_INT, 1 } };
+   gatherByGid(s, runAtomStrain, &r, out, 2);
+   return 0;
+}
+
+int comdStrainSummary(SimFlat* s, double rCut, double threshold, double* out9)
+{
+   rCut = strainRadius(s, rCut);
+   if (!(rCut > 0.0) || !(threshold > 0.0)) return -1;
+   double local[9];          /* sum gamma, max gamma, gid, sum vol, sum D^2, max D^2, valid, invalid, above (computeAtomStrainSummary) */
+   computeAtomStrain(&s->gpu, (real_t)rCut, NULL, NULL);
+   computeAtomStrainSummary(&s->gpu, threshold, local);
+   const int nRanks = getNRanks(), me = getMyRank();
+   if (nRanks > 1) {
+      /* the sums add; the extremes and the gid go through one slot per rank of a summed vector (no MAX of doubles in the transport), taken in rank order */
+      double* mine = (double*)calloc(2 * (size_t)(6 + 3 * nRanks), sizeof(double));
+      double* all = mine + 6 + 3 * (size_t)nRanks;
+      mine[0] = local[0]; mine[1] = local[3]; mine[2] = local[4]; mine[3] = local[6]; mine[4] = local[7]; mine[5] = local[8];
+      if (local[6] > 0.0) { double* slot = mine + 6 + 3 * (size_t)me; slot[0] = local[1]; slot[1] = local[2] + 1.0; slot[2] = local[5]; }
+      startTimer(commReduceTimer);
+      addDoubleParallel(mine, all, 6 + 3 * nRanks);
+      stopTimer(commReduceTimer);
+      local[0] = all[0]; local[3] = all[1]; local[4] = all[2]; local[6] = all[3]; local[7] = all[4]; local[8] = all[5];
+      local[1] = -INFINITY; local[2] = -1.0; local[5] = -INFINITY;
+      for (int r = 0; r < nRanks; ++r) {
+         const double* slot = all + 6 + 3 * (size_t)r;
+         if (slot[1] == 0.0) continue;          /* a rank without valid atoms */
+         const double g = slot[1] - 1.0;
+         if (local[2] < 0.0 || slot[0] > local[1] || (slot[0] == local[1] && g < local[2])) { local[1] = slot[0]; local[2] = g; }
+         if (slot[2] > local[5]) local[5] = slot[2];
+      }
+      free(mine);
+   }
+   const double N = local[6];
+   out9[0] = N + local[7]; out9[1] = local[7];
+   out9[2] = N > 0.0 ? local[0] / N : 0.0; out9[3] = N > 0.0 ? local[1] : 0.0; out9[4] = local[2];
+   out9[5] = N > 0.0 ? local[3] / N : 0.0; out9[6] = N > 0.0 ? local[4] / N : 0.0; out9[7] = N > 0.0 ? local[5] : 0.0; out9[8] = local[8];
+   return 0;
+}
+
+/* ---- displacement tracking (not in the reference; comd_host.h) ---- */
+int comdTrackDisplacement(SimFlat* s, int on)
+{
+   int fail = comdTrackDisplacementGpu(&s->gpu, s->atoms->nGlobal, on), anyFail = 0;
+   maxIntParallel(&fail, &anyFail, 1);
+   if (anyFail && !fail) comdTrackDisplacementGpu(&s->gpu, s->atoms->nGlobal, 0);      /* all ranks or none */
+   s->trackDisp = on != 0 && !anyFail;
+   return anyFail;
+}
+
+#define COMD_DISP_UNIT (1.0 / 4294967296.0)      /* Angstroms per unit of the device records */
+
+int comdDisplacements(SimFlat* s, double* out)
+{
+   if (!s->trackDisp) return -1;
+   const size_t n = (size_t)s->atoms->nGlobal;
+   int64_t* raw = (int64_t*)malloc(4 * n * sizeof(int64_t));
+   comdCopyDisplacementsGpu(&s->gpu, raw);
+   if (getNRanks() == 1) {
+      for (size_t g = 0; g < n; ++g) for (int c = 0; c < 3; ++c) out[3 * g + c] = (double)raw[4 * g + c] * COMD_DISP_UNIT;
+      free(raw);
+      return 0;
+   }
+   /* the ranks' parts as doubles (exact below 2^53), summed */
+   const int64_t top = (int64_t)1 << 53;
+   double* mine = (double*)malloc(3 * n * sizeof(double));
+   int bad = 0, anyBad = 0;
+   for (size_t g = 0; g < n; ++g)
+      for (int c = 0; c < 3; ++c) {
+         const int64_t v = raw[4 * g + c];
+         if (v >= top || v <= -top) bad = 1;
+         mine[3 * g + c] = (double)v;
+      }
+   free(raw);
+   maxIntParallel(&bad, &anyBad, 1);
+   if (!anyBad) {
+      startTimer(commReduceTimer);
+      addDoubleParallelLong(mine, out, 3 * n);
+      stopTimer(commReduceTimer);
+      for (size_t k = 0; k < 3 * n; ++k) out[k] *= COMD_DISP_UNIT;
+   }
+   free(mine);
+   return anyBad ? -2 : 0;
+}
+
+int comdMsd(SimFlat* s, double* out7)
+{
+   if (!s->trackDisp) return -1;
+   const size_t n = (size_t)s->atoms->nGlobal;
+   out7[6] = (double)n;
+   if (getNRanks() == 1) { computeDisplacementSums(&s->gpu, out7); return 0; }
+   double* d = (double*)malloc(3 * n * sizeof(double));
+   const int rc = comdDisplacements(s, d);
+   for (int c = 0; c < 6; ++c) out7[c] = 0.0;
+   if (rc == 0)
+      for (size_t g = 0; g < n; ++g)
+         for (int c = 0; c < 3; ++c) { const double v = d[3 * g + c]; out7[c] += v; out7[3 + c] += v * v; }
+   free(d);
+   return rc;
+}

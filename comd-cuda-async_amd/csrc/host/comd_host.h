@@ -107,6 +107,8 @@ void sendReceiveDevice2Sized(void* sendM, int nSendM, int dstM, void* recvP, int
 void addIntParallel(int* sendBuf, int* recvBuf, int count);
 void addRealParallel(real_t* sendBuf, real_t* recvBuf, int count);
 void addDoubleParallel(double* sendBuf, double* recvBuf, int count);
+void addIntParallelLong(int* sendBuf, int* recvBuf, size_t count);            /* counts beyond an int: in chunks of 2^28 */
+void addDoubleParallelLong(double* sendBuf, double* recvBuf, size_t count);
 void maxIntParallel(int* sendBuf, int* recvBuf, int count);
 void bcastParallel(void* buf, int len, int root);
 
@@ -345,16 +347,14 @@ typedef struct SimFlatSt {
    double* cspRows;                 /* [cspSamples][7]: step, defects, atoms with fewer than 12 neighbours, mean and max of the finite csp, mean coordination, atoms with coordination != 12 */
    int cspSamples, cspCap;
    double* cspLast;                 /* [2 nGlobal]: csp and coordination by gid of the last sample (--cspDump) */
-   void* cspStage;                  /* comdCentroSymmetry: host staging for the by-slot results, the gids and the occupancies, kept between calls */
-   size_t cspStageBytes;
+   void* analysisStage;             /* the by-gid analyses (analysis.c): host staging for the by-slot results, the gids and the occupancies, kept between calls */
+   size_t analysisStageBytes;
    int cspDefectsNow;               /* the Defects column of printThings: the last sample */
    int cna;                         /* --cna: comdMain samples the structure types at every printed step */
    char cnaFile[1024], cnaDump[1024];
    long long* cnaRows;              /* [cnaSamples][5]: step, atoms of type OTHER, FCC, HCP, ICO */
    int cnaSamples, cnaCap;
    int* cnaLast;                    /* [nGlobal]: type by gid of the last sample (--cnaDump) */
-   void* cnaStage;                  /* comdCommonNeighbors: host staging for the by-slot types, the gids and the occupancies, kept between calls */
-   size_t cnaStageBytes;
    long long cnaNonFccNow;          /* the NonFCC column of printThings: the last sample */
    /* box deformation (--erateX/Y/Z, comdSetBox, comdSetStrainRate): the box is box0 (1 + strain), strain = deformEpsBase + erate * deformTime / 1000 */
    double box0[3];                  /* the global extents the simulation was created with */
@@ -377,8 +377,6 @@ typedef struct SimFlatSt {
    double* stressRows;              /* [stressSamples][8]: step, the seven values of comdStressSummary (eV/A^3) */
    int stressSamples, stressCap;
    double stressMaxVmNow;           /* the MaxVM(GPa) column of printThings: the last sample, in eV/A^3 */
-   void* stressStage;               /* comdAtomStress: host staging for the by-slot planes, the gids and the occupancies, kept between calls */
-   size_t stressStageBytes;
    int strainHasRef;                /* comdStrainReference: the device holds a reference table */
    double strainL0[3];              /* the global box when the reference was taken */
    int strain, strainRef;           /* --strain: comdMain takes the reference at global step strainRef and samples the summary at every printed step from then on */
@@ -387,8 +385,6 @@ typedef struct SimFlatSt {
    double* strainRows;              /* [strainSamples][10]: step, the nine values of comdStrainSummary */
    int strainSamples, strainCap;
    double strainMaxShearNow;        /* the MaxShear column of printThings: the last sample, 0 before the reference */
-   void* strainStage;               /* comdAtomStrain: host staging for the by-slot planes, the counts, the gids and the occupancies, kept between calls */
-   size_t strainStageBytes;
 } SimFlat;
 
 SimFlat* initSimulation(Command cmd);

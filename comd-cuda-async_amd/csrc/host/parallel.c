@@ -101,6 +101,21 @@ void addDoubleParallel(double* sendBuf, double* recvBuf, int count)
    if (nRanks > 1 || loopback) transport.allreduce(transport.ctx, recvBuf, count, 1);
 }
 
+/* the same for counts beyond an int: in chunks of 2^28 elements */
+#define PARALLEL_LONG_CHUNK ((size_t)1 << 28)
+
+void addIntParallelLong(int* sendBuf, int* recvBuf, size_t count)
+{
+   for (size_t o = 0; o < count; o += PARALLEL_LONG_CHUNK)
+      addIntParallel(sendBuf + o, recvBuf + o, (int)(count - o < PARALLEL_LONG_CHUNK ? count - o : PARALLEL_LONG_CHUNK));
+}
+
+void addDoubleParallelLong(double* sendBuf, double* recvBuf, size_t count)
+{
+   for (size_t o = 0; o < count; o += PARALLEL_LONG_CHUNK)
+      addDoubleParallel(sendBuf + o, recvBuf + o, (int)(count - o < PARALLEL_LONG_CHUNK ? count - o : PARALLEL_LONG_CHUNK));
+}
+
 void maxIntParallel(int* sendBuf, int* recvBuf, int count)
 {
    memmove(recvBuf, sendBuf, (size_t)count * sizeof(int));

@@ -306,11 +306,11 @@ void destroySimulation(SimFlat** ps)
    free(s->ljTable);
    free(s->rdfSum);
    free(s->msdRows);
-   free(s->cspRows); free(s->cspLast); free(s->cspStage);
-   free(s->cnaRows); free(s->cnaLast); free(s->cnaStage);
+   free(s->cspRows); free(s->cspLast); free(s->analysisStage);
+   free(s->cnaRows); free(s->cnaLast);
    free(s->deformRows);
-   free(s->stressRows); free(s->stressStage);
-   free(s->strainRows); free(s->strainStage);
+   free(s->stressRows);
+   free(s->strainRows);
    free(s->species); free(s->domain); free(s);
    *ps = NULL;
 }
@@ -422,11 +422,31 @@ static void startMsd(SimFlat* s)
    if (comdTrackDisplacement(s, 1) != 0) { printf("Error: --msd: no device memory for the displacement records of %d atoms.\n", s->atoms->nGlobal); exit(-1); }
 }
 
+/* positions by gid over all ranks, [nGlobal][3], malloc'd: collective */
+static double* positionsByGid(SimFlat* s)
+{
+   const size_t n = (size_t)s->atoms->nGlobal;
+   double* mine = (double*)calloc(n ? 3 * n : 1, sizeof(double));
+   double* pos = (double*)malloc((n ? 3 * n : 1) * sizeof(double));
+   comdGatherByGid(s, 0, mine);
+   addDoubleParallelLong(mine, pos, 3 * n);
+   free(mine);
+   return pos;
+}
+
+/* the next row of a table of samples that grows by doubling: rows[cap][width] elements of `size` bytes */
+static void* nextRow(void* rowsPtr, int* cap, int* samples, size_t width, size_t size)
+{
+   void* rows;
+   memcpy(&rows, rowsPtr, sizeof rows);          /* rowsPtr: the address of a double* or a long long* */
+   if (*samples == *cap) { *cap = *cap ? 2 * *cap : 64; rows = realloc(rows, (size_t)*cap * width * size); memcpy(rowsPtr, &rows, sizeof rows); }
+   return (char*)rows + width * size * (size_t)(*samples)++;
+}
+
 /* --msd: one more row {step, sum d (3), sum d^2 (3), N} */
 static void sampleMsd(SimFlat* s, int iStep)
 {
-   if (s->msdSamples == s->msdCap) { s->msdCap = s->msdCap ? 2 * s->msdCap : 64; s->msdRows = (double*)realloc(s->msdRows, (size_t)s->msdCap * 8 * sizeof(double)); }
-   double* row = s->msdRows + 8 * (size_t)s->msdSamples++;
+   double* row = (double*)nextRow(&s->msdRows, &s->msdCap, &s->msdSamples, 8, sizeof(double));
    row[0] = (double)iStep;
    if (comdMsd(s, row + 1) != 0) { printf("Error: --msd: the displacements could not be summed.\n"); exit(-1); }
    s->msdNow = (row[4] + row[5] + row[6]) / row[7];
@@ -482,8 +502,7 @@ static void sampleCsp(SimFlat* s, int iStep)
    const size_t n = (size_t)s->atoms->nGlobal;
    if (!s->cspLast) s->cspLast = (double*)malloc((n ? 2 * n : 1) * sizeof(double));
    if (comdCentroSymmetry(s, s->cspCoord, s->cspLast, s->cspLast + n) != 0) { printf("Error: --csp --cspCoord %g was refused.\n", s->cspCoord); exit(-1); }
-   if (s->cspSamples == s->cspCap) { s->cspCap = s->cspCap ? 2 * s->cspCap : 64; s->cspRows = (double*)realloc(s->cspRows, (size_t)s->cspCap * 7 * sizeof(double)); }
-   double* row = s->cspRows + 7 * (size_t)s->cspSamples++;
+   double* row = (double*)nextRow(&s->cspRows, &s->cspCap, &s->cspSamples, 7, sizeof(double));
    double defects = 0.0, few = 0.0, sum = 0.0, top = 0.0, coordSum = 0.0, not12 = 0.0;
    for (size_t g = 0; g < n; ++g) {
       const double c = s->cspLast[g], z = s->cspLast[n + g];
@@ -505,12 +524,7 @@ static void writeCsp(FILE* yaml, SimFlat* s)
    const size_t n = (size_t)s->atoms->nGlobal;
    double* pos = NULL;
    if (s->cspDump[0]) {          /* collective: before the other ranks leave */
-      double* mine = (double*)calloc(n ? 3 * n : 1, sizeof(double));
-      pos = (double*)malloc((n ? 3 * n : 1) * sizeof(double));
-      comdGatherByGid(s, 0, mine);
-      const size_t chunk = (size_t)1 << 28;
-      for (size_t o = 0; o < 3 * n; o += chunk) addDoubleParallel(mine + o, pos + o, (int)(3 * n - o < chunk ? 3 * n - o : chunk));
-      free(mine);
+      pos = positionsByGid(s);
    }
    if (!printRank()) { free(pos); return; }
    const int samples = s->cspSamples;
@@ -556,8 +570,7 @@ static void sampleCna(SimFlat* s, int iStep)
    if (!s->cnaLast) s->cnaLast = (int*)malloc((n ? n : 1) * sizeof(int));
    long long counts[5];
    comdCommonNeighbors(s, s->cnaLast, counts);
-   if (s->cnaSamples == s->cnaCap) { s->cnaCap = s->cnaCap ? 2 * s->cnaCap : 64; s->cnaRows = (long long*)realloc(s->cnaRows, (size_t)s->cnaCap * 5 * sizeof(long long)); }
-   long long* row = s->cnaRows + 5 * (size_t)s->cnaSamples++;
+   long long* row = (long long*)nextRow(&s->cnaRows, &s->cnaCap, &s->cnaSamples, 5, sizeof(long long));
    row[0] = iStep; row[1] = counts[COMD_CNA_OTHER]; row[2] = counts[COMD_CNA_FCC]; row[3] = counts[COMD_CNA_HCP]; row[4] = counts[COMD_CNA_ICO];
    s->cnaNonFccNow = (long long)n - counts[COMD_CNA_FCC];
 }
@@ -569,12 +582,7 @@ static void writeCna(FILE* yaml, SimFlat* s)
    const size_t n = (size_t)s->atoms->nGlobal;
    double* pos = NULL;
    if (s->cnaDump[0]) {          /* collective: before the other ranks leave */
-      double* mine = (double*)calloc(n ? 3 * n : 1, sizeof(double));
-      pos = (double*)malloc((n ? 3 * n : 1) * sizeof(double));
-      comdGatherByGid(s, 0, mine);
-      const size_t chunk = (size_t)1 << 28;
-      for (size_t o = 0; o < 3 * n; o += chunk) addDoubleParallel(mine + o, pos + o, (int)(3 * n - o < chunk ? 3 * n - o : chunk));
-      free(mine);
+      pos = positionsByGid(s);
    }
    if (!printRank()) { free(pos); return; }
    const int samples = s->cnaSamples;
@@ -619,8 +627,7 @@ static void writeCna(FILE* yaml, SimFlat* s)
  * the tensors computePressure has just left in W, K, V */
 static void sampleDeform(SimFlat* s, int iStep)
 {
-   if (s->deformSamples == s->deformCap) { s->deformCap = s->deformCap ? 2 * s->deformCap : 64; s->deformRows = (double*)realloc(s->deformRows, (size_t)s->deformCap * 15 * sizeof(double)); }
-   double* row = s->deformRows + 15 * (size_t)s->deformSamples++;
+   double* row = (double*)nextRow(&s->deformRows, &s->deformCap, &s->deformSamples, 15, sizeof(double));
    row[0] = (double)iStep; row[1] = iStep * s->dt;
    for (int a = 0; a < 3; ++a) { row[5 + a] = (double)s->domain->globalExtent[a]; row[2 + a] = row[5 + a] / s->box0[a] - 1.0; }
    row[8] = (double)s->V;
@@ -663,8 +670,7 @@ static void writeDeform(FILE* yaml, SimFlat* s)
 /* --stress: one more row {step, mean / min / max hydrostatic pressure, mean / max von Mises stress, the gid of the max, N} from the device reduction (eV/A^3) */
 static void sampleStress(SimFlat* s, int iStep)
 {
-   if (s->stressSamples == s->stressCap) { s->stressCap = s->stressCap ? 2 * s->stressCap : 64; s->stressRows = (double*)realloc(s->stressRows, (size_t)s->stressCap * 8 * sizeof(double)); }
-   double* row = s->stressRows + 8 * (size_t)s->stressSamples++;
+   double* row = (double*)nextRow(&s->stressRows, &s->stressCap, &s->stressSamples, 8, sizeof(double));
    row[0] = (double)iStep;
    if (comdStressSummary(s, 1, row + 1) != 0) { printf("Error: --stress needs the device state.\n"); exit(-1); }
    s->stressMaxVmNow = row[5];
@@ -679,13 +685,8 @@ static void writeStress(FILE* yaml, SimFlat* s, int iStep)
    const double omega = (double)s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2] / (n ? (double)n : 1.0);
    double *pos = NULL, *ten = NULL;
    if (s->stressDump[0]) {          /* collective: before the other ranks leave */
-      double* mine = (double*)calloc(n ? 3 * n : 1, sizeof(double));
-      pos = (double*)malloc((n ? 3 * n : 1) * sizeof(double));
+      pos = positionsByGid(s);
       ten = (double*)malloc((n ? 6 * n : 1) * sizeof(double));
-      comdGatherByGid(s, 0, mine);
-      const size_t chunk = (size_t)1 << 28;
-      for (size_t o = 0; o < 3 * n; o += chunk) addDoubleParallel(mine + o, pos + o, (int)(3 * n - o < chunk ? 3 * n - o : chunk));
-      free(mine);
       if (comdAtomStress(s, 1, ten) != 0) { printf("Error: --stressDump needs the device state.\n"); exit(-1); }
    }
    if (!printRank()) { free(pos); free(ten); return; }
@@ -751,8 +752,7 @@ static void startStrain(SimFlat* s)
  * the threshold} from the device reduction */
 static void sampleStrain(SimFlat* s, int iStep)
 {
-   if (s->strainSamples == s->strainCap) { s->strainCap = s->strainCap ? 2 * s->strainCap : 64; s->strainRows = (double*)realloc(s->strainRows, (size_t)s->strainCap * 10 * sizeof(double)); }
-   double* row = s->strainRows + 10 * (size_t)s->strainSamples++;
+   double* row = (double*)nextRow(&s->strainRows, &s->strainCap, &s->strainSamples, 10, sizeof(double));
    row[0] = (double)iStep;
    if (comdStrainSummary(s, s->strainCutoff, s->strainThreshold, row + 1) != 0) { printf("Error: --strain needs the device state and a reference.\n"); exit(-1); }
    s->strainMaxShearNow = row[4];
@@ -773,14 +773,9 @@ static void writeStrain(FILE* yaml, SimFlat* s, int iStep)
    double *pos = NULL, *ten = NULL;
    int* cnt = NULL;
    if (s->strainDump[0]) {          /* collective: before the other ranks leave */
-      double* mine = (double*)calloc(n ? 3 * n : 1, sizeof(double));
-      pos = (double*)malloc((n ? 3 * n : 1) * sizeof(double));
+      pos = positionsByGid(s);
       ten = (double*)malloc((n ? 7 * n : 1) * sizeof(double));
       cnt = (int*)malloc((n ? n : 1) * sizeof(int));
-      comdGatherByGid(s, 0, mine);
-      const size_t chunk = (size_t)1 << 28;
-      for (size_t o = 0; o < 3 * n; o += chunk) addDoubleParallel(mine + o, pos + o, (int)(3 * n - o < chunk ? 3 * n - o : chunk));
-      free(mine);
       if (comdAtomStrain(s, s->strainCutoff, ten, cnt) != 0) { printf("Error: --strainDump needs the device state and a reference.\n"); exit(-1); }
    }
    if (!printRank()) { free(pos); free(ten); free(cnt); return; }

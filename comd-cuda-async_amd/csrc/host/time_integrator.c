@@ -205,360 +205,6 @@ void kineticEnergyGpu(SimFlat* s)
    s->eKinetic = eSum[1];
 }
 
-void computePressure(SimFlat* s)
-{
-   real_t local[12], sum[12];
-   computeVirial(&s->gpu, local);
-   addRealParallel(local, sum, 12);
-   for (int c = 0; c < 6; ++c) { s->W[c] = sum[c]; s->K[c] = sum[6 + c]; }
-   s->V = s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2];
-}
-
-int comdPairHistogram(SimFlat* s, int nBins, double rMax, double* outCounts)
-{
-   const double cutoff = s->pot->cutoff;
-   if (rMax <= 0.0) rMax = cutoff;
-   if (nBins < 1 || nBins > COMD_RDF_MAX_BINS || !(rMax <= cutoff)) return -1;
-   uint64_t* local = (uint64_t*)malloc((size_t)nBins * sizeof(uint64_t));
-   double* mine = (double*)malloc((size_t)nBins * sizeof(double));
-   computePairHistogram(&s->gpu, nBins, (real_t)rMax, local);
-   for (int k = 0; k < nBins; ++k) mine[k] = (double)local[k];
-   addDoubleParallel(mine, outCounts, nBins);
-   for (int k = 0; k < nBins; ++k) outCounts[k] *= 0.5;
-   free(local); free(mine);
-   return 0;
-}
-
-/* ---- centro-symmetry and coordination (not in the reference; comd_host.h) ---- */
-double comdDefaultCoordRadius(SimFlat* s)
-{
-   const double r = 0.5 * (M_SQRT1_2 + 1.0) * s->lat, cutoff = s->pot->cutoff;
-   return r < cutoff ? r : cutoff;
-}
-
-int comdCentroSymmetry(SimFlat* s, double rCoord, double* cspByGid, double* coordByGid)
-{
-   const double cutoff = s->pot->cutoff;
-   if (rCoord <= 0.0) rCoord = comdDefaultCoordRadius(s);
-   if (!(rCoord <= cutoff)) return -1;
-   const int cap = s->boxes->maxAtoms, nLocalBoxes = s->boxes->nLocalBoxes;
-   const size_t nSlots = (size_t)nLocalBoxes * cap, n = (size_t)s->atoms->nGlobal;
-   /* staging for the by-slot arrays, kept with the simulation: fresh pages for 64 MB at 80^3 would cost more than the kernel */
-   const size_t need = (nSlots + 1) * (sizeof(real_t) + 2 * sizeof(int)) + ((size_t)nLocalBoxes + 1) * sizeof(int);
-   if (need > s->cspStageBytes) { free(s->cspStage); s->cspStage = malloc(need); s->cspStageBytes = need; }
-   real_t* csp = (real_t*)s->cspStage;
-   int* coord = (int*)(csp + nSlots + 1);
-   int* gid = coord + nSlots + 1;
-   int* nAtoms = gid + nSlots + 1;
-   computeCentroSymmetry(&s->gpu, (real_t)rCoord, csp, coord);          /* blocks: the stream is drained, the two copies below see the same state */
-   comdMemcpyDtoH(gid, s->gpu.atoms.gid, (long)(nSlots * sizeof(int)));
-   comdMemcpyDtoH(nAtoms, s->gpu.boxes.nAtoms, (long)((size_t)nLocalBoxes * sizeof(int)));
-   const int one = getNRanks() == 1;
-   double* mine = one ? NULL : (double*)calloc(n ? 2 * n : 1, sizeof(double));
-   double* outCsp = one ? cspByGid : mine;
-   double* outCoord = one ? coordByGid : mine + n;
-   if (one) { memset(cspByGid, 0, n * sizeof(double)); memset(coordByGid, 0, n * sizeof(double)); }
-   for (int b = 0; b < nLocalBoxes; ++b)
-      for (size_t o = (size_t)b * cap, e = o + (size_t)nAtoms[b]; o < e; ++o) {
-         const size_t g = (size_t)gid[o];
-         if (g < n) { outCsp[g] = (double)csp[o]; outCoord[g] = (double)coord[o]; }
-      }
-   if (!one) {
-      /* every other rank holds 0 for a gid (and inf + 0 = inf); in chunks whose count fits addDoubleParallel's int */
-      const size_t chunk = (size_t)1 << 28;
-      startTimer(commReduceTimer);
-      for (size_t o = 0; o < n; o += chunk) {
-         const int len = (int)(n - o < chunk ? n - o : chunk);
-         addDoubleParallel(mine + o, cspByGid + o, len);
-         addDoubleParallel(mine + n + o, coordByGid + o, len);
-      }
-      stopTimer(commReduceTimer);
-   }
-   free(mine);
-   return 0;
-}
-
-/* ---- adaptive common neighbour analysis (not in the reference; comd_host.h) ---- */
-int comdCommonNeighbors(SimFlat* s, int* typeByGid, long long counts[5])
-{
-   const int cap = s->boxes->maxAtoms, nLocalBoxes = s->boxes->nLocalBoxes;
-   const size_t nSlots = (size_t)nLocalBoxes * cap, n = (size_t)s->atoms->nGlobal;
-   /* staging for the by-slot arrays, kept with the simulation as comdCentroSymmetry's */
-   const size_t need = (2 * (nSlots + 1) + (size_t)nLocalBoxes + 1) * sizeof(int);
-   if (need > s->cnaStageBytes) { free(s->cnaStage); s->cnaStage = malloc(need); s->cnaStageBytes = need; }
-   int* type = (int*)s->cnaStage;
-   int* gid = type + nSlots + 1;
-   int* nAtoms = gid + nSlots + 1;
-   computeCommonNeighbors(&s->gpu, type);          /* blocks: the stream is drained, the two copies below see the same state */
-   comdMemcpyDtoH(gid, s->gpu.atoms.gid, (long)(nSlots * sizeof(int)));
-   comdMemcpyDtoH(nAtoms, s->gpu.boxes.nAtoms, (long)((size_t)nLocalBoxes * sizeof(int)));
-   const int one = getNRanks() == 1;
-   int* mine = one ? typeByGid : (int*)malloc((n ? n : 1) * sizeof(int));
-   memset(mine, 0, n * sizeof(int));
-   for (int b = 0; b < nLocalBoxes; ++b)
-      for (size_t o = (size_t)b * cap, e = o + (size_t)nAtoms[b]; o < e; ++o) {
-         const size_t g = (size_t)gid[o];
-         if (g < n) mine[g] = type[o];
-      }
-   if (!one) {
-      /* every other rank holds 0 for a gid; in chunks whose count fits addIntParallel's int */
-      const size_t chunk = (size_t)1 << 28;
-      startTimer(commReduceTimer);
-      for (size_t o = 0; o < n; o += chunk) addIntParallel(mine + o, typeByGid + o, (int)(n - o < chunk ? n - o : chunk));
-      stopTimer(commReduceTimer);
-      free(mine);
-   }
-   for (int t = 0; t < 5; ++t) counts[t] = 0;
-   for (size_t g = 0; g < n; ++g) { const int t = typeByGid[g]; counts[t >= 0 && t <= 4 ? t : 0] += 1; }
-   return 0;
-}
-
-/* ---- per-atom virial stress (not in the reference; comd_host.h) ---- */
-int comdAtomStress(SimFlat* s, int withKinetic, double* stressByGid)
-{
-   if (!s->gpu.boxes.nAtoms) return -1;
-   const int cap = s->boxes->maxAtoms, nLocalBoxes = s->boxes->nLocalBoxes;
-   const size_t nSlots = (size_t)nLocalBoxes * cap, n = (size_t)s->atoms->nGlobal;
-   /* staging for the by-slot planes, kept with the simulation as comdCentroSymmetry's */
-   const size_t need = (6 * nSlots + 1) * sizeof(real_t) + (nSlots + 1 + (size_t)nLocalBoxes + 1) * sizeof(int);
-   if (need > s->stressStageBytes) { free(s->stressStage); s->stressStage = malloc(need); s->stressStageBytes = need; }
-   real_t* planes = (real_t*)s->stressStage;
-   int* gid = (int*)(planes + 6 * nSlots + 1);
-   int* nAtoms = gid + nSlots + 1;
-   computeAtomStress(&s->gpu, withKinetic, planes);          /* blocks: the stream is drained, the two copies below see the same state */
-   comdMemcpyDtoH(gid, s->gpu.atoms.gid, (long)(nSlots * sizeof(int)));
-   comdMemcpyDtoH(nAtoms, s->gpu.boxes.nAtoms, (long)((size_t)nLocalBoxes * sizeof(int)));
-   const int one = getNRanks() == 1;
-   double* mine = one ? stressByGid : (double*)malloc((n ? 6 * n : 1) * sizeof(double));
-   memset(mine, 0, 6 * n * sizeof(double));
-   for (int b = 0; b < nLocalBoxes; ++b)
-      for (size_t o = (size_t)b * cap, e = o + (size_t)nAtoms[b]; o < e; ++o) {
-         const size_t g = (size_t)gid[o];
-         if (g < n) for (int c = 0; c < 6; ++c) mine[6 * g + c] = (double)planes[(size_t)c * nSlots + o];
-      }
-   if (!one) {
-      /* every other rank holds 0 for a gid; in chunks whose count fits addDoubleParallel's int */
-      const size_t chunk = (size_t)1 << 28;
-      startTimer(commReduceTimer);
-      for (size_t o = 0; o < 6 * n; o += chunk) addDoubleParallel(mine + o, stressByGid + o, (int)(6 * n - o < chunk ? 6 * n - o : chunk));
-      stopTimer(commReduceTimer);
-      free(mine);
-   }
-   return 0;
-}
-
-int comdStressSummary(SimFlat* s, int withKinetic, double* out7)
-{
-   if (!s->gpu.boxes.nAtoms) return -1;
-   const double n = (double)s->atoms->nGlobal;
-   const double omega = (double)s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2] / (n > 0.0 ? n : 1.0);
-   double local[7];
-   computeAtomStress(&s->gpu, withKinetic, NULL);
-   computeAtomStressSummary(&s->gpu, omega, local);
-   const int nRanks = getNRanks(), me = getMyRank();
-   if (nRanks > 1) {
-      /* the sums add; the extremes and the gid go through one slot per rank of a summed vector (no MIN/MAX of doubles in the transport), taken in rank order */
-      double* mine = (double*)calloc(2 * (size_t)(3 + 4 * nRanks), sizeof(double));
-      double* all = mine + 3 + 4 * (size_t)nRanks;
-      mine[0] = local[0]; mine[1] = local[3]; mine[2] = local[6];
-      if (local[6] > 0.0) { double* slot = mine + 3 + 4 * (size_t)me; slot[0] = local[1]; slot[1] = local[2]; slot[2] = local[4]; slot[3] = local[5] + 1.0; }
-      startTimer(commReduceTimer);
-      addDoubleParallel(mine, all, 3 + 4 * nRanks);
-      stopTimer(commReduceTimer);
-      local[0] = all[0]; local[3] = all[1]; local[6] = all[2];
-      local[1] = INFINITY; local[2] = -INFINITY; local[4] = -INFINITY; local[5] = -1.0;
-      for (int r = 0; r < nRanks; ++r) {
-         const double* slot = all + 3 + 4 * (size_t)r;
-         if (slot[3] == 0.0) continue;          /* a rank without atoms */
-         const double g = slot[3] - 1.0;
-         if (slot[0] < local[1]) local[1] = slot[0];
-         if (slot[1] > local[2]) local[2] = slot[1];
-         if (local[5] < 0.0 || slot[2] > local[4] || (slot[2] == local[4] && g < local[5])) { local[4] = slot[2]; local[5] = g; }
-      }
-      free(mine);
-   }
-   const double N = local[6];
-   out7[0] = N > 0.0 ? local[0] / N : 0.0; out7[1] = local[1]; out7[2] = local[2];
-   out7[3] = N > 0.0 ? local[3] / N : 0.0; out7[4] = local[4]; out7[5] = local[5]; out7[6] = N;
-   return 0;
-}
-
-/* ---- per-atom strain and D^2min (not in the reference; comd_host.h) ---- */
-int comdStrainReference(SimFlat* s, int on)
-{
-   if (!s->gpu.boxes.nAtoms) return -1;
-   const int nGlobal = s->atoms->nGlobal;
-   int fail = comdStrainReferenceGpu(&s->gpu, nGlobal, on), anyFail = 0;
-   maxIntParallel(&fail, &anyFail, 1);
-   if (anyFail && !fail) comdStrainReferenceGpu(&s->gpu, nGlobal, 0);      /* all ranks or none */
-   s->strainHasRef = on != 0 && !anyFail;
-   if (!s->strainHasRef) return anyFail;
-   for (int a = 0; a < 3; ++a) s->strainL0[a] = s->gpu.strainL0[a] = (double)s->domain->globalExtent[a];
-   if (getNRanks() > 1) {
-      /* halo neighbours need the records of the other ranks' atoms: every other rank holds 0 for a gid; in chunks whose count fits addDoubleParallel's int */
-      const size_t n = 4 * (size_t)nGlobal, chunk = (size_t)1 << 28;
-      double* mine = (double*)malloc(2 * n * sizeof(double));
-      double* all = mine + n;
-      comdMemcpyDtoH(mine, s->gpu.strainRefBuf, (long)(n * sizeof(double)));
-      startTimer(commReduceTimer);
-      for (size_t o = 0; o < n; o += chunk) addDoubleParallel(mine + o, all + o, (int)(n - o < chunk ? n - o : chunk));
-      stopTimer(commReduceTimer);
-      comdMemcpyHtoD(s->gpu.strainRefBuf, all, (long)(n * sizeof(double)));
-      free(mine);
-   }
-   return 0;
-}
-
-int comdStrainReferenceBox(SimFlat* s, double* L0)
-{
-   if (!s->strainHasRef) return -1;
-   for (int a = 0; a < 3; ++a) L0[a] = s->strainL0[a];
-   return 0;
-}
-
-/* the radius the two entries launch with: the default for rCut <= 0; 0 when the entry has to refuse */
-static double strainRadius(SimFlat* s, double rCut)
-{
-   if (!s->gpu.boxes.nAtoms || !s->strainHasRef) return 0.0;
-   if (rCut <= 0.0) rCut = comdDefaultCoordRadius(s);
-   return rCut <= s->pot->cutoff ? rCut : 0.0;
-}
-
-int comdAtomStrain(SimFlat* s, double rCut, double* strainByGid7, int* countByGid)
-{
-   rCut = strainRadius(s, rCut);
-   if (!(rCut > 0.0)) return -1;
-   const int cap = s->boxes->maxAtoms, nLocalBoxes = s->boxes->nLocalBoxes;
-   const size_t nSlots = (size_t)nLocalBoxes * cap, n = (size_t)s->atoms->nGlobal;
-   /* staging for the by-slot planes, kept with the simulation as comdCentroSymmetry's */
-   const size_t need = (7 * nSlots + 1) * sizeof(real_t) + (2 * (nSlots + 1) + (size_t)nLocalBoxes + 1) * sizeof(int);
-   if (need > s->strainStageBytes) { free(s->strainStage); s->strainStage = malloc(need); s->strainStageBytes = need; }
-   real_t* planes = (real_t*)s->strainStage;
-   int* count = (int*)(planes + 7 * nSlots + 1);
-   int* gid = count + nSlots + 1;
-   int* nAtoms = gid + nSlots + 1;
-   computeAtomStrain(&s->gpu, (real_t)rCut, planes, count);          /* blocks: the stream is drained, the two copies below see the same state */
-   comdMemcpyDtoH(gid, s->gpu.atoms.gid, (long)(nSlots * sizeof(int)));
-   comdMemcpyDtoH(nAtoms, s->gpu.boxes.nAtoms, (long)((size_t)nLocalBoxes * sizeof(int)));
-   const int one = getNRanks() == 1;
-   double* mine = one ? strainByGid7 : (double*)malloc((n ? 7 * n : 1) * sizeof(double));
-   int* mineN = one ? countByGid : (int*)malloc((n ? n : 1) * sizeof(int));
-   memset(mine, 0, 7 * n * sizeof(double));
-   memset(mineN, 0, n * sizeof(int));
-   for (int b = 0; b < nLocalBoxes; ++b)
-      for (size_t o = (size_t)b * cap, e = o + (size_t)nAtoms[b]; o < e; ++o) {
-         const size_t g = (size_t)gid[o];
-         if (g < n) { for (int c = 0; c < 7; ++c) mine[7 * g + c] = (double)planes[(size_t)c * nSlots + o]; mineN[g] = count[o]; }
-      }
-   if (!one) {
-      /* every other rank holds 0 for a gid (and NaN + 0 = NaN, an invalid atom stays one); in chunks whose count fits the int of the sums */
-      const size_t chunk = (size_t)1 << 28;
-      startTimer(commReduceTimer);
-      for (size_t o = 0; o < 7 * n; o += chunk) addDoubleParallel(mine + o, strainByGid7 + o, (int)(7 * n - o < chunk ? 7 * n - o : chunk));
-      for (size_t o = 0; o < n; o += chunk) addIntParallel(mineN + o, countByGid + o, (int)(n - o < chunk ? n - o : chunk));
-      stopTimer(commReduceTimer);
-      free(mine); free(mineN);
-   }
-   return 0;
-}
-
-int comdStrainSummary(SimFlat* s, double rCut, double threshold, double* out9)
-{
-   rCut = strainRadius(s, rCut);
-   if (!(rCut > 0.0) || !(threshold > 0.0)) return -1;
-   double local[9];          /* sum gamma, max gamma, gid, sum vol, sum D^2, max D^2, valid, invalid, above (computeAtomStrainSummary) */
-   computeAtomStrain(&s->gpu, (real_t)rCut, NULL, NULL);
-   computeAtomStrainSummary(&s->gpu, threshold, local);
-   const int nRanks = getNRanks(), me = getMyRank();
-   if (nRanks > 1) {
-      /* the sums add; the extremes and the gid go through one slot per rank of a summed vector (no MAX of doubles in the transport), taken in rank order */
-      double* mine = (double*)calloc(2 * (size_t)(6 + 3 * nRanks), sizeof(double));
-      double* all = mine + 6 + 3 * (size_t)nRanks;
-      mine[0] = local[0]; mine[1] = local[3]; mine[2] = local[4]; mine[3] = local[6]; mine[4] = local[7]; mine[5] = local[8];
-      if (local[6] > 0.0) { double* slot = mine + 6 + 3 * (size_t)me; slot[0] = local[1]; slot[1] = local[2] + 1.0; slot[2] = local[5]; }
-      startTimer(commReduceTimer);
-      addDoubleParallel(mine, all, 6 + 3 * nRanks);
-      stopTimer(commReduceTimer);
-      local[0] = all[0]; local[3] = all[1]; local[4] = all[2]; local[6] = all[3]; local[7] = all[4]; local[8] = all[5];
-      local[1] = -INFINITY; local[2] = -1.0; local[5] = -INFINITY;
-      for (int r = 0; r < nRanks; ++r) {
-         const double* slot = all + 6 + 3 * (size_t)r;
-         if (slot[1] == 0.0) continue;          /* a rank without valid atoms */
-         const double g = slot[1] - 1.0;
-         if (local[2] < 0.0 || slot[0] > local[1] || (slot[0] == local[1] && g < local[2])) { local[1] = slot[0]; local[2] = g; }
-         if (slot[2] > local[5]) local[5] = slot[2];
-      }
-      free(mine);
-   }
-   const double N = local[6];
-   out9[0] = N + local[7]; out9[1] = local[7];
-   out9[2] = N > 0.0 ? local[0] / N : 0.0; out9[3] = N > 0.0 ? local[1] : 0.0; out9[4] = local[2];
-   out9[5] = N > 0.0 ? local[3] / N : 0.0; out9[6] = N > 0.0 ? local[4] / N : 0.0; out9[7] = N > 0.0 ? local[5] : 0.0; out9[8] = local[8];
-   return 0;
-}
-
-/* ---- displacement tracking (not in the reference; comd_host.h) ---- */
-int comdTrackDisplacement(SimFlat* s, int on)
-{
-   int fail = comdTrackDisplacementGpu(&s->gpu, s->atoms->nGlobal, on), anyFail = 0;
-   maxIntParallel(&fail, &anyFail, 1);
-   if (anyFail && !fail) comdTrackDisplacementGpu(&s->gpu, s->atoms->nGlobal, 0);      /* all ranks or none */
-   s->trackDisp = on != 0 && !anyFail;
-   return anyFail;
-}
-
-#define COMD_DISP_UNIT (1.0 / 4294967296.0)      /* Angstroms per unit of the device records */
-
-int comdDisplacements(SimFlat* s, double* out)
-{
-   if (!s->trackDisp) return -1;
-   const size_t n = (size_t)s->atoms->nGlobal;
-   int64_t* raw = (int64_t*)malloc(4 * n * sizeof(int64_t));
-   comdCopyDisplacementsGpu(&s->gpu, raw);
-   if (getNRanks() == 1) {
-      for (size_t g = 0; g < n; ++g) for (int c = 0; c < 3; ++c) out[3 * g + c] = (double)raw[4 * g + c] * COMD_DISP_UNIT;
-      free(raw);
-      return 0;
-   }
-   /* the ranks' parts as doubles (exact below 2^53), summed in chunks whose count fits addDoubleParallel's int */
-   const int64_t top = (int64_t)1 << 53;
-   double* mine = (double*)malloc(3 * n * sizeof(double));
-   int bad = 0, anyBad = 0;
-   for (size_t g = 0; g < n; ++g)
-      for (int c = 0; c < 3; ++c) {
-         const int64_t v = raw[4 * g + c];
-         if (v >= top || v <= -top) bad = 1;
-         mine[3 * g + c] = (double)v;
-      }
-   free(raw);
-   maxIntParallel(&bad, &anyBad, 1);
-   if (!anyBad) {
-      const size_t chunk = (size_t)1 << 28;
-      startTimer(commReduceTimer);
-      for (size_t o = 0; o < 3 * n; o += chunk) addDoubleParallel(mine + o, out + o, (int)(3 * n - o < chunk ? 3 * n - o : chunk));
-      stopTimer(commReduceTimer);
-      for (size_t k = 0; k < 3 * n; ++k) out[k] *= COMD_DISP_UNIT;
-   }
-   free(mine);
-   return anyBad ? -2 : 0;
-}
-
-int comdMsd(SimFlat* s, double* out7)
-{
-   if (!s->trackDisp) return -1;
-   const size_t n = (size_t)s->atoms->nGlobal;
-   out7[6] = (double)n;
-   if (getNRanks() == 1) { computeDisplacementSums(&s->gpu, out7); return 0; }
-   double* d = (double*)malloc(3 * n * sizeof(double));
-   const int rc = comdDisplacements(s, d);
-   for (int c = 0; c < 6; ++c) out7[c] = 0.0;
-   if (rc == 0)
-      for (size_t g = 0; g < n; ++g)
-         for (int c = 0; c < 3; ++c) { const double v = d[3 * g + c]; out7[c] += v; out7[3 + c] += v * v; }
-   free(d);
-   return rc;
-}
-
 double pressureOf(const SimFlat* s)
 {
    return ((double)s->K[0] + s->K[1] + s->K[2] + s->W[0] + s->W[1] + s->W[2]) / (3.0 * s->V);
