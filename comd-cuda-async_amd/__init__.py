@@ -150,6 +150,14 @@ def lib_host():
         lib.comdAtomStress.restype = ctypes.c_int
         lib.comdStressSummary.argtypes = [vp, ctypes.c_int, c_double_p]
         lib.comdStressSummary.restype = ctypes.c_int
+        lib.comdHeatFlux.argtypes = [vp, c_double_p]
+        lib.comdHeatFlux.restype = ctypes.c_int
+        lib.comdAtomHeatFlux.argtypes = [vp, c_double_p]
+        lib.comdAtomHeatFlux.restype = ctypes.c_int
+        lib.comdHeatFluxAcf.argtypes = [c_double_p, ctypes.c_int, ctypes.c_int, c_double_p]
+        lib.comdHeatFluxAcf.restype = ctypes.c_int
+        lib.comdAtomMass.argtypes = [vp]
+        lib.comdAtomMass.restype = ctypes.c_double
         lib.comdStrainReference.argtypes = [vp, ctypes.c_int]
         lib.comdStrainReference.restype = ctypes.c_int
         lib.comdAtomStrain.argtypes = [vp, ctypes.c_double, c_double_p, c_int_p]
@@ -585,6 +593,42 @@ class Simulation:
         return {"mean_pressure": out[0], "min_pressure": out[1], "max_pressure": out[2], "mean_von_mises": out[3], "max_von_mises": out[4],
                 "max_von_mises_gid": int(out[5]), "n": int(out[6])}
 
+    # --- heat flux (not in the reference: comd-hip --heatflux, --hfStart, --hfWindow, --hfFile, --hfAcfFile) ---
+    @property
+    def mass(self):
+        """The mass of the (one) species in eV fs^2/A^2: v = p / mass."""
+        return self.lib.comdAtomMass(self.ptr)
+
+    def heat_flux(self):
+        """{"kinetic", "potential", "virial", "total"}: float64 (3,) each, the heat flux J V of the current state in eV A/fs (flux density x volume), summed
+        over all atoms of all ranks on the device (computeHeatFlux; nothing per atom leaves it): sum_i (|p_i|^2 / 2 m) v_i, sum_i e_i v_i,
+        1/2 sum_i sum_j r_ij (f_ij . v_i), and their sum.  Valid when virial() is and the per-atom energies are current: after creation, compute_force(),
+        set_box() or a step() call -- between step() calls, whose last step evaluates the energies."""
+        np = self._np
+        if self.host_only:
+            raise RuntimeError("heat_flux: a host-only simulation has no device state")
+        out = (ctypes.c_double * 9)()
+        if self.lib.comdHeatFlux(self.ptr, out) != 0:
+            raise RuntimeError("heat_flux: comdHeatFlux failed")
+        j = np.array(out[0:9], dtype=np.float64)
+        return {"kinetic": j[0:3].copy(), "potential": j[3:6].copy(), "virial": j[6:9].copy(), "total": (j[0:3] + j[3:6]) + j[6:9]}
+
+    def atomic_heat_flux(self):
+        """float64 (n_global, 9) keyed by gid: every atom's kinetic (columns 0-2), potential (3-5) and virial (6-8) part of heat_flux(), x y z each, in
+        eV A/fs; summed over the ranks (every rank gets the global array)."""
+        np = self._np
+        if self.host_only:
+            raise RuntimeError("atomic_heat_flux: a host-only simulation has no device state")
+        n = self.n_global
+        out = np.zeros((max(n, 1), 9), dtype=np.float64)
+        if self.lib.comdAtomHeatFlux(self.ptr, out.ctypes.data_as(c_double_p)) != 0:
+            raise RuntimeError("atomic_heat_flux: comdAtomHeatFlux failed")
+        return out[:n]
+
+    def heat_flux_density(self):
+        """float64 (3,): heat_flux()["total"] / volume, the heat flux density J in eV/A^2/fs."""
+        return self.heat_flux()["total"] / self.volume
+
     # --- per-atom strain (not in the reference: comd-hip --strain, --strainRef, --strainCutoff, --strainThreshold, --strainFile, --strainDump, --strainDumpMin) ---
     def set_strain_reference(self, on=True):
         """Take the current state as the reference of atomic_strain(): every atom's position, keyed by gid, in a table of doubles on every rank's device
@@ -825,6 +869,19 @@ class Simulation:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def heat_flux_acf(j, window):
+    """float64 (window, 3): the autocorrelation C_a(k) = (1 / (samples - k)) sum_t j[t, a] j[t + k, a] of a series j (samples, 3), 0 <= k < window <= samples
+    (comdHeatFluxAcf of the host library; no device).  ValueError for another shape or window."""
+    import numpy as np
+    j = np.ascontiguousarray(j, dtype=np.float64)
+    if j.ndim != 2 or j.shape[1] != 3 or not 1 <= int(window) <= j.shape[0]:
+        raise ValueError(f"heat_flux_acf: need a series (samples, 3) and 1 <= window <= samples (got {j.shape}, {window})")
+    out = np.zeros((int(window), 3), dtype=np.float64)
+    if lib_host().comdHeatFluxAcf(j.ctypes.data_as(c_double_p), j.shape[0], int(window), out.ctypes.data_as(c_double_p)) != 0:
+        raise ValueError("heat_flux_acf: comdHeatFluxAcf refused the series")
+    return out
 
 
 def run_main(args):

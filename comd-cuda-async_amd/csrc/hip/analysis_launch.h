@@ -184,6 +184,43 @@ extern "C" void computeAtomStressSummary(SimGpu* sim, double atomVolume, double*
    launchSummary(sim, AtomStress_Summary, AtomStress_SummaryFinal, sim->stressBuf, 1.0 / atomVolume, sim->stressSumBuf, ATOMSTRESS_SUM_BLOCKS, ATOMSTRESS_SUM_N, out);
 }
 
+// Not in the reference: the per-atom heat flux (heatflux_kernels.h), one kernel instance per pair function of the force paths and per output, as computeVirial.
+// outBySlot9: the nine planes are stored and copied; else, out9: the sampled path, nine sums of this rank's atoms through the rows, nothing per atom written.
+// The planes and the rows are allocated by the first call that needs them.
+extern "C" void computeHeatFlux(SimGpu* sim, real_t* outBySlot9, double* out9)
+{
+   hipStream_t st = analysisStream(sim);
+   const size_t nSlots = localSlots(sim);
+   HeatFluxArgs v;
+   fillStencilArgs(v, sim);
+   v.px = sim->atoms.p.x; v.py = sim->atoms.p.y; v.pz = sim->atoms.p.z;
+   v.e = sim->atoms.e;
+   v.iSpecies = sim->atoms.iSpecies; v.speciesMass = sim->species_mass;
+   v.plane = nSlots;
+   if (outBySlot9) {
+      if (!sim->heatFluxBuf) sim->heatFluxBuf = dalloc<real_t>(HEATFLUX_N * nSlots);
+      withPairFunction(sim, [&](auto p, real_t rc2) {
+         v.rc2 = rc2;
+         hipLaunchKernelGGL((HeatFlux_thread_atom<decltype(p), true>), dim3(HEATFLUX_BLOCKS), dim3(256), 0, st, v, p, sim->heatFluxBuf, (double*)nullptr);
+      });
+      LAUNCH_CHECK();
+      HIP_CHECK(hipMemcpyAsync(outBySlot9, sim->heatFluxBuf, HEATFLUX_N * nSlots * sizeof(real_t), hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipStreamSynchronize(st));
+   }
+   if (out9) {
+      if (!sim->heatFluxSumBuf) sim->heatFluxSumBuf = dalloc<double>((size_t)(HEATFLUX_BLOCKS + 1) * HEATFLUX_N, false);
+      double* final = sim->heatFluxSumBuf + (size_t)HEATFLUX_BLOCKS * HEATFLUX_N;
+      withPairFunction(sim, [&](auto p, real_t rc2) {
+         v.rc2 = rc2;
+         hipLaunchKernelGGL((HeatFlux_thread_atom<decltype(p), false>), dim3(HEATFLUX_BLOCKS), dim3(256), 0, st, v, p, (real_t*)nullptr, sim->heatFluxSumBuf);
+      });
+      hipLaunchKernelGGL(HeatFlux_Final, dim3(1), dim3(256), 0, st, sim->heatFluxSumBuf, HEATFLUX_BLOCKS, final);
+      LAUNCH_CHECK();
+      HIP_CHECK(hipMemcpyAsync(out9, final, HEATFLUX_N * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipStreamSynchronize(st));
+   }
+}
+
 // Not in the reference: the reference snapshot of the per-atom strain (strain_kernels.h).  on: one 32-byte record of doubles per global atom id, zeroed, then
 // the positions of this rank's local atoms at their gids (taken again when it is already on); the host adds the ranks' tables and uploads the sum into
 // strainRefBuf.  off: the table and the planes of computeAtomStrain are freed.  1 and no reference when the device cannot give the memory.

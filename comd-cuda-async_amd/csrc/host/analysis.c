@@ -1,5 +1,5 @@
 /* analysis.c -- the host entries of the analyses (not in the reference; comd_host.h): pressure, g(r), centro-symmetry, common neighbour analysis, per-atom
- * stress and strain, displacements.  Each is a call into include/comd_hip.h for this rank's share and a sum over the ranks. */
+ * stress and strain, heat flux and its autocorrelation, displacements.  Each is a call into include/comd_hip.h for this rank's share and a sum over the ranks. */
 #include "comd_host.h"
 #include "slot_gather.h"
 #include <math.h>
@@ -37,7 +37,7 @@ double comdDefaultCoordRadius(SimFlat* s)
    return r < cutoff ? r : cutoff;
 }
 
-/* ---- the by-gid gather of comdCentroSymmetry, comdCommonNeighbors, comdAtomStress and comdAtomStrain ----
+/* ---- the by-gid gather of comdCentroSymmetry, comdCommonNeighbors, comdAtomStress, comdAtomStrain and comdAtomHeatFlux ----
  * An output is out[nGlobal][width], filled from `width` consecutive by-slot planes of one kind (slot_gather.h); the real_t outputs come first.  `run` launches the
  * kernel and copies its planes into plane[k], one pointer per output. */
 typedef struct { void* out; int kind, width; } GidOutput;
@@ -62,7 +62,7 @@ static void gatherByGid(SimFlat* s, SlotKernel run, const void* arg, const GidOu
    /* one rank writes straight into the caller's arrays */
    const int one = getNRanks() == 1;
    void* mine[2];
-   SlotPlane planes[8];
+   SlotPlane planes[10];
    int nPlanes = 0;
    for (int k = 0; k < nOut; ++k) {
       const size_t len = (size_t)out[k].width * n;
@@ -156,6 +156,40 @@ int comdStressSummary(SimFlat* s, int withKinetic, double* out7)
    const double N = local[6];
    out7[0] = N > 0.0 ? local[0] / N : 0.0; out7[1] = local[1]; out7[2] = local[2];
    out7[3] = N > 0.0 ? local[3] / N : 0.0; out7[4] = local[4]; out7[5] = local[5]; out7[6] = N;
+   return 0;
+}
+
+/* ---- heat flux (not in the reference; comd_host.h) ---- */
+int comdHeatFlux(SimFlat* s, double out9[9])
+{
+   if (!s->gpu.boxes.nAtoms) return -1;
+   double local[9];
+   computeHeatFlux(&s->gpu, NULL, local);
+   startTimer(commReduceTimer);
+   addDoubleParallel(local, out9, 9);
+   stopTimer(commReduceTimer);
+   return 0;
+}
+
+static void runAtomHeatFlux(SimFlat* s, void* const* plane, const void* none) { computeHeatFlux(&s->gpu, (real_t*)plane[0], NULL); }
+
+int comdAtomHeatFlux(SimFlat* s, double* byGid)
+{
+   if (!s->gpu.boxes.nAtoms) return -1;
+   const GidOutput out = { byGid, SLOT_REAL, 9 };
+   gatherByGid(s, runAtomHeatFlux, NULL, &out, 1);
+   return 0;
+}
+
+int comdHeatFluxAcf(const double* j, int samples, int window, double* acf)
+{
+   if (!j || !acf || samples < 1 || window < 1 || window > samples) return -1;
+   for (int k = 0; k < window; ++k)
+      for (int a = 0; a < 3; ++a) {
+         double sum = 0.0;
+         for (int t = 0; t + k < samples; ++t) sum += j[3 * (size_t)t + a] * j[3 * (size_t)(t + k) + a];
+         acf[3 * (size_t)k + a] = sum / (double)(samples - k);
+      }
    return 0;
 }
 

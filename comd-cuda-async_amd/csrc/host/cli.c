@@ -23,7 +23,10 @@
  * --strain, --strainRef S, --strainCutoff R, --strainThreshold X, --strainFile PATH, --strainDump PATH, --strainDumpMin X (per-atom strain against the state at
  * the end of global step S: the Green-Lagrange tensor of the best affine map of every atom's neighbourhood within R, its shear invariant and the non-affine
  * residue D^2min, reduced on the device at every printed step; a MaxShear column, PATH gets a line per sample and the dump the tensors of the atoms of the last
- * step whose shear strain is at least X as extended XYZ). */
+ * step whose shear strain is at least X as extended XYZ),
+ * --heatflux, --hfStart S, --hfWindow M, --hfFile PATH, --hfAcfFile PATH (heat flux J V = sum_i (e_kin,i + e_i) v_i + 1/2 sum_i sum_j r_ij (f_ij . v_i), reduced on the
+ * device at every printed step from global step S on; a Jx(eV/A^2/fs) column, PATH gets the samples, the ACF file the autocorrelation over M lags and the running
+ * Green-Kubo thermal conductivity in W/(m K); the reference has no transport output). */
 #include "comd_host.h"
 #include <getopt.h>
 #include <math.h>
@@ -64,6 +67,8 @@ Command parseCommandLine(int argc, char** argv)
    strcpy(cmd.stressFile, "stress.dat");
    strcpy(cmd.strainFile, "strain.dat");
    cmd.strainThreshold = 0.1;
+   strcpy(cmd.hfFile, "heatflux.dat");
+   strcpy(cmd.hfAcfFile, "hfacf.dat");
    int help = 0;
 
    const ArgDef defs[] = {
@@ -132,6 +137,11 @@ Command parseCommandLine(int argc, char** argv)
       { "strainFile",    0,  1, 's', cmd.strainFile, sizeof cmd.strainFile, "file the samples are written to (default strain.dat)" },
       { "strainDump",    0,  1, 's', cmd.strainDump, sizeof cmd.strainDump, "extended-XYZ file of the per-atom strain tensors, shear strain and D^2min of the last step (default: none)" },
       { "strainDumpMin", 0,  1, 'd', &cmd.strainDumpMin,  0, "only atoms with a shear strain of at least this are dumped (default 0: all atoms)" },
+      { "heatflux",      0,  0, 'i', &cmd.heatflux,       0, "heat flux and Green-Kubo thermal conductivity, sampled at every printed step (a Jx(eV/A^2/fs) column; -n sets the sampling interval)" },
+      { "hfStart",       0,  1, 'i', &cmd.hfStart,        0, "global step the heat-flux sampling begins at (0..nSteps; default 0)" },
+      { "hfWindow",      0,  1, 'i', &cmd.hfWindow,       0, "lags of the heat-flux autocorrelation (default 0: half the samples; clipped to the samples)" },
+      { "hfFile",        0,  1, 's', cmd.hfFile, sizeof cmd.hfFile, "file the flux samples are written to (default heatflux.dat)" },
+      { "hfAcfFile",     0,  1, 's', cmd.hfAcfFile, sizeof cmd.hfAcfFile, "file the autocorrelation and the running conductivity are written to (default hfacf.dat)" },
    };
    const int nDefs = (int)(sizeof defs / sizeof defs[0]);
 
@@ -214,6 +224,7 @@ void printCmdYaml(FILE* file, Command* cmd)
    if (cmd->cna) fprintf(file, "  CNA file: %s\n", cmd->cnaFile);
    if (cmd->stress) fprintf(file, "  Stress file: %s\n", cmd->stressFile);
    if (cmd->strain) fprintf(file, "  Strain reference step: %d\n  Strain file: %s\n", cmd->strainRef, cmd->strainFile);
+   if (cmd->heatflux) fprintf(file, "  Heat flux from step: %d\n  Heat flux file: %s\n  Heat flux ACF file: %s\n", cmd->hfStart, cmd->hfFile, cmd->hfAcfFile);
    if (cmd->msd) fprintf(file, "  MSD from step: %d\n  MSD file: %s\n", cmd->msdStart, cmd->msdFile);
    if (cmd->erate[0] != 0.0 || cmd->erate[1] != 0.0 || cmd->erate[2] != 0.0)
       fprintf(file, "  Strain rates: [ %g, %g, %g ] 1/ps\n  Deform from step: %d\n  Deform file: %s\n", cmd->erate[0], cmd->erate[1], cmd->erate[2], cmd->deformStart, cmd->deformFile);

@@ -78,6 +78,11 @@ typedef struct CommandSt {
    char strainFile[1024]; /* extension: where the print rank writes the samples (default strain.dat) */
    char strainDump[1024]; /* extension: extended-XYZ file of the per-atom tensors of the last step; empty = none */
    double strainDumpMin;  /* extension: only atoms with a shear strain of at least this are dumped; 0 = all */
+   int heatflux;          /* extension: the heat flux J V, reduced on the device at every printed step, its autocorrelation and the Green-Kubo thermal conductivity */
+   int hfStart;           /* extension: the global step sampling begins at, 0..nSteps (default 0) */
+   int hfWindow;          /* extension: lags of the autocorrelation; 0 = half the samples; more than the samples is clipped */
+   char hfFile[1024];     /* extension: where the print rank writes the flux samples (default heatflux.dat) */
+   char hfAcfFile[1024];  /* extension: where it writes the autocorrelation and the running conductivity (default hfacf.dat) */
 } Command;
 
 #define COMD_LANGEVIN_SEED 0x436f4d44ull     /* "CoMD" */
@@ -385,6 +390,11 @@ typedef struct SimFlatSt {
    double* strainRows;              /* [strainSamples][10]: step, the nine values of comdStrainSummary */
    int strainSamples, strainCap;
    double strainMaxShearNow;        /* the MaxShear column of printThings: the last sample, 0 before the reference */
+   int heatflux, hfStart, hfWindow; /* --heatflux: comdMain samples comdHeatFlux at every printed step from global step hfStart on; lags of the autocorrelation (0 = half the samples) */
+   char hfFile[1024], hfAcfFile[1024];
+   double* hfRows;                  /* [hfSamples][13]: step, time (fs), the nine sums of comdHeatFlux (eV A/fs), temperature (K), volume (A^3) */
+   int hfSamples, hfCap;
+   double hfJxNow;                  /* the Jx column of printThings: the x component of the flux density of the last sample in eV/A^2/fs, 0 before hfStart */
 } SimFlat;
 
 SimFlat* initSimulation(Command cmd);
@@ -445,6 +455,19 @@ int comdAtomStress(SimFlat* s, int withKinetic, double* stressByGid);
  * pressure p and von Mises stress sigma of every atom's tensor over the uniform atomic volume V / N, in eV/A^3 (x eVperA3inGPa = GPa), reduced on the device
  * (computeAtomStress without a copy, computeAtomStressSummary) and then over the ranks.  The same on every rank.  Collective.  -1 as comdAtomStress. */
 int comdStressSummary(SimFlat* s, int withKinetic, double* out7);
+/* not in the reference: the heat flux of the current state in eV A/fs (flux density x volume; computeHeatFlux, comd_hip.h, has the formulas).  Valid whenever
+ * computePressure is AND the per-atom energies are current: after computeForce, comdDeformTo or a timestep() call (the last step of a call asks the force kernels
+ * for them), so between the timestep() calls of a run, not inside one.
+ * comdHeatFlux: out9 = the sums over all atoms of jk x y z (kinetic convective), jp x y z (potential convective), jv x y z (virial): this rank's sums from the
+ *    device reduction, then the sum over the ranks.  J V is the sum of the three parts, the flux density J V / V.  The same on every rank.  Collective.
+ * comdAtomHeatFlux: byGid[9 g + c], nGlobal x 9 doubles, the same nine components per atom.  Each rank fills the entries of its local atoms, the others stay
+ *    0, and the array is summed over the ranks: the same on every rank.  Collective.
+ * Both: -1 and nothing launched on a simulation without device state. */
+int comdHeatFlux(SimFlat* s, double out9[9]);
+int comdAtomHeatFlux(SimFlat* s, double* byGid);
+/* not in the reference: the autocorrelation of a series j[samples][3], acf[3 k + a] = (1 / (samples - k)) sum_t j[t][a] j[t + k][a] for 0 <= k < window, summed in
+ * time order in double.  Plain C, no device.  -1 and nothing written unless 1 <= window <= samples. */
+int comdHeatFluxAcf(const double* j, int samples, int window, double* acf);
 /* not in the reference: the reference snapshot of the per-atom strain.  on != 0: the current positions of all atoms become x0, keyed by gid, in a table of
  * doubles replicated on every rank's device (32 bytes per global atom: each rank stores its local atoms, the tables are summed over the ranks -- every other
  * rank holds 0 for a gid -- and uploaded), and the current global box becomes L0; already on: the reference moves to the current state.  on == 0: it is
@@ -487,7 +510,7 @@ void ensureInteriorForceLaunched(SimFlat* sim);
 
 /* ---- performanceTimers.h ---- */
 enum TimerHandle { totalTimer, loopTimer, timestepTimer, positionTimer, velocityTimer, redistributeTimer, atomHaloTimer,
-                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, cspTimer, cnaTimer, deformTimer, stressTimer, strainTimer, numberOfTimers };
+                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, cspTimer, cnaTimer, deformTimer, stressTimer, strainTimer, heatfluxTimer, numberOfTimers };
 void profileStart(enum TimerHandle handle);
 void profileStop(enum TimerHandle handle);
 double getElapsedTime(enum TimerHandle handle);
@@ -530,6 +553,7 @@ void     comdVirial(SimFlat* s, double out[13]);          /* computePressure, th
 double   comdCutoff(SimFlat* s);                          /* the force cutoff in Angstroms: the largest rMax of comdPairHistogram, and its default */
 double   comdLatticeConstant(SimFlat* s);                 /* the lattice constant the crystal was made with, in Angstroms: lat^2 / 4 is the default defect threshold */
 double   comdVolume(SimFlat* s);                          /* volume of the global domain in A^3 */
+double   comdAtomMass(SimFlat* s);                        /* the mass of the (one) species in the project's units, eV fs^2/A^2: v = p / mass */
 void     comdGridInfo(SimFlat* s, int out[6]);            /* gridSize[3], nLocalBoxes, nTotalBoxes, maxAtoms */
 int      comdMain(int argc, char** argv);                /* the reference's main(): CoMD.c:86-187 */
 void     comdDestroy(SimFlat* s);

@@ -195,6 +195,11 @@ SimFlat* initSimulationHost(Command cmd)
    sim->strainCutoff = cmd.strainCutoffSet ? cmd.strainCutoff : comdDefaultCoordRadius(sim);
    sim->strainThreshold = cmd.strainThreshold; sim->strainDumpMin = cmd.strainDumpMin;
    strcpy(sim->strainFile, cmd.strainFile); strcpy(sim->strainDump, cmd.strainDump);
+   /* --heatflux (not in the reference): sampling begins at a global step of this run; a window of 0 lags means half the samples */
+   if (cmd.hfStart < 0 || cmd.hfStart > cmd.nSteps) { printf("Error: --hfStart must lie in 0..nSteps = 0..%d (got %d).\n", cmd.nSteps, cmd.hfStart); exit(-1); }
+   if (cmd.hfWindow < 0) { printf("Error: --hfWindow must be >= 0 lags (got %d).\n", cmd.hfWindow); exit(-1); }
+   sim->heatflux = cmd.heatflux; sim->hfStart = cmd.hfStart; sim->hfWindow = cmd.hfWindow;
+   strcpy(sim->hfFile, cmd.hfFile); strcpy(sim->hfAcfFile, cmd.hfAcfFile);
    /* --erateX/Y/Z (not in the reference): the box strains at constant engineering rates; profile mode never redistributes, which the remap needs */
    for (int a = 0; a < 3; ++a) if (!(fabs(cmd.erate[a]) < 1e300)) { printf("Error: --erate%c must be a finite rate in 1/ps (got %g).\n", 'X' + a, cmd.erate[a]); exit(-1); }
    sim->deform = cmd.erate[0] != 0.0 || cmd.erate[1] != 0.0 || cmd.erate[2] != 0.0;
@@ -311,6 +316,7 @@ void destroySimulation(SimFlat** ps)
    free(s->deformRows);
    free(s->stressRows);
    free(s->strainRows);
+   free(s->hfRows);
    free(s->species); free(s->domain); free(s);
    *ps = NULL;
 }
@@ -334,10 +340,10 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
       s->firstPrint = 0;
       fprintf(screenOut,
               "#                                                                                         Performance\n"
-              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms%s%s%s%s%s%s%s\n",
+              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms%s%s%s%s%s%s%s%s\n",
               s->pressure ? "    Pressure(GPa)" : "", s->msd ? "         MSD(A^2)" : "", s->csp ? "      Defects" : "", s->cna ? "       NonFCC" : "",
               s->deformReport ? "           V/V0         Sxx(GPa)" : "", s->stress ? "       MaxVM(GPa)" : "",
-              s->strain ? "         MaxShear" : "");
+              s->strain ? "         MaxShear" : "", s->heatflux ? "       Jx(eV/A^2/fs)" : "");
       fflush(screenOut);
    }
    real_t time = iStep * s->dt;
@@ -355,6 +361,7 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
    if (s->deformReport) fprintf(screenOut, " %14.10f %16.10f", (double)s->V / (s->box0[0] * s->box0[1] * s->box0[2]), -((double)s->K[0] + s->W[0]) / s->V * eVperA3inGPa);
    if (s->stress) fprintf(screenOut, " %16.10f", s->stressMaxVmNow * eVperA3inGPa);
    if (s->strain) fprintf(screenOut, " %16.10f", s->strainMaxShearNow);
+   if (s->heatflux) fprintf(screenOut, " %19.10e", s->hfJxNow);
    fprintf(screenOut, "\n");
 }
 
@@ -829,6 +836,84 @@ static void writeStrain(FILE* yaml, SimFlat* s, int iStep)
    fflush(yaml);
 }
 
+/* --heatflux: one more row {step, time, the nine sums of comdHeatFlux, temperature, volume}.  Only at a printed step are the per-atom energies those of the
+ * current positions: timestep() asks the force kernels for them on its last step alone */
+static void sampleHeatFlux(SimFlat* s, int iStep)
+{
+   double* row = (double*)nextRow(&s->hfRows, &s->hfCap, &s->hfSamples, 13, sizeof(double));
+   row[0] = (double)iStep; row[1] = iStep * s->dt;
+   if (comdHeatFlux(s, row + 2) != 0) { printf("Error: --heatflux needs the device state.\n"); exit(-1); }
+   row[11] = (s->eKinetic / s->atoms->nGlobal) / (kB_eV * 1.5);
+   row[12] = (double)s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2];
+   s->hfJxNow = ((row[2] + row[5]) + row[8]) / row[12];
+}
+
+#define eVperFsAKinWperMK 1.602176634e6      /* 1 eV/(fs A K) in W/(m K) */
+
+/* --heatflux: the two files and the YAML block.  hfFile: a header with N, V, the time between samples, the start step and the number of samples, then per
+ * sample the step, the time, J V = jk + jp + jv, its convective part jk + jp and its virial part jv (eV A/fs).  hfAcfFile: per lag k < M the time k dt, the
+ * autocorrelation C_x, C_y, C_z of J V (comdHeatFluxAcf) and the running conductivity kappa(k) = dt trapezoid_0^k (C_x + C_y + C_z) / (3 V kB T^2) in W/(m K),
+ * with T and V the means over the samples (V: the box may strain). */
+static void writeHeatFlux(FILE* yaml, SimFlat* s)
+{
+   if (!printRank()) return;
+   const int samples = s->hfSamples;
+   const double dtSample = (double)s->printRate * s->dt;
+   double meanT = 0.0, meanV = 0.0, meanJ[3] = { 0.0, 0.0, 0.0 };
+   double* jv = (double*)malloc((samples ? 3 * (size_t)samples : 1) * sizeof(double));
+   for (int k = 0; k < samples; ++k) {
+      const double* r = s->hfRows + 13 * (size_t)k;
+      for (int a = 0; a < 3; ++a) { jv[3 * (size_t)k + a] = (r[2 + a] + r[5 + a]) + r[8 + a]; meanJ[a] += jv[3 * (size_t)k + a]; }
+      meanT += r[11]; meanV += r[12];
+   }
+   if (samples) { meanT /= samples; meanV /= samples; for (int a = 0; a < 3; ++a) meanJ[a] /= samples; }
+   else meanV = (double)s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2];
+   FILE* f = fopen(s->hfFile, "w");
+   if (!f) { printf("Error: cannot write %s\n", s->hfFile); exit(-1); }
+   fprintf(f, "# HeatFlux: N %d V %.17g A^3 (mean of the samples) dt %.17g fs between samples startStep %d samples %d | columns: step, time (fs), "
+              "J V x y z (eV A/fs), convective part x y z, virial part x y z\n", s->atoms->nGlobal, meanV, dtSample, s->hfStart, samples);
+   for (int k = 0; k < samples; ++k) {
+      const double* r = s->hfRows + 13 * (size_t)k;
+      fprintf(f, "%.0f %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", r[0], r[1], jv[3 * (size_t)k], jv[3 * (size_t)k + 1], jv[3 * (size_t)k + 2],
+              r[2] + r[5], r[3] + r[6], r[4] + r[7], r[8], r[9], r[10]);
+   }
+   fclose(f);
+   int window = s->hfWindow > 0 ? s->hfWindow : samples / 2;
+   const int clipped = window > samples;
+   if (clipped) window = samples;
+   if (window < 1) window = samples > 0 ? 1 : 0;
+   double* acf = (double*)malloc((3 * (size_t)window + 1) * sizeof(double));
+   if (window > 0) comdHeatFluxAcf(jv, samples, window, acf);
+   f = fopen(s->hfAcfFile, "w");
+   if (!f) { printf("Error: cannot write %s\n", s->hfAcfFile); exit(-1); }
+   fprintf(f, "# HeatFluxACF: N %d V %.17g A^3 T %.17g K (means of the samples) dt %.17g fs samples %d window %d%s | columns: lag time (fs), "
+              "C x y z of J V (eV^2 A^2/fs^2), running kappa (W/m/K)\n", s->atoms->nGlobal, meanV, meanT, dtSample, samples, window,
+           clipped ? " (clipped to the samples)" : "");
+   const double unit = meanT > 0.0 ? eVperFsAKinWperMK / (3.0 * meanV * kB_eV * meanT * meanT) : 0.0;
+   double integral = 0.0, kappa = 0.0;
+   for (int k = 0; k < window; ++k) {
+      const double* c = acf + 3 * (size_t)k;
+      if (k > 0) integral += 0.5 * (((c[-3] + c[-2]) + c[-1]) + ((c[0] + c[1]) + c[2])) * dtSample;
+      kappa = unit * integral;
+      fprintf(f, "%.17g %.17g %.17g %.17g %.17g\n", k * dtSample, c[0], c[1], c[2], kappa);
+   }
+   fclose(f);
+   free(acf); free(jv);
+   if (!yaml) return;
+   fprintf(yaml, "HeatFlux:\n");
+   fprintf(yaml, "  startStep: %d\n", s->hfStart);
+   fprintf(yaml, "  samples: %d\n", samples);
+   fprintf(yaml, "  window: %d\n", window);
+   fprintf(yaml, "  file: %s\n", s->hfFile);
+   fprintf(yaml, "  acfFile: %s\n", s->hfAcfFile);
+   fprintf(yaml, "  meanJV: [ %.12e, %.12e, %.12e ]\n", meanJ[0], meanJ[1], meanJ[2]);
+   fprintf(yaml, "  fluxUnits: eV A/fs\n");
+   if (samples >= 2) fprintf(yaml, "  kappa: %.12e\n", kappa); else fprintf(yaml, "  kappa: n/a\n");
+   fprintf(yaml, "  kappaUnits: W/m/K\n");
+   fprintf(yaml, "\n");
+   fflush(yaml);
+}
+
 Validate* initValidate(SimFlat* sim)
 {
    sumAtoms(sim);
@@ -933,6 +1018,7 @@ int comdMain(int argc, char** argv)
       if (sim->cna) { startTimer(cnaTimer); sampleCna(sim, iStep); stopTimer(cnaTimer); }
       if (sim->stress) { startTimer(stressTimer); sampleStress(sim, iStep); stopTimer(stressTimer); }
       if (sim->strain && iStep >= sim->strainRef) { startTimer(strainTimer); if (iStep == sim->strainRef) startStrain(sim); sampleStrain(sim, iStep); stopTimer(strainTimer); }
+      if (sim->heatflux && iStep >= sim->hfStart) { startTimer(heatfluxTimer); sampleHeatFlux(sim, iStep); stopTimer(heatfluxTimer); }
       printThings(sim, iStep, getElapsedTime(timestepTimer));
       /* --msdStart between two printed steps: the interval is taken as two timestep() calls (which give the bits of one) with the origin in between */
       const int toOrigin = sim->msd && sim->msdStart > iStep && sim->msdStart < iStep + printRate ? sim->msdStart - iStep : 0;
@@ -961,6 +1047,7 @@ int comdMain(int argc, char** argv)
    if (sim->cna) { startTimer(cnaTimer); sampleCna(sim, iStep); stopTimer(cnaTimer); }
    if (sim->stress) { startTimer(stressTimer); sampleStress(sim, iStep); stopTimer(stressTimer); }
    if (sim->strain && iStep >= sim->strainRef) { startTimer(strainTimer); if (iStep == sim->strainRef) startStrain(sim); sampleStrain(sim, iStep); stopTimer(strainTimer); }
+   if (sim->heatflux && iStep >= sim->hfStart) { startTimer(heatfluxTimer); sampleHeatFlux(sim, iStep); stopTimer(heatfluxTimer); }
    printThings(sim, iStep, getElapsedTime(timestepTimer));
    timestampBarrier("Ending simulation\n");
    if (sim->pressure) printPressureYaml(yamlFile, sim);
@@ -971,6 +1058,7 @@ int comdMain(int argc, char** argv)
    if (sim->deformReport) writeDeform(yamlFile, sim);
    if (sim->stress) { startTimer(stressTimer); writeStress(yamlFile, sim, iStep); stopTimer(stressTimer); }
    if (sim->strain) { startTimer(strainTimer); writeStrain(yamlFile, sim, iStep); stopTimer(strainTimer); }
+   if (sim->heatflux) { startTimer(heatfluxTimer); writeHeatFlux(yamlFile, sim); stopTimer(heatfluxTimer); }
 
    validateResult(validate, sim);
    profileStop(totalTimer);
@@ -1049,6 +1137,7 @@ int comdLjTable(SimFlat* s, double* x0, double* invDx, double* values)
 
 double comdCutoff(SimFlat* s) { return s->pot->cutoff; }
 double comdLatticeConstant(SimFlat* s) { return s->lat; }
+double comdAtomMass(SimFlat* s) { return (double)s->species[0].mass; }
 double comdVolume(SimFlat* s) { return (double)s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2]; }
 
 void comdGridInfo(SimFlat* s, int out[6])

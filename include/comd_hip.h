@@ -256,6 +256,8 @@ typedef struct SimGpuSt {
    real_t*      strainBuf;             /* device [7][nLocalBoxes*maxAtoms]: the planes E xx yy zz yz xz xy and D^2 of computeAtomStrain, allocated by its first call */
    int*         strainCountBuf;        /* device [nLocalBoxes*maxAtoms]: its neighbour counts, allocated with strainBuf */
    double*      strainSumBuf;          /* device: the workgroups' rows for computeAtomStrainSummary, allocated with strainBuf */
+   real_t*      heatFluxBuf;           /* device [9][nLocalBoxes*maxAtoms]: the planes jk, jp, jv (x y z each) of computeHeatFlux, allocated by its first call that stores them */
+   double*      heatFluxSumBuf;        /* device: the workgroups' rows for the sums of computeHeatFlux, allocated by its first call that reduces */
 } SimGpu;
 
 /* Everything AllocateGpu needs to know about the rank's geometry and potential.
@@ -511,6 +513,17 @@ void computeAtomStress(SimGpu* sim, int withKinetic, real_t* outBySlot6);
  * Seven doubles are copied, never the planes.  Same stream; deterministic two-stage reduction.  A call without a computeAtomStress before it ends the run.
  * Blocks until the result is on the host. */
 void computeAtomStressSummary(SimGpu* sim, double atomVolume, double* out);
+/* Not in the reference (CoMD has no transport output): the heat flux of THIS rank's local atoms (hip/heatflux_kernels.h), in eV A/fs (flux density x volume).
+ * For the atom in local slot o = cell * maxAtoms + index, with v = p / m and its neighbours j (local or halo image) at 0 < |r_ij|^2 <= cutoff^2,
+ *   jk = (|p|^2 / 2 m) v,   jp = e v (e: the per-atom energy of the last force evaluation),   jv = 1/2 sum_j r_ij (f_ij . v) = -s v, s the pair part of
+ * computeAtomStress: its pair convention, pair functions and acceptance test.  The virial part is one-sided, so no momentum of a halo slot is read.
+ * outBySlot9 != NULL: outBySlot9[c * nLocalBoxes * maxAtoms + o] is component c = jk x y z, jp x y z, jv x y z, nine planes in host memory; entries of empty
+ * slots mean nothing.  out9 != NULL: the nine sums over this rank's atoms, in double, through a deterministic two-stage reduction that writes nothing per atom.
+ * Either may be NULL.  Valid when computeVirial is AND e[] is current: after computeForce, or after a timestep() call (whose last step asks for the energies:
+ * comdSetEnergyNeeded), any method.  Launched on the stream computeEnergy uses, after the force work of both streams of the overlap mode; no atomics,
+ * bit-reproducible; reads r, p, e, dfEmbed, species and the cell tables, writes only its own planes or rows (allocated by the first call that needs them,
+ * freed by DestroyGpu).  Blocks until the results are on the host. */
+void computeHeatFlux(SimGpu* sim, real_t* outBySlot9, double* out9);
 /* Not in the reference (CoMD has no strain output): the reference snapshot of the per-atom strain (hip/strain_kernels.h).  on != 0: allocate and zero one
  * 32-byte record {x, y, z, spare} of doubles (in both precision builds) per global atom id and store the current position of every one of THIS rank's local
  * atoms at its gid, with plain vector stores (already on: the table is zeroed and filled again).  Halo neighbours need the records of other ranks' atoms: with
