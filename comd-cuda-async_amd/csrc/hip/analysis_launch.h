@@ -269,6 +269,8 @@ extern "C" void computeAtomStrain(SimGpu* sim, real_t rCut, real_t* outBySlot7, 
    const real_t cutoff = pairCutoff(sim);
    if (!sim->strainRefBuf) { fprintf(stderr, "computeAtomStrain: no reference (comdStrainReferenceGpu)\n"); exit(-1); }
    if (!(rCut > R(0.0)) || rCut > cutoff) { fprintf(stderr, "computeAtomStrain: rCut %g outside (0, cutoff = %g]\n", (double)rCut, (double)cutoff); exit(-1); }
+   for (int a = 0; a < 3; ++a)
+      if (!(sim->strainL[a] > 0.0)) { fprintf(stderr, "computeAtomStrain: sim->strainL[%d] = %g: set it to the current global box before the call\n", a, sim->strainL[a]); exit(-1); }
    const size_t nSlots = localSlots(sim);
    if (!sim->strainBuf) {
       sim->strainBuf = dalloc<real_t>(ATOMSTRAIN_PLANES * nSlots);
@@ -280,6 +282,7 @@ extern "C" void computeAtomStrain(SimGpu* sim, real_t rCut, real_t* outBySlot7, 
    v.gid = sim->atoms.gid; v.ref = sim->strainRefBuf; v.nRef = sim->strainRefN;
    v.rs2 = rCut * rCut;
    v.L0x = sim->strainL0[0]; v.L0y = sim->strainL0[1]; v.L0z = sim->strainL0[2];
+   v.sx = sim->strainL0[0] / sim->strainL[0]; v.sy = sim->strainL0[1] / sim->strainL[1]; v.sz = sim->strainL0[2] / sim->strainL[2];
    v.plane = nSlots;
    hipLaunchKernelGGL(AtomStrain_thread_atom, dim3(ATOMSTRAIN_BLOCKS), dim3(256), 0, st, v, sim->strainBuf, sim->strainCountBuf);
    LAUNCH_CHECK();

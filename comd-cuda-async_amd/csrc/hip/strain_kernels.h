@@ -6,7 +6,10 @@
 // local atoms with plain vector stores (one thread owns a gid); the host adds the ranks' tables and uploads the sum.
 //
 // For every local atom i, with the neighbours j (local or halo image) at 0 < |d|^2 <= rs^2 in the CURRENT configuration, d = x_j - x_i formed in
-// real_t (the halo positions carry their periodic shift) and d0 = x0[gid_j] - x0[gid_i] reduced per axis to the minimum image of L0, in double:
+// real_t (the halo positions carry their periodic shift) and d0 = x0[gid_j] - x0[gid_i] reduced per axis, in double, to the image of L0 nearest the current
+// separation mapped back to the reference box, d0 -= L0 rint((d0 - d L0 / L) / L0) with L the current global box.  That is the image the pair was accepted
+// through.  The shortest image, rint(d0 / L0), is the same one unless |d0| can pass L0 / 2 on an axis: a 2-cell axis with rs near the force cutoff, where it
+// returns the other image and d0 is wrong by a whole box length.
 //   V = sum d0 d0^T (6)   A = sum d d0^T (9)   S = sum |d|^2   n = the neighbours           -- 17 sums, in double in both builds
 //   F = A V^-1 (the adjugate of the symmetric V over its determinant), so that d ~ F d0
 //   E = 1/2 (F^T F - I)                the Green-Lagrange strain, xx yy zz yz xz xy
@@ -56,6 +59,7 @@ struct AtomStrainArgs : StencilArgs {
    int nRef;
    real_t rs2;
    double L0x, L0y, L0z;
+   double sx, sy, sz;                  // L0 / L per axis, L the current global box: a current separation mapped back to the reference box
    size_t plane;                       // nLocalBoxes * cap: the slots of one plane of the output
 };
 
@@ -85,8 +89,10 @@ void AtomStrain_thread_atom(AtomStrainArgs v, real_t* __restrict__ out, int* __r
             if ((unsigned)gj < (unsigned)v.nRef) {
                const double* __restrict__ rj = v.ref + 4 * (size_t)gj;
                double px = rj[0] - x0i, py = rj[1] - y0i, pz = rj[2] - z0i;
-               px -= v.L0x * __builtin_rint(px / v.L0x); py -= v.L0y * __builtin_rint(py / v.L0y); pz -= v.L0z * __builtin_rint(pz / v.L0z);
                const double dx = (double)ex, dy = (double)ey, dz = (double)ez;
+               // the image of d0 nearest d mapped back to the reference box: the image the pair was accepted through, not the shortest one
+               px -= v.L0x * __builtin_rint((px - dx * v.sx) / v.L0x); py -= v.L0y * __builtin_rint((py - dy * v.sy) / v.L0y);
+               pz -= v.L0z * __builtin_rint((pz - dz * v.sz) / v.L0z);
                vxx = __builtin_fma(px, px, vxx); vyy = __builtin_fma(py, py, vyy); vzz = __builtin_fma(pz, pz, vzz);
                vyz = __builtin_fma(py, pz, vyz); vxz = __builtin_fma(px, pz, vxz); vxy = __builtin_fma(px, py, vxy);
                axx = __builtin_fma(dx, px, axx); axy = __builtin_fma(dx, py, axy); axz = __builtin_fma(dx, pz, axz);

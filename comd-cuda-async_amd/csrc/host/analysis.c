@@ -234,7 +234,14 @@ static double strainRadius(SimFlat* s, double rCut)
    return rCut <= s->pot->cutoff ? rCut : 0.0;
 }
 
-static void runAtomStrain(SimFlat* s, void* const* plane, const void* rCut) { computeAtomStrain(&s->gpu, *(const real_t*)rCut, (real_t*)plane[0], (int*)plane[1]); }
+/* computeAtomStrain picks the image of a reference separation with the box of now (strain_kernels.h) */
+static void atomStrainOnTheCurrentBox(SimFlat* s, real_t rCut, real_t* planes, int* counts)
+{
+   for (int a = 0; a < 3; ++a) s->gpu.strainL[a] = (double)s->domain->globalExtent[a];
+   computeAtomStrain(&s->gpu, rCut, planes, counts);
+}
+
+static void runAtomStrain(SimFlat* s, void* const* plane, const void* rCut) { atomStrainOnTheCurrentBox(s, *(const real_t*)rCut, (real_t*)plane[0], (int*)plane[1]); }
 
 int comdAtomStrain(SimFlat* s, double rCut, double* strainByGid7, int* countByGid)
 {
@@ -251,7 +258,7 @@ int comdStrainSummary(SimFlat* s, double rCut, double threshold, double* out9)
    rCut = strainRadius(s, rCut);
    if (!(rCut > 0.0) || !(threshold > 0.0)) return -1;
    double local[9];          /* sum gamma, max gamma, gid, sum vol, sum D^2, max D^2, valid, invalid, above (computeAtomStrainSummary) */
-   computeAtomStrain(&s->gpu, (real_t)rCut, NULL, NULL);
+   atomStrainOnTheCurrentBox(s, (real_t)rCut, NULL, NULL);
    computeAtomStrainSummary(&s->gpu, threshold, local);
    const int nRanks = getNRanks(), me = getMyRank();
    if (nRanks > 1) {

@@ -253,6 +253,7 @@ typedef struct SimGpuSt {
    double*      strainRefBuf;          /* device [strainRefN][4]: the reference positions by gid of comdStrainReferenceGpu, all ranks' atoms, NULL = no reference */
    int          strainRefN;            /* records strainRefBuf holds = nGlobal */
    double       strainL0[3];           /* host: the global box when the reference was taken, in A; the host library sets it with the table */
+   double       strainL[3];            /* host: the global box now, in A; the host library sets it before every computeAtomStrain call */
    real_t*      strainBuf;             /* device [7][nLocalBoxes*maxAtoms]: the planes E xx yy zz yz xz xy and D^2 of computeAtomStrain, allocated by its first call */
    int*         strainCountBuf;        /* device [nLocalBoxes*maxAtoms]: its neighbour counts, allocated with strainBuf */
    double*      strainSumBuf;          /* device: the workgroups' rows for computeAtomStrainSummary, allocated with strainBuf */
@@ -533,7 +534,9 @@ void computeHeatFlux(SimGpu* sim, real_t* outBySlot9, double* out9);
 int comdStrainReferenceGpu(SimGpu* sim, int nGlobal, int on);
 /* Not in the reference: the Green-Lagrange strain and the non-affine displacement D^2min (Falk and Langer) of every one of THIS rank's local atoms against
  * the reference table.  For the atom in local slot o = cell * maxAtoms + index, with its neighbours j (local or halo image) at 0 < |d|^2 <= rCut^2 in the
- * CURRENT configuration, d = x_j - x_i, and d0 = x0[gid_j] - x0[gid_i] reduced per axis to the minimum image of strainL0:
+ * CURRENT configuration, d = x_j - x_i, and d0 = x0[gid_j] - x0[gid_i] reduced per axis to the image of strainL0 nearest the current separation mapped
+ * back to the reference box, d0 -= strainL0 rint((d0 - d strainL0 / strainL) / strainL0), the image the pair was accepted through (the shortest image is
+ * another one where |d0| passes strainL0 / 2: a 2-cell axis with rCut near the force cutoff).  sim->strainL must hold the current global box:
  *   V = sum d0 d0^T, A = sum d d0^T, S = sum |d|^2 (doubles in both builds), F = A V^-1, E = 1/2 (F^T F - I), D^2 = max(0, S - F:A) = sum |d - F d0|^2.
  * outBySlot7[c * nLocalBoxes * maxAtoms + o]: c = 0..5 E xx yy zz yz xz xy, c = 6 D^2 in A^2; outCountBySlot[o]: the neighbours n.  An atom with n < 3 or
  * det V <= 1e-9 (tr V / 3)^3 has NaN in all seven planes and its n.  Entries of empty slots mean nothing.  NULL output pointers: the planes stay on the device

@@ -1,5 +1,5 @@
-"""The analysis kernels on sparse, void and dense states: the virial, the pair histogram, centro-symmetry, common neighbour analysis, per-atom stress and
-per-atom strain (with the two device reductions) in the eight regimes of tests/test_density_regimes.py, where cells are empty, hold 1 to 4 atoms or
+"""The analysis kernels on sparse, void and dense states: the virial, the pair histogram, centro-symmetry, common neighbour analysis, per-atom stress,
+per-atom strain (with the two device reductions) and the heat flux in the eight regimes of tests/test_density_regimes.py, where cells are empty, hold 1 to 4 atoms or
 six waves of them, and atoms have no neighbour at all.
 
 Every other test of these kernels runs where all cells are occupied and nearly evenly filled.  What hip/stencil_walk.h and hip/nearest12_walk.h do
@@ -30,6 +30,13 @@ Largest error / bound observed on an MI355X when the module was written, double 
   stress pair / kinetic part    0.019, 0.66 | 0.55, 0.70                 rows against -W, -(K + W)    2.1e-4, 0.030 | 6.9e-3, 5.2e-3
   stress reduction              means 3.1e-4, extremes 0.021 | 2.9e-4, 0.021
   strain E, D^2 (C = 1)         0.11, 0.087 | 4.2e-3, 9.6e-4             strain reduction             means 7.8e-4, extremes 0.019 | 6.5e-4, 0
+  heat flux columns             kinetic 0.47, potential 6.4e-3, virial 0.018 | 0.40, 0.48, 0.42           sums against the rows 0.33 | 0; two ranks 1.2e-4 | 6.4e-3
+
+The heat-flux leg (_check_heat_flux; lj_dense stays PAIR_ONLY, it is state A of test_heat_flux) runs wherever the stress leg runs: in the regimes at both stages, the layouts,
+the message halo (nine planes and four sums), two ranks (tests/heatflux_worker.py) and the executable (--heatflux).  Its rules are test_heat_flux.py's, with the per-atom
+energies of the potential columns from an all-pairs sum in numpy, not from gather(3).  An atom without a neighbour has B_i = 0 and virial columns exactly 0 (every atom of
+lj_void, whose potential columns are exactly 0 too); the 20 such atoms of eam_void carry F(0) v_i, and F(0) = 0 for Cu_u6.eam.  In the float build the virial columns
+inherit FLOAT_STRESS_LEFT_OUT: a CPU test puts the float pair function through -s_i v_i with the checker's momenta (FLOAT_FLUX_FACTORS).
 
 Bounds that are not an imported module's, with the reasoning (none is fitted to a measurement):
   K against sum p p^T / m       1e-12 of the largest component (float build 1e-5, the float rule of the virial): a sum of at most 8736 products in double,
@@ -56,7 +63,7 @@ import test_csp as csp
 import test_density_regimes as dr
 import test_rdf as rdf
 from test_density_regimes import HOT, REGIMES, _extent, _flags, _make, _neighbour_counts
-from test_pressure import CSRC, EPS as LJ_EPS, HERE, ROOT, SIGMA, SINGLE, _child, _interpolate, _pairs, _rel, _tensor
+from test_pressure import CSRC, EPS as LJ_EPS, HERE, ROOT, SIGMA, SINGLE, TOL, _child, _interpolate, _pairs, _rel, _tensor
 
 DELTA = rdf.DELTA32 if SINGLE else rdf.DELTA64
 EPS_REAL = stress.EPS24 if SINGLE else stress.EPS53
@@ -91,6 +98,10 @@ FLOAT_LEFT_OUT = {("eam_void", 0): 2, ("eam_dense", 0): 62, ("eam_dense", 1): 58
 # steps).  In the float leg the comparison of the pair part with the restatement is left out in these regimes, by name; what does not hang on that bound stays (atoms
 # without neighbours exactly 0, the kinetic part, the rows against virial(), the reduction against numpy).
 FLOAT_STRESS_LEFT_OUT = {"eam_void": (7.4, 1.9), "eam_sparse": (4.0, 1.6)}
+# The virial columns of the heat flux are -s_i v_i, so their float comparison inherits the omission.  The same float pair function through -s_i v_i with the checker's
+# momenta against (n + 64) 2^-24 B (the CPU test that shows the factors above), double checker's positions at (step 0, after the steps); the float checker's give
+# 7.4, 0.26 and 1.5, 0.57.
+FLOAT_FLUX_FACTORS = {"eam_void": (7.2, 0.71), "eam_sparse": (0.86, 0.36)}
 # Regimes in which the one-pass form of D^2 (S - F : A, the kernel's) misses test_atomic_strain's bound (n + 64) eps S when evaluated in numpy in double on the checker's
 # positions, by the conditioning of the state alone (CPU test below): there D^2 is held to that bound times kappa(V_i), the factor the bound on E carries already.
 D2_BY_KAPPA = ("lj_sparse", "eam_void", "eam_sparse")
@@ -287,7 +298,64 @@ def _check_stress(sim, name, what, pos, box, rc, w, k):
         # every von Mises stress is 0: the gid is decided by the "lowest gid of equals" rule alone, across the workgroups of the reduction
         assert not s0.any()
         assert summary0 == {"mean_pressure": 0.0, "min_pressure": 0.0, "max_pressure": 0.0, "mean_von_mises": 0.0, "max_von_mises": 0.0, "max_von_mises_gid": 0, "n": 144}
-    return s0, s1, summary0, summary1
+    return s0, s1, summary0, summary1, (want, big_a, cnt)
+
+
+def _check_heat_flux(sim, name, what, pos, box, rc, restated):
+    """The rules of test_heat_flux.py's docstring on the restatement _check_stress has made (want, A, n): the virial columns against -s_i v_i within 1e-11 B_i,a (float
+    build (n_i + 64) 2^-24 B_i,a; the regimes of FLOAT_STRESS_LEFT_OUT aside, as the stress they are made of), and exactly 0 for an atom without a neighbour, whose B is
+    0; the kinetic columns by test_heat_flux._convective; the potential columns against e_ref,i v_i with e_ref from the all-pairs sums of test_density_regimes on the
+    gathered positions -- not gather(3), the array the kernel reads -- within (per_atom_energy_abs + 8 eps (|e_i| + ke_i)) |v_i,a|; heat_flux() against the column sums
+    (test_reduction_is_the_sum_of_the_rows, k from the run); heat_flux_density().  lj_void: every potential and virial column is exactly 0.  An EAM atom without
+    a neighbour carries F(0) v_i."""
+    import math
+    import test_heat_flux as hf
+    g = REGIMES[name]
+    want, big_a, cnt = restated
+    mom, mass = sim.gather(1).copy(), sim.mass
+    v = mom / mass
+    assert np.abs(v).min() > 0.0                                        # no velocity component is 0: every column is there to be seen
+    j, sums = sim.atomic_heat_flux(), sim.heat_flux()
+    assert j.shape == (len(pos), 9) and j.dtype == np.float64
+    lone = cnt == 0
+    b = hf._times_v(big_a, np.abs(v))
+    assert not b[lone].any() and np.all(b[~lone] > 0.0)                 # B_i = 0 for the atoms without a neighbour and for no other (test_figures_of_the_regimes counts them)
+    bound = ((cnt[:, None] + 64.0) * stress.EPS24 * b) if SINGLE else 1e-11 * b
+    assert not j[lone, 6:9].any()                                       # no neighbour: the virial columns are exactly 0
+    if not (SINGLE and name in FLOAT_STRESS_LEFT_OUT):
+        stress._assert_close(j[:, 6:9], -hf._times_v(want, v), bound, f"{what} heat flux, virial columns")
+        with np.errstate(invalid="ignore", divide="ignore"):
+            _ratio("heat flux virial", np.where(bound > 0.0, np.abs(j[:, 6:9] + hf._times_v(want, v)) / np.where(bound > 0.0, bound, 1.0), 0.0).max())
+    if g.eam:
+        tables = [sim.eam_table(which) for which in range(3)]
+        e_ref = dr._eam_all_pairs(pos, box, rc, tables)[1]
+        f0 = float(_interpolate(*tables[2], np.zeros(1))[0][0])
+        assert np.all(e_ref[lone] == f0)                                # rhobar = 0: the atom carries F(0) v_i (Cu_u6.eam: F(0) = 0, so its potential columns are 0 too)
+        if f0 == 0.0:
+            assert not j[lone, 3:6].any()
+    else:
+        e_ref = np.asarray(dr._lj_all_pairs(pos, box, rc)[1], dtype=np.float64)
+    jk, jp, mag = hf._convective(e_ref, mom, mass)
+    tol = TOL["per_atom_energy_abs"]                                    # reference_values.json tolerances / tolerances_single
+    stress._assert_close(j[:, 0:3], jk, 8.0 * EPS_REAL * mag, f"{what} heat flux, kinetic columns")
+    stress._assert_close(j[:, 3:6], jp, tol * np.abs(v) + 8.0 * EPS_REAL * mag, f"{what} heat flux, potential columns")
+    _ratio("heat flux kinetic", (np.abs(j[:, 0:3] - jk) / (8.0 * EPS_REAL * mag)).max())
+    _ratio("heat flux potential", (np.abs(j[:, 3:6] - jp) / (tol * np.abs(v) + 8.0 * EPS_REAL * mag)).max())
+    if name == "lj_void":
+        assert lone.all() and not e_ref.any() and not j[:, 3:9].any()
+    k = math.ceil(math.ceil(sim.n_local_boxes * math.ceil(sim.max_atoms / 64) / 2048) / 4)
+    assert k == 1, (sim.n_local_boxes, sim.max_atoms)
+    rows = np.abs(j).sum(0)
+    for i, part in enumerate(("kinetic", "potential", "virial")):
+        cols = slice(3 * i, 3 * i + 3)
+        stress._assert_close(sums[part], j[:, cols].sum(0), (k + 2) * EPS_REAL * rows[cols], f"{what} heat flux, {part} sum")
+        with np.errstate(invalid="ignore", divide="ignore"):
+            _ratio("heat flux sums", np.where(rows[cols] > 0.0, np.abs(sums[part] - j[:, cols].sum(0)) / np.where(rows[cols] > 0.0, (k + 2) * EPS_REAL * rows[cols], 1.0), 0.0).max())
+    total = j[:, 0:3].sum(0) + j[:, 3:6].sum(0) + j[:, 6:9].sum(0)
+    stress._assert_close(sums["total"], total, (k + 3) * EPS_REAL * (rows[0:3] + rows[3:6] + rows[6:9]), f"{what} heat flux, total")
+    assert np.array_equal(sums["total"], (sums["kinetic"] + sums["potential"]) + sums["virial"])
+    assert np.array_equal(sim.heat_flux_density(), sums["total"] / sim.volume)
+    return j, sums
 
 
 def _check_strain_summary(sim, what, got, m, rc):
@@ -344,7 +412,8 @@ def _analyse(sim, name, k, what, reference=None, exact=False, regular_cells=True
     if not (SINGLE and (name, k) in FLOAT_LEFT_OUT):
         out["csp"], out["coord"] = _check_csp(sim, name, what, pos, box, rc)
     out["cna"] = _check_cna(sim, name, what, pos, box, rc)
-    out["s0"], out["s1"], out["stress_summary0"], out["stress_summary1"] = _check_stress(sim, name, what, pos, box, rc, out["w"], out["k"])
+    out["s0"], out["s1"], out["stress_summary0"], out["stress_summary1"], restated = _check_stress(sim, name, what, pos, box, rc, out["w"], out["k"])
+    out["j"], out["heat_flux"] = _check_heat_flux(sim, name, what, pos, box, rc, restated)
     if reference is not None:
         (out["e"], out["d2"], out["n"]), out["strain_summary"], out["m"] = _check_strain(sim, name, what, pos, box, rc, *reference)
     return out
@@ -352,6 +421,25 @@ def _analyse(sim, name, k, what, reference=None, exact=False, regular_cells=True
 
 # ================================================================ CPU
 _CPU = {}
+_MOMENTA = {}
+
+
+def _cpu_momenta(orc, name):
+    """the checker's momenta at step 0 and after the regime's steps (dr._reference keeps none); once per regime"""
+    if name not in _MOMENTA:
+        g = REGIMES[name]
+        o = _make(orc, g)
+        p0 = o.gather(orc.P).copy()
+        o.step(g.steps)
+        _MOMENTA[name] = (p0, o.gather(orc.P).copy())
+        o.close()
+    return _MOMENTA[name]
+
+
+def _checker_pair_function(ref, snap):
+    if ref["g"].eam:
+        return stress._pair_function("eam", ref["tables"][0], ref["tables"][1], snap["df"])
+    return stress._pair_function("lj")
 
 
 def _cpu_figures(orc, name):
@@ -385,6 +473,15 @@ def _cpu_figures(orc, name):
         out["invalid_by_count"] = int((m["n"] < 3).sum())
         out["det"] = float(m["det_ratio"][valid].min()) if valid.any() else None
         out["kappa"] = float(m["kappa"][valid].max()) if valid.any() else None
+        # what decides the heat-flux leg: the atoms whose B_i = sum_b A_i,ab |v_i,b| is 0 (their virial columns must be exactly 0) and the velocity components that are 0
+        import test_heat_flux as hf
+        out["b_zero"], out["v_zero"] = [], []
+        for pos, snap, p in zip(states, (ref["s0"], ref["sk"]), _cpu_momenta(orc, name)):
+            _, big_a, _ = stress._restate(pos.astype(np.float64), box, rc, _checker_pair_function(ref, snap))
+            b = hf._times_v(big_a, np.abs(p))
+            assert np.array_equal((b == 0.0).any(1), (b == 0.0).all(1))
+            out["b_zero"].append(int((b == 0.0).all(1).sum()))
+            out["v_zero"].append(int((p == 0.0).sum()))
     _CPU[name] = out
     return out
 
@@ -423,6 +520,8 @@ def test_figures_of_the_regimes(orc, name):
         return
     for counts in got["cna"]:
         assert counts[fig["cna"]] == fig["atoms"], (name, counts)
+    # the heat-flux leg: B_i = 0 for the atoms without a neighbour and for no other (in lj_void that is every atom), and no velocity component is 0
+    assert tuple(got["b_zero"]) == fig["none"] and got["v_zero"] == [0, 0], (name, got["b_zero"], got["v_zero"])
     assert got["invalid"] == got["invalid_by_count"]                    # none by the determinant: the singular state below is the one that is
     if not SINGLE:
         assert got["invalid"] == fig["invalid"], (name, got["invalid"])
@@ -475,8 +574,9 @@ def test_float_pair_function_alone_against_the_float_stress_bound(orc, name):
     f32 = np.float32
     ref = dr._reference(orc, name)
     g, box, rc = ref["g"], _box(ref["g"]), ref["rc"]
-    worst = []
-    for snap in (ref["s0"], ref["sk"]):
+    import test_heat_flux as hf
+    worst, worst_b = [], []
+    for snap, p in zip((ref["s0"], ref["sk"]), _cpu_momenta(orc, name)):
         pos = snap["r"].astype(np.float64)
         if g.eam:
             phi, rho, _ = ref["tables"]
@@ -488,7 +588,20 @@ def test_float_pair_function_alone_against_the_float_stress_bound(orc, name):
         got, _, _ = stress._restate(pos, box, rc, lambda i, j, r: rounded(i, j, r.astype(f32)).astype(np.float64))
         bound = (cnt[:, None] + 64.0) * stress.EPS24 * big_a
         worst.append(float(np.where(bound > 0.0, np.abs(got - want) / np.where(bound > 0.0, bound, 1.0), 0.0).max()))
-    print(f"{name}: the pair function in float32 against the float rule, error / bound at step 0 and after the steps: {worst[0]:.3g}, {worst[1]:.3g}")
+        # the virial columns of the heat flux, -s_i v_i with the checker's momenta (v = p / m: the ratio does not hang on m), against (n + 64) 2^-24 B_i,a
+        bound_b = (cnt[:, None] + 64.0) * stress.EPS24 * hf._times_v(big_a, np.abs(p))
+        worst_b.append(float(np.where(bound_b > 0.0, np.abs(hf._times_v(got - want, p)) / np.where(bound_b > 0.0, bound_b, 1.0), 0.0).max()))
+    print(f"{name}: the pair function in float32 against the float rule, error / bound at step 0 and after the steps: {worst[0]:.3g}, {worst[1]:.3g}; "
+          f"through -s v against the B bound: {worst_b[0]:.3g}, {worst_b[1]:.3g}")
+    # the heat-flux leg of the float build leaves out what the stress leg leaves out, and no other.  On the float checker's positions -- the build the omission is for --
+    # both regimes miss the B bound (7.4, 0.26 and 1.5, 0.57); on the double checker's eam_void does (7.2, 0.71) and eam_sparse comes to 0.86, 0.36 of it: v_i weights
+    # the components of s_i, so the worst component of -s_i v_i is relatively better than the worst of s_i
+    if name in FLOAT_STRESS_LEFT_OUT:
+        assert max(worst_b) > (1.0 if SINGLE or name == "eam_void" else 0.5), (name, worst_b)
+        for got, recorded in zip(worst_b, FLOAT_FLUX_FACTORS[name]):
+            assert SINGLE or abs(got / recorded - 1.0) <= 0.05, (name, worst_b)
+    else:
+        assert max(worst_b) <= 1.0, (name, worst_b)
     if name in FLOAT_STRESS_LEFT_OUT:
         assert max(worst) > 1.0, (name, worst)
         for got, recorded in zip(worst, FLOAT_STRESS_LEFT_OUT[name]):          # (recorded from the double checker's positions, to two digits; the float checker's give 8.4, 0.71 and 4.8, 3.4)
@@ -790,7 +903,8 @@ ALL_SIX = """
     w, k = sim.virial()
     e, d2, n = sim.atomic_strain(rc)
     c, coord = sim.centro_symmetry(r_coord=rc)
-    np.savez({out!r}, pos=sim.gather(0), w=w, k=k, counts=sim.pair_histogram({bins})[1], csp=c, coord=coord, cna=sim.common_neighbor_analysis(),
+    flux = sim.heat_flux()
+    np.savez({out!r}, pos=sim.gather(0), w=w, k=k, j=sim.atomic_heat_flux(), j_kinetic=flux["kinetic"], j_potential=flux["potential"], j_virial=flux["virial"], j_total=flux["total"], counts=sim.pair_histogram({bins})[1], csp=c, coord=coord, cna=sim.common_neighbor_analysis(),
              s0=sim.atomic_stress(kinetic=False), s1=sim.atomic_stress(kinetic=True), e=e, d2=d2, n=n,
              stress_summary=json.dumps(sim.stress_summary()), strain_summary=json.dumps(sim.strain_summary(cutoff=rc)), halo=int(sim.cells()["nAtoms"][sim.n_local_boxes:].sum()))
     sim.close()
@@ -814,13 +928,14 @@ def test_message_halo_gives_the_mirrored_halos_bits(tmp_path, name):
     a = _all_six_in_child(tmp_path, "mirror", _flags(g, "thread_atom", 0), g.steps, {"COMD_HALO_MIRROR": "1"})
     b = _all_six_in_child(tmp_path, "message", _flags(g, "thread_atom", 0), g.steps, {"COMD_HALO_MIRROR": "0"})
     assert int(a["halo"]) > 0 and int(a["halo"]) == int(b["halo"]) and a["counts"].sum() > 0 and np.isnan(a["e"]).any() and not np.isnan(a["e"]).all()
+    assert a["j"].shape == (g.atoms, 9) and np.abs(a["j"]).max(0).min() > 0.0 and {"j", "j_kinetic", "j_potential", "j_virial", "j_total"} <= set(a.files)
     for key in a.files:
         assert np.array_equal(a[key], b[key], equal_nan=a[key].dtype.kind == "f"), key
 
 
 # ================================================================ GPU 4: two ranks sharing the device
 RANKS = {"lj_sparse": (1, 1, 2), "eam_sparse": (2, 1, 1), "lj_void": (2, 1, 1)}
-WORKERS = ("pressure", "rdf", "csp", "cna", "stress", "strain")
+WORKERS = ("pressure", "rdf", "csp", "cna", "stress", "heatflux", "strain")
 _ONE_RANK = {}
 
 
@@ -849,6 +964,15 @@ def _one_rank(gpu, name):
             sim.step(g.steps)
             out["strain"], out["strain_summary"] = sim.atomic_strain(), sim.strain_summary()
             out["m"] = strain._restate(sim.gather(0).copy(), box, pos, box, rc, dtype=REAL)
+        # the heat flux as tests/heatflux_worker.py takes it: at step 0, after a scatter of the seeded momenta of test_heat_flux._new_momenta (the halo slots keep the old ones)
+        import test_heat_flux as hf
+        with gpu.Simulation(_rank_flags(name)) as sim:
+            p = hf._new_momenta(sim.n_global, sim.mass)
+            sim.scatter(1, p)
+            out["j"], out["j_sums"] = sim.atomic_heat_flux(), sim.heat_flux()
+            v = p / sim.mass
+            out["b_max"], out["v_max"] = float(hf._times_v(big_a, np.abs(v)).max()), float(np.abs(v).max())
+            out["conv_max"] = float(hf._convective(sim.gather(3).copy(), p, sim.mass)[2].max())
         _ONE_RANK[name] = out
     return _ONE_RANK[name]
 
@@ -939,6 +1063,31 @@ def test_two_ranks_give_the_one_rank_results(gpu, tmp_path, name, worker):
                 assert abs(summary[key] - sum0[key]) <= 4.0 * bound / one["omega"], key
             if name == "lj_void":
                 assert not s.any() and summary == sum0 and summary["max_von_mises_gid"] == 0 and summary["max_von_mises"] == 0.0
+    elif worker == "heatflux":
+        # test_heat_flux.py::test_ranks_give_the_one_rank_array: every rank returns the global array, the one-rank one within 1e-12 of the largest magnitude of the part,
+        # and the sums over the ranks within 1e-12 of the sums of magnitudes.  Float build: two runs, each within the module's float bounds of the exact columns --
+        # (n + 64) 2^-24 B for the virial ones, 8 x 2^-24 (|e| + ke) |v| for the convective ones, whose e_i the two runs hold within per_atom_energy_abs each -- and
+        # the sums within the sum of the atoms' bounds plus the (k + 3) 2^-24 of the two reductions.
+        _launch(worker, grid, [str(tmp_path), args])
+        j0, sums0 = one["j"], one["j_sums"]
+        if SINGLE:
+            conv = 2.0 * (8.0 * stress.EPS24 * one["conv_max"] + TOL["per_atom_energy_abs"] * one["v_max"])
+            scale = np.array([conv] * 6 + [2.0 * (one["n_max"] + 64.0) * stress.EPS24 * one["b_max"]] * 3)
+        else:
+            scale = 1e-12 * np.array([one["conv_max"]] * 6 + [one["b_max"]] * 3)
+        mag = np.abs(j0).sum(0)
+        sum_bound = (len(j0) * scale + 8.0 * stress.EPS24 * mag) if SINGLE else 1e-12 * mag
+        for r in range(2):
+            d = np.load(tmp_path / f"heatflux_rank{r}.npz")
+            assert d["j"].shape == j0.shape == (REGIMES[name].atoms, 9)
+            err = np.abs(d["j"] - j0).max(0)
+            print(f"RATIO heat flux ranks {name} rank {r}:", (err / np.where(scale > 0.0, scale, 1.0)).max())
+            assert np.all(err <= scale), (name, err, scale)
+            for i, part in enumerate(("kinetic", "potential", "virial")):
+                assert np.all(np.abs(d["sums"][3 * i:3 * i + 3] - sums0[part]) <= sum_bound[3 * i:3 * i + 3]), part
+            assert np.all(np.abs(d["sums"][9:12] - sums0["total"]) <= sum_bound[0:3] + sum_bound[3:6] + sum_bound[6:9])
+            if name == "lj_void":
+                assert not d["j"][:, 3:9].any() and not d["sums"][3:9].any()          # no pair at all: the potential and virial parts are exactly 0 on both ranks
     else:
         g = REGIMES[name]
         _launch(worker, grid, [str(tmp_path), str(g.steps), args])
@@ -987,7 +1136,9 @@ EXE_RUN = """
     sim.set_strain_reference()
     for _ in range(3):
         sim.step(10)
-    print("PYTHON", json.dumps([sim.strain_summary(cutoff=sim.cutoff), sim.stress_summary(), sim.structure_counts(), int(np.isinf(sim.centro_symmetry()[0]).sum())]))
+    flux = sim.heat_flux()
+    print("PYTHON", json.dumps([sim.strain_summary(cutoff=sim.cutoff), sim.stress_summary(), sim.structure_counts(), int(np.isinf(sim.centro_symmetry()[0]).sum()),
+                                [flux[k].tolist() for k in ("kinetic", "potential", "virial", "total")], sim.volume]))
     sim.close()
 """
 
@@ -1000,19 +1151,22 @@ def test_comd_hip_with_every_analysis_on_eam_sparse(tmp_path):
     g = REGIMES["eam_sparse"]
     flags = [str(a) for a in _flags(g, "thread_atom", 0)]
     proc = subprocess.run([os.path.join(CSRC, "comd-hip"), "-d", os.path.join(ROOT, "pots"), *flags, "-N", "30", "-n", "10", "--pressure", "--rdf", "48", "--csp", "--cna",
-                           "--stress", "--strain", "--strainCutoff", "4.95"], capture_output=True, text=True, cwd=tmp_path, timeout=300)
+                           "--stress", "--strain", "--strainCutoff", "4.95", "--heatflux"], capture_output=True, text=True, cwd=tmp_path, timeout=300)
     assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-2000:]
     header = [line for line in proc.stdout.splitlines() if line.startswith("#  Loop")][0].split()
-    assert header[-2:] == ["MaxVM(GPa)", "MaxShear"] and "Pressure(GPa)" in header, header
+    extra = header[header.index("Atoms") + 1:]                          # the columns behind "# Atoms", as the rows have them
+    assert [h for h in extra if h != "Jx(eV/A^2/fs)"][-2:] == ["MaxVM(GPa)", "MaxShear"] and "Pressure(GPa)" in extra and "Jx(eV/A^2/fs)" in extra, header
+    vm, shear, jx = (extra.index(h) for h in ("MaxVM(GPa)", "MaxShear", "Jx(eV/A^2/fs)"))
     rows = re.findall(r"^\s+(\d+)\s+(\d+\.\d+\s+\S+\s+\S+\s+\S+\s+\S+)\s+\S+\s+(\d+)(.*)$", proc.stdout, flags=re.M)
-    assert [r[0] for r in rows] == ["0", "10", "20", "30"] and all(int(r[2]) == g.atoms for r in rows)
+    assert [r[0] for r in rows] == ["0", "10", "20", "30"] and all(int(r[2]) == g.atoms and len(r[3].split()) == len(extra) for r in rows)
     for r in rows:
         assert "nan" not in " ".join(r).lower() and "inf" not in " ".join(r).lower(), r
         assert np.all(np.isfinite([float(x) for x in r[1].split() + r[3].split()]))
-    assert float(rows[0][3].split()[-1]) == 0.0 and float(rows[-1][3].split()[-1]) > 0.0 and float(rows[-1][3].split()[-2]) > 0.0
+    assert float(rows[0][3].split()[shear]) == 0.0 and float(rows[-1][3].split()[shear]) > 0.0 and float(rows[-1][3].split()[vm]) > 0.0
+    assert all(float(r[3].split()[jx]) != 0.0 for r in rows)
     child = _child(EXE_RUN.format(args=_flags(g, "thread_atom", 0)), env={"COMD_PRECISION": "double"})
     assert child.returncode == 0, child.stdout[-2000:] + child.stderr[-2000:]
-    strain_py, stress_py, cna_py, few_py = json.loads(re.search(r"^PYTHON (.*)$", child.stdout, flags=re.M).group(1))
+    strain_py, stress_py, cna_py, few_py, flux_py, volume_py = json.loads(re.search(r"^PYTHON (.*)$", child.stdout, flags=re.M).group(1))
 
     def last(name):
         lines = (tmp_path / name).read_text().splitlines()
@@ -1024,9 +1178,15 @@ def test_comd_hip_with_every_analysis_on_eam_sparse(tmp_path):
     assert row == [30.0, 480.0, 0.0, 0.0, 0.0] and cna_py == {"other": 480, "fcc": 0, "hcp": 0, "ico": 0}
     row = last("strain.dat")
     assert row[0] == 30.0 and row[8] == strain_py["invalid"] > 0 and row[3] == strain_py["max_shear_gid"] and np.all(np.isfinite(row))
-    assert abs(row[2] - strain_py["max_shear"]) <= 1e-14 * row[2] and abs(row[2] - float(rows[-1][3].split()[-1])) <= 1e-10
+    assert abs(row[2] - strain_py["max_shear"]) <= 1e-14 * row[2] and abs(row[2] - float(rows[-1][3].split()[shear])) <= 1e-10
     row = last("stress.dat")
     assert row[0] == 30.0 and row[6] == stress_py["max_von_mises_gid"] and np.all(np.isfinite(row))
+    # heatflux.dat: step, time, J V (3), its convective part (3), its virial part (3) -- test_heat_flux.py holds the rows to heat_flux() of a Python run to the bit
+    row = np.array(last("heatflux.dat"))
+    kin, pot, vir, tot = (np.array(x) for x in flux_py)
+    assert row[0] == 30.0 and len(row) == 11 and np.all(np.isfinite(row))
+    assert np.array_equal(row[2:5], tot) and np.array_equal(row[8:11], vir) and np.array_equal(row[5:8], kin + pot)
+    assert abs(float(rows[-1][3].split()[jx]) - tot[0] / volume_py) <= 1e-10 * abs(tot[0] / volume_py)      # the column prints 11 digits
     table = rdf._rdf_file(tmp_path / "rdf.dat")[1]
     assert table.shape == (48, 4) and np.all(np.isfinite(table)) and table[:, 3].sum() > 0
 

@@ -61,15 +61,31 @@ def _adjugate_fit(vm, am):
     return am @ c / np.where(det != 0.0, det, 1.0)[:, None, None], det
 
 
-def _restate(pos, box, ref, box0, rs, dtype=np.float64, block=256):
+def _image_of_d0(d0, dd, box, box0, image):
+    """the integer image per pair and axis that d0 = ref_j - ref_i is reduced by.  "nearest" (per axis; the kernel's): the image nearest the current separation
+    mapped back to the reference box, rint((d0 - d box0 / box) / box0) -- the image the pair was accepted through.  "minimum": the shortest one, rint(d0 / box0),
+    the rule before; another image where |d0| passes box0 / 2 on an axis, which takes a 2-cell axis and rs near the force cutoff.  A sequence of three names
+    selects the rule per axis."""
+    rules = (image,) * 3 if isinstance(image, str) else tuple(image)
+    assert len(rules) == 3 and all(r in ("nearest", "minimum") for r in rules), image
+    k = np.empty_like(d0)
+    for a, rule in enumerate(rules):
+        k[:, a] = np.rint(((d0[:, a] - dd[:, a] * box0[a] / box[a]) if rule == "nearest" else d0[:, a]) / box0[a])
+    return k
+
+
+def _restate(pos, box, ref, box0, rs, dtype=np.float64, block=256, image="nearest", image_rows=None):
     """The definitions of the issue, all pairs under the minimum image: for atom i the neighbours j with 0 < |d|^2 <= rs^2, d = x_j - x_i of the CURRENT
-    positions formed in `dtype` (the periodic shift applied to x_j, as the halo copies carry it), d0 = ref_j - ref_i reduced to the minimum image of box0
-    in double, V = sum d0 d0^T, A = sum d d0^T, F = A adj(V) / det V, E = 1/2 (F^T F - I), D^2 = sum |d - F d0|^2 (the direct form).  Invalid
-    (n < 3 or det V <= 1e-9 (tr V / 3)^3): NaN.  Returns a dict with e, d2, n and what the bounds need: kappa, s, rmin, det_ratio."""
+    positions formed in `dtype` (the periodic shift applied to x_j, as the halo copies carry it), d0 = ref_j - ref_i reduced in double to the image of box0
+    that `image` selects per axis (_image_of_d0; default: the one nearest d mapped back to the reference box), V = sum d0 d0^T, A = sum d d0^T,
+    F = A adj(V) / det V, E = 1/2 (F^T F - I), D^2 = sum |d - F d0|^2 (the direct form).  Invalid
+    (n < 3 or det V <= 1e-9 (tr V / 3)^3): NaN.  Returns a dict with e, d2, n and what the bounds need: kappa, s, rmin, det_ratio.  image_rows: a list
+    that receives arrays of rows (i, j, kx, ky, kz), the accepted ordered pairs with the integer images their d0 was reduced by."""
     n = len(pos)
     p = [np.ascontiguousarray(pos[:, a].astype(dtype)) for a in range(3)]
     lc = [dtype(box[a]) for a in range(3)]
     rs2 = dtype(rs) * dtype(rs)
+    box, box0 = np.asarray(box, dtype=np.float64), np.asarray(box0, dtype=np.float64)
 
     def pairs(s0, m):
         d = []
@@ -81,12 +97,14 @@ def _restate(pos, box, ref, box0, rs, dtype=np.float64, block=256):
         ii, jj = np.nonzero((r2 > 0) & (r2 <= rs2))
         dd = np.stack([da[ii, jj].astype(np.float64) for da in d], axis=1)
         d0 = ref[jj] - ref[s0 + ii]
-        d0 -= box0[None, :] * np.rint(d0 / box0[None, :])
+        k = _image_of_d0(d0, dd, box, box0, image)
+        d0 -= box0[None, :] * k
+        images.append(np.column_stack([s0 + ii, jj, k.astype(np.int64)]))
         return ii, jj, dd, d0
 
     vm, am = np.zeros((n, 3, 3)), np.zeros((n, 3, 3))
     s, cnt, rmin = np.zeros(n), np.zeros(n, dtype=np.int64), np.full(n, np.inf)
-    lists7 = []
+    lists7, images = [], []
     for s0 in range(0, n, block):
         m = min(block, n - s0)
         ii, jj, dd, d0 = pairs(s0, m)
@@ -104,6 +122,8 @@ def _restate(pos, box, ref, box0, rs, dtype=np.float64, block=256):
     invalid = (cnt < 3) | (det <= 1e-9 * tr3 ** 3)
     g = 0.5 * (np.swapaxes(f, 1, 2) @ f - np.eye(3)[None])
     e = np.stack([g[:, 0, 0], g[:, 1, 1], g[:, 2, 2], g[:, 1, 2], g[:, 0, 2], g[:, 0, 1]], axis=1)
+    if image_rows is not None:                                  # (before the second walk, which forms the same rows again)
+        image_rows.extend(images)
     d2 = np.zeros(n)
     for s0 in range(0, n, block):                               # second walk: the direct form of D^2 needs F
         m = min(block, n - s0)

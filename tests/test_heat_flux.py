@@ -2,7 +2,8 @@
 atomic_heat_flux / heat_flux_density, heat_flux_acf, comd-hip --heatflux).
 
 CoMD computes no heat flux, so nothing here is compared with a recorded number.  The checks are restatement and physics, on the states of
-tests/test_atom_stress.py (together they cover every chunk class of hip/stencil_walk.h):
+tests/test_atom_stress.py (together they cover every chunk class of evenly filled cells of hip/stencil_walk.h; the classes with empty stencil cells, atoms
+without a neighbour and chunks of 1 to 3 atoms are the heat-flux leg of tests/test_analysis_regimes.py, the 2-cell and straining boxes tests/test_per_atom_fields_edges.py):
   * every atom's virial part jv_i = 1/2 sum_j r_ij (f_ij . v_i) against -s_i v_i, with s_i the all-pairs minimum-image tensor of test_atom_stress._restate
     and, for the -P splines, the tensor of Simulation.atomic_stress(kinetic=False);
   * the convective parts against gather(3), gather(1) and the mass, formed in extended precision;

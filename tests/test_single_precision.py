@@ -17,6 +17,7 @@ import pytest
 from test_analysis_regimes import GPU_CASE_COUNT as ANALYSIS_REGIMES_GPU_CASE_COUNT
 from test_capacities import GPU_CASE_COUNT
 from test_kernel_legs import FAMILY_LEG_COUNT
+from test_per_atom_fields_edges import GPU_CASE_COUNT as PER_ATOM_EDGES_GPU_CASE_COUNT
 from test_two_cell_boxes import GPU_CASE_COUNT as TWO_CELL_GPU_CASE_COUNT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -105,6 +106,17 @@ def test_single_precision_analysis_regimes():
     out = _run(["tests/test_analysis_regimes.py"], None, "gpu", 900)
     passed = re.search(r"(\d+) passed", out)
     assert passed and int(passed.group(1)) == ANALYSIS_REGIMES_GPU_CASE_COUNT and "skipped" not in out and "failed" not in out, out[-1500:]
+
+
+@pytest.mark.gpu
+def test_single_precision_per_atom_fields_edges():
+    """tests/test_per_atom_fields_edges.py in the float build: per-atom stress, heat flux and strain on the 2-cell boxes, on a straining box driven from Python and where
+    the image of a reference separation decides, each under its module's float rule.  Its CPU tests show on the float checker first where the two image rules differ;
+    none skipped."""
+    _run(["tests/test_per_atom_fields_edges.py"], None, "not gpu", 900)
+    out = _run(["tests/test_per_atom_fields_edges.py"], None, "gpu", 900)
+    passed = re.search(r"(\d+) passed", out)
+    assert passed and int(passed.group(1)) == PER_ATOM_EDGES_GPU_CASE_COUNT and "skipped" not in out and "failed" not in out, out[-1500:]
 
 
 SPLINE_CASE = r"""
