@@ -181,6 +181,15 @@ def lib_host():
         lib.comdSetStrainRate.argtypes = [vp, c_double_p]
         lib.comdSetStrainRate.restype = ctypes.c_int
         lib.comdGetBox.argtypes = [vp, c_double_p]
+        lib.comdVirialFdotr.argtypes = [vp, c_double_p]
+        lib.comdPeriodicFacePairs.argtypes = [vp, c_int_p, ctypes.c_int]
+        lib.comdPeriodicFacePairs.restype = ctypes.c_int
+        lib.comdBerendsenScale.argtypes = [c_double_p, c_double_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, c_double_p]
+        lib.comdBerendsenScale.restype = ctypes.c_int
+        lib.comdSetBarostat.argtypes = [vp, ctypes.c_int, c_double_p, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        lib.comdSetBarostat.restype = ctypes.c_int
+        lib.comdGetBarostat.argtypes = [vp, c_double_p]
+        lib.comdGetBarostat.restype = ctypes.c_int
         lib.comdLocalBounds.argtypes = [vp, c_double_p]
         lib.comdSetLangevin.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_int]
         lib.comdSetLangevin.restype = ctypes.c_int
@@ -448,6 +457,64 @@ class Simulation:
             xx, yy, zz, yz, xz, xy = c
             return np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]], dtype=np.float64)
         return sym(out[0:6]), sym(out[6:12])
+
+    def virial_fdotr(self):
+        """(W, K) like virial(), from the forces of the last force evaluation: sum_i r_i F_i^T over the atoms minus the shift term of the pairs that cross
+        a periodic face (computeVirialFdotr; hip/fdotr_kernels.h has the identity).  What the barostat reads inside the step loop: a surface-sized share of
+        virial()'s pair walk.  Valid after step(), set_box() or any complete force evaluation; same tensor as virial() up to rounding."""
+        if self.host_only:
+            raise RuntimeError("virial_fdotr: a host-only simulation has no device state")
+        np = self._np
+        out = (ctypes.c_double * 13)()
+        self.lib.comdVirialFdotr(self.ptr, out)
+
+        def sym(c):
+            xx, yy, zz, yz, xz, xy = c
+            return np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]], dtype=np.float64)
+        return sym(out[0:6]), sym(out[6:12])
+
+    def periodic_face_pairs(self):
+        """int32 (n, 5): the work list of virial_fdotr()'s face kernel on this rank: (local cell, halo cell that holds periodic images, sign x, sign y, sign z),
+        the images stored at home position + sign_a L_a.  Built from the static neighbour table and the process grid; works on a host-only simulation."""
+        np = self._np
+        n = self.lib.comdPeriodicFacePairs(self.ptr, None, 0)
+        out = np.zeros((n, 5), dtype=np.int32)
+        if n:
+            self.lib.comdPeriodicFacePairs(self.ptr, out.ctypes.data_as(c_int_p), n)
+        return out
+
+    def set_barostat(self, pressure_gpa=0.0, tau_fs=1000.0, modulus_gpa=140.0, every=10, axes="xyz", iso=False, on=True):
+        """Berendsen barostat for the coming step() calls: after every `every`-th step (counted by the global step) the pressure of virial_fdotr() gives
+        mu_a = berendsen_scale(...) with dt_coupling = every * dt, and the next step's remap sets L_a mu_a on the axes of `axes` (a subset of "xyz").  The
+        target is a scalar or (x, y, z) in GPa, compressive positive; iso=True: one mu from the mean over the chosen axes.  on=False switches it off.  With
+        set_langevin() this is NPT.  ValueError, state unchanged, for what is refused: profile mode -s, an axis that also has a strain rate, every < 1, no
+        axis, tau <= 0, modulus <= 0, every * dt > tau, a non-finite value.  RuntimeError on a host-only simulation."""
+        if self.host_only:
+            raise RuntimeError("set_barostat: a host-only simulation has no integrator")
+        np = self._np
+        ax = str(axes)
+        mask = sum(1 << "xyz".index(c) for c in set(ax) if c in "xyz")
+        if not on:
+            self.lib.comdSetBarostat(self.ptr, 0, None, 0.0, 0.0, 0, 0, 0)
+            return
+        if len(set(ax)) != len(ax) or any(c not in "xyz" for c in ax) or not ax:
+            raise ValueError(f"set_barostat: axes must be a non-empty subset of 'xyz' (got {axes!r})")
+        t = np.asarray(pressure_gpa, dtype=np.float64)
+        if t.shape not in ((), (3,)):
+            raise ValueError(f"set_barostat: the pressure is a scalar or (x, y, z) in GPa (got {pressure_gpa!r})")
+        t = np.ascontiguousarray(np.broadcast_to(t, (3,)))
+        if self.lib.comdSetBarostat(self.ptr, 1, t.ctypes.data_as(c_double_p), float(tau_fs), float(modulus_gpa), int(every), mask, int(bool(iso))) != 0:
+            raise ValueError(f"set_barostat: refused (pressure {t.tolist()} GPa, tau {tau_fs} fs, modulus {modulus_gpa} GPa, every {every}, axes {axes!r}): "
+                             "profile mode, an axis with a strain rate, every < 1, tau <= 0, modulus <= 0, every * dt > tau or a non-finite value")
+
+    @property
+    def barostat(self):
+        """The barostat's settings: {"on", "pressure_gpa" (3,), "tau_fs", "modulus_gpa", "every", "axes", "iso"}."""
+        out = (ctypes.c_double * 8)()
+        on = self.lib.comdGetBarostat(self.ptr, out)
+        mask = int(out[6])
+        return {"on": bool(on), "pressure_gpa": self._np.array(out[0:3], dtype=self._np.float64), "tau_fs": out[3], "modulus_gpa": out[4],
+                "every": int(out[5]), "axes": "".join(c for a, c in enumerate("xyz") if mask >> a & 1), "iso": bool(int(out[7]))}
 
     def pressure_tensor(self):
         """(K + W) / V in eV/A^3, V the volume of the global domain (positive: compressive).  1 eV/A^3 = 160.21766208 GPa."""
@@ -767,7 +834,7 @@ class Simulation:
             raise ValueError(f"set_strain_rate: need three rates (x, y, z) in 1/ps (got {rates_per_ps!r})")
         r = np.ascontiguousarray(r)
         if self.lib.comdSetStrainRate(self.ptr, r.ctypes.data_as(c_double_p)) != 0:
-            raise ValueError(f"set_strain_rate: rates {r.tolist()} refused (not finite, or the simulation runs in profile mode -s)")
+            raise ValueError(f"set_strain_rate: rates {r.tolist()} refused (not finite, the simulation runs in profile mode -s, or an axis is under the barostat)")
 
     # --- dynamics (not in the reference: comd-hip --msd, --msdStart, --msdFile) ---
     def track_displacement(self, on=True):
@@ -882,6 +949,24 @@ def heat_flux_acf(j, window):
     if lib_host().comdHeatFluxAcf(j.ctypes.data_as(c_double_p), j.shape[0], int(window), out.ctypes.data_as(c_double_p)) != 0:
         raise ValueError("heat_flux_acf: comdHeatFluxAcf refused the series")
     return out
+
+
+def berendsen_scale(p, target, dt_coupling, tau, modulus, axes="xyz", iso=False):
+    """float64 (3,): the Berendsen scale factors mu_a = (1 - (dt_coupling / tau) (target_a - p_a) / modulus)^(1/3) on the axes of `axes`, 1 on the others;
+    iso=True: one mu from the means over the chosen axes (comdBerendsenScale of the host library; no device).  p and target are scalars or (x, y, z), positive
+    when compressive, in the unit of modulus.  ValueError for what the routine refuses: a non-finite argument, tau <= 0, modulus <= 0, dt_coupling > tau, no axis."""
+    import numpy as np
+    ax = str(axes)
+    if len(set(ax)) != len(ax) or any(c not in "xyz" for c in ax):
+        raise ValueError(f"berendsen_scale: axes must be a subset of 'xyz' (got {axes!r})")
+    mask = sum(1 << "xyz".index(c) for c in ax)
+    pp = np.ascontiguousarray(np.broadcast_to(np.asarray(p, dtype=np.float64), (3,)))
+    tt = np.ascontiguousarray(np.broadcast_to(np.asarray(target, dtype=np.float64), (3,)))
+    mu = np.ones(3, dtype=np.float64)
+    if lib_host().comdBerendsenScale(pp.ctypes.data_as(c_double_p), tt.ctypes.data_as(c_double_p), float(dt_coupling), float(tau), float(modulus), mask,
+                                     int(bool(iso)), mu.ctypes.data_as(c_double_p)) != 0:
+        raise ValueError(f"berendsen_scale: refused (p {pp.tolist()}, target {tt.tolist()}, dt {dt_coupling}, tau {tau}, modulus {modulus}, axes {axes!r})")
+    return mu
 
 
 def run_main(args):

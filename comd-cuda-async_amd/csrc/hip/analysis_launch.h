@@ -67,6 +67,56 @@ extern "C" void computeVirial(SimGpu* sim, real_t* out12)
    for (int c = 0; c < VIRIAL_N; ++c) out12[c] = (real_t)h[c];
 }
 
+// Not in the reference: the work list of the face kernel of computeVirialFdotr (fdotr_kernels.h).  Every id is checked here: the kernel trusts the rows
+extern "C" void comdSetFacePairsGpu(SimGpu* sim, const int* rows5, int nRows)
+{
+   for (int k = 0; k < nRows; ++k) {
+      const int* r = rows5 + 5 * (size_t)k;
+      const bool ok = r[0] >= 0 && r[0] < sim->boxes.nLocalBoxes && r[1] >= sim->boxes.nLocalBoxes && r[1] < sim->boxes.nTotalBoxes
+                      && r[2] >= -1 && r[2] <= 1 && r[3] >= -1 && r[3] <= 1 && r[4] >= -1 && r[4] <= 1;
+      if (!ok) { fprintf(stderr, "comdSetFacePairsGpu: row %d (%d, %d, %d, %d, %d) is out of range\n", k, r[0], r[1], r[2], r[3], r[4]); exit(-1); }
+   }
+   if (sim->fdotrRows) { HIP_CHECK(hipStreamSynchronize(S(sim->boundary_stream))); HIP_CHECK(hipFree(sim->fdotrRows)); }
+   sim->fdotrRows = dalloc<int>(5 * (size_t)(nRows > 0 ? nRows : 1), false);
+   if (nRows > 0) HIP_CHECK(hipMemcpy(sim->fdotrRows, rows5, 5 * (size_t)nRows * sizeof(int), hipMemcpyHostToDevice));
+   sim->fdotrNRows = nRows;
+}
+
+// Not in the reference: the pair virial from the forces on the device and the periodic face pairs (fdotr_kernels.h), one face-kernel instance per pair function
+extern "C" void computeVirialFdotr(SimGpu* sim, const double box[3], real_t* out12)
+{
+   hipStream_t st = analysisStream(sim);
+   if (!sim->fdotrRows) { fprintf(stderr, "computeVirialFdotr: no work list (comdSetFacePairsGpu)\n"); exit(-1); }
+   const dim3 atomsGrid = integratorGrid(sim);
+   const int nPartial = (int)atomsGrid.x + FDOTR_FACE_BLOCKS;
+   if (!sim->fdotrBuf) sim->fdotrBuf = dalloc<double>((size_t)(nPartial + 1) * VIRIAL_N, false);
+   double* out = sim->fdotrBuf + (size_t)nPartial * VIRIAL_N;
+   FdotrAtomsArgs a;
+   a.rx = sim->atoms.r.x; a.ry = sim->atoms.r.y; a.rz = sim->atoms.r.z;
+   a.fx = sim->atoms.f.x; a.fy = sim->atoms.f.y; a.fz = sim->atoms.f.z;
+   a.px = sim->atoms.p.x; a.py = sim->atoms.p.y; a.pz = sim->atoms.p.z;
+   a.iSpecies = sim->atoms.iSpecies; a.speciesMass = sim->species_mass; a.nAtoms = sim->boxes.nAtoms;
+   a.nLocalBoxes = sim->boxes.nLocalBoxes; a.cap = sim->maxAtoms; a.laneBits = integratorLaneBits(sim);
+   a.cx = (real_t)(0.5 * box[0]); a.cy = (real_t)(0.5 * box[1]); a.cz = (real_t)(0.5 * box[2]);
+   a.partial = sim->fdotrBuf;
+   hipLaunchKernelGGL(Fdotr_atoms, atomsGrid, dim3(256), 0, st, a);
+   FdotrFaceArgs v;
+   v.rx = sim->atoms.r.x; v.ry = sim->atoms.r.y; v.rz = sim->atoms.r.z;
+   v.nAtoms = sim->boxes.nAtoms; v.rows = sim->fdotrRows; v.nRows = sim->fdotrNRows; v.cap = sim->maxAtoms;
+   v.lx = (real_t)box[0]; v.ly = (real_t)box[1]; v.lz = (real_t)box[2];
+   v.partial = sim->fdotrBuf + (size_t)atomsGrid.x * VIRIAL_N;
+   withPairFunction(sim, [&](auto p, real_t rc2) {
+      v.rc2 = rc2;
+      hipLaunchKernelGGL(Fdotr_face<decltype(p)>, dim3(FDOTR_FACE_BLOCKS), dim3(256), 0, st, v, p);
+   });
+   hipLaunchKernelGGL(Virial_Final, dim3(1), dim3(256), 0, st, sim->fdotrBuf, nPartial, out);
+   LAUNCH_CHECK();
+   double h[VIRIAL_N];
+   HIP_CHECK(hipMemcpyAsync(h, out, sizeof h, hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+   for (int c = 0; c < VIRIAL_N; ++c) out12[c] = (real_t)h[c];
+}
+
 // Not in the reference: the pair-distance histogram (rdf_kernels.h).  One instance for every potential and method: it reads positions and cells only
 extern "C" void computePairHistogram(SimGpu* sim, int nBins, real_t rMax, uint64_t* outCounts)
 {

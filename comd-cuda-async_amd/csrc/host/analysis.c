@@ -15,6 +15,26 @@ void computePressure(SimFlat* s)
    s->V = s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2];
 }
 
+/* the fast pressure (comd_host.h): this rank's share from computeVirialFdotr on the box of now, summed over the ranks.  The work list is built and uploaded once */
+void comdVirialFdotr(SimFlat* s, double out[13])
+{
+   if (!s->facePairs) {
+      s->nFacePairs = comdPeriodicFacePairs(s, NULL, 0);
+      s->facePairs = (int*)malloc(5 * (size_t)(s->nFacePairs > 0 ? s->nFacePairs : 1) * sizeof(int));
+      comdPeriodicFacePairs(s, s->facePairs, s->nFacePairs);
+      comdSetFacePairsGpu(&s->gpu, s->facePairs, s->nFacePairs);
+   }
+   double box[3];
+   real_t local[12], sum[12];
+   for (int a = 0; a < 3; ++a) box[a] = (double)s->domain->globalExtent[a];
+   computeVirialFdotr(&s->gpu, box, local);
+   startTimer(commReduceTimer);
+   addRealParallel(local, sum, 12);
+   stopTimer(commReduceTimer);
+   for (int c = 0; c < 12; ++c) out[c] = (double)sum[c];
+   out[12] = box[0] * box[1] * box[2];
+}
+
 int comdPairHistogram(SimFlat* s, int nBins, double rMax, double* outCounts)
 {
    const double cutoff = s->pot->cutoff;

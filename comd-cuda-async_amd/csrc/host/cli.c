@@ -17,6 +17,8 @@
  * NonFCC column, PATH gets the four counts per sample and the dump the non-FCC atoms of the last step as extended XYZ),
  * --erateX R, --erateY R, --erateZ R, --deformStart S, --deformFile PATH (box deformation: engineering strain rates in 1/ps applied from global step S on, the
  * positions remapped affinely at the top of every step; V/V0 and Sxx(GPa) columns, PATH gets strain, box and stress tensor per sample; the reference's box is fixed),
+ * --baro, --baroP GPA, --baroTau FS, --baroModulus GPA, --baroEvery N, --baroAxes xyz, --baroIso, --baroStart S, --baroFile PATH (Berendsen barostat: every N steps the
+ *   pressure from the forces of the step scales the chosen axes towards the target),
  * --stress, --stressFile PATH, --stressDump PATH, --stressDumpMin X (per-atom virial stress: hydrostatic pressure and von Mises stress of every atom with the
  * uniform atomic volume V/N, reduced on the device at every printed step; a MaxVM(GPa) column, PATH gets a line per sample and the dump the tensors of the atoms
  * of the last step whose von Mises stress is at least X GPa as extended XYZ; the reference has no stress output),
@@ -69,6 +71,9 @@ Command parseCommandLine(int argc, char** argv)
    cmd.strainThreshold = 0.1;
    strcpy(cmd.hfFile, "heatflux.dat");
    strcpy(cmd.hfAcfFile, "hfacf.dat");
+   cmd.baroTau = 1000.0; cmd.baroModulus = 140.0; cmd.baroEvery = 10;
+   strcpy(cmd.baroAxes, "xyz");
+   strcpy(cmd.baroFile, "baro.dat");
    int help = 0;
 
    const ArgDef defs[] = {
@@ -142,6 +147,15 @@ Command parseCommandLine(int argc, char** argv)
       { "hfWindow",      0,  1, 'i', &cmd.hfWindow,       0, "lags of the heat-flux autocorrelation (default 0: half the samples; clipped to the samples)" },
       { "hfFile",        0,  1, 's', cmd.hfFile, sizeof cmd.hfFile, "file the flux samples are written to (default heatflux.dat)" },
       { "hfAcfFile",     0,  1, 's', cmd.hfAcfFile, sizeof cmd.hfAcfFile, "file the autocorrelation and the running conductivity are written to (default hfacf.dat)" },
+      { "baro",          0,  0, 'i', &cmd.baro,           0, "Berendsen barostat on a per-step pressure from the forces and the periodic face pairs (Pressure(GPa) and V/V0 columns; with --langevin: NPT)" },
+      { "baroP",         0,  1, 'd', &cmd.baroP,          0, "barostat target pressure in GPa, compressive positive (default 0)" },
+      { "baroTau",       0,  1, 'd', &cmd.baroTau,        0, "barostat coupling time in fs (default 1000)" },
+      { "baroModulus",   0,  1, 'd', &cmd.baroModulus,    0, "bulk modulus the barostat assumes, in GPa (default 140)" },
+      { "baroEvery",     0,  1, 'i', &cmd.baroEvery,      0, "steps between couplings (default 10)" },
+      { "baroAxes",      0,  1, 's', cmd.baroAxes, sizeof cmd.baroAxes, "axes the barostat scales, a subset of xyz (default xyz; an axis with an --erate is not allowed)" },
+      { "baroIso",       0,  0, 'i', &cmd.baroIso,        0, "one scale factor from the mean pressure of the chosen axes" },
+      { "baroStart",     0,  1, 'i', &cmd.baroStart,      0, "global step coupling begins at (default 0)" },
+      { "baroFile",      0,  1, 's', cmd.baroFile, sizeof cmd.baroFile, "file the couplings are written to (default baro.dat)" },
    };
    const int nDefs = (int)(sizeof defs / sizeof defs[0]);
 
@@ -228,6 +242,9 @@ void printCmdYaml(FILE* file, Command* cmd)
    if (cmd->msd) fprintf(file, "  MSD from step: %d\n  MSD file: %s\n", cmd->msdStart, cmd->msdFile);
    if (cmd->erate[0] != 0.0 || cmd->erate[1] != 0.0 || cmd->erate[2] != 0.0)
       fprintf(file, "  Strain rates: [ %g, %g, %g ] 1/ps\n  Deform from step: %d\n  Deform file: %s\n", cmd->erate[0], cmd->erate[1], cmd->erate[2], cmd->deformStart, cmd->deformFile);
+   if (cmd->baro)
+      fprintf(file, "  Barostat: 1\n  Barostat target: %g GPa\n  Barostat tau: %g fs\n  Barostat modulus: %g GPa\n  Barostat every: %d steps\n  Barostat axes: %s%s\n  Barostat from step: %d\n"
+                    "  Barostat file: %s\n", cmd->baroP, cmd->baroTau, cmd->baroModulus, cmd->baroEvery, cmd->baroAxes, cmd->baroIso ? " (iso)" : "", cmd->baroStart, cmd->baroFile);
    fprintf(file, "\n");
    fflush(file);
 }

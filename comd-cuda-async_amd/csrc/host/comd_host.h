@@ -83,6 +83,15 @@ typedef struct CommandSt {
    int hfWindow;          /* extension: lags of the autocorrelation; 0 = half the samples; more than the samples is clipped */
    char hfFile[1024];     /* extension: where the print rank writes the flux samples (default heatflux.dat) */
    char hfAcfFile[1024];  /* extension: where it writes the autocorrelation and the running conductivity (default hfacf.dat) */
+   int baro;              /* extension: Berendsen barostat on the pressure of comdVirialFdotr; the reference's box is fixed */
+   double baroP;          /* extension: its target pressure in GPa, compressive positive (default 0) */
+   double baroTau;        /* extension: its coupling time in fs (default 1000) */
+   double baroModulus;    /* extension: the bulk modulus the scale rule assumes, in GPa (default 140) */
+   int baroEvery;         /* extension: steps between couplings (default 10) */
+   char baroAxes[16];     /* extension: the axes it scales, a subset of xyz (default xyz) */
+   int baroIso;           /* extension: one scale factor from the mean pressure of the chosen axes */
+   int baroStart;         /* extension: the global step coupling begins at (default 0) */
+   char baroFile[1024];   /* extension: where the print rank writes the couplings (default baro.dat) */
 } Command;
 
 #define COMD_LANGEVIN_SEED 0x436f4d44ull     /* "CoMD" */
@@ -395,6 +404,20 @@ typedef struct SimFlatSt {
    double* hfRows;                  /* [hfSamples][13]: step, time (fs), the nine sums of comdHeatFlux (eV A/fs), temperature (K), volume (A^3) */
    int hfSamples, hfCap;
    double hfJxNow;                  /* the Jx column of printThings: the x component of the flux density of the last sample in eV/A^2/fs, 0 before hfStart */
+   /* Berendsen barostat (--baro, comdSetBarostat): every baroEvery steps the step ends unfused, the pressure of comdVirialFdotr gives mu, and the next step's remap
+    * sets the box the coupling asked for */
+   int baro;                        /* on: timestep() couples */
+   double baroTarget[3];            /* GPa, compressive positive */
+   double baroTau, baroModulus;     /* fs, GPa */
+   int baroEvery, baroAxes, baroIso, baroStart;      /* axes: bit a = axis a is scaled */
+   int baroPending;                 /* a coupling has set baroNext: the remap of the coming step applies it */
+   double baroNext[3];              /* the extents that remap will set on the barostat's axes */
+   int baroReport;                  /* comdMain: the Pressure(GPa) and V/V0 columns, the file and the YAML block */
+   char baroFile[1024];
+   double* baroRows;                /* [baroSamples][12]: step, time (fs), p xx yy zz (GPa), mu x y z, L x y z (A), V (A^3) -- the box after the coupling */
+   int baroSamples, baroCap;
+   int* facePairs;                  /* comdVirialFdotr: the rows of comdPeriodicFacePairs, built at its first call */
+   int nFacePairs;
 } SimFlat;
 
 SimFlat* initSimulation(Command cmd);
@@ -497,20 +520,41 @@ int comdStrainSummary(SimFlat* s, double rCut, double threshold, double* out9);
  * comdDeformTo: comdSetBox, then a redistribution (with lists: a list build), a force evaluation and an energy read, so that the energy, the virial, the gathered
  *    arrays and the analyses are those of the new state.  -1 as comdSetBox.
  * comdSetStrainRate: engineering strain rates in 1/ps for the coming timestep() calls, from the current box on; all zero = off, and timestep() is then what it was
- *    without the feature, bit for bit.  -1, nothing changed, for a rate that is not finite or with -s (no redistribution there).
+ *    without the feature, bit for bit.  -1, nothing changed, for a rate that is not finite, with -s (no redistribution there) or on an axis the barostat scales.
  * comdGetBox: out[0..2] the current global extents, out[3..5] those at creation.  comdLocalBounds: out[0..2] this rank's localMin, out[3..5] its localMax. */
 int  comdSetBox(SimFlat* s, const double L[3]);
 int  comdDeformTo(SimFlat* s, const double L[3]);
 int  comdSetStrainRate(SimFlat* s, const double ratesPerPs[3]);
 void comdGetBox(SimFlat* s, double out[6]);
 void comdLocalBounds(SimFlat* s, double out[6]);
+/* not in the reference: pressure coupling.
+ * comdPeriodicFacePairs: the work list of computeVirialFdotr (comd_hip.h) from the static neighbour table and the process grid: rows of 5 ints (local cell, halo cell
+ *    that holds periodic images, sign x, sign y, sign z; the images sit at home position + sign_a L_a).  Returns the number of rows and writes the first `cap` of them
+ *    to out5 (NULL: count only).  Needs no device: it works on a host-only simulation.
+ * comdVirialFdotr: comdVirial's twin on the forces of the last force evaluation, {W[6], K[6], V} summed over the ranks; collective; valid after timestep(),
+ *    computeForce() or comdDeformTo().  It does not touch the W, K, V that computePressure keeps.
+ * comdBerendsenScale: the scale rule, plain C, no device.  mu_a = (1 - (dtCoupling / tau) (target_a - p_a) / modulus)^(1/3) on the axes of axesMask (bit a), 1 on the
+ *    others; iso != 0: one mu from the means of p and target over the chosen axes.  p positive when compressive, p_a = (K_aa + W_aa) / V, in the units of target and
+ *    modulus; dtCoupling and tau in the same unit of time.  -1 and mu untouched for a non-finite argument, tau <= 0, modulus <= 0, dtCoupling > tau, dtCoupling < 0, an
+ *    empty or out-of-range mask or a mu that would not be positive.
+ * comdSetBarostat: the barostat for the coming timestep() calls: every `every` steps (those after which stepCount - baroStart is a positive multiple of every) the
+ *    step ends unfused, comdVirialFdotr gives p, comdBerendsenScale with dtCoupling = every * dt gives mu, and the remap at the top of the next step sets L_a mu_a on
+ *    the chosen axes through comdSetBox.  on == 0: off, timestep() is what it was.  -1 and nothing changed with -s, without device state, for an axis that also has a
+ *    non-zero strain rate, every < 1, an empty mask, or what comdBerendsenScale refuses (dtCoupling is checked at timestep(), which knows dt).
+ * comdGetBarostat: returns on/off; out8 = {target x y z (GPa), tau (fs), modulus (GPa), every, axesMask, iso}. */
+int  comdPeriodicFacePairs(SimFlat* s, int* out5, int cap);
+void comdVirialFdotr(SimFlat* s, double out[13]);
+int  comdBerendsenScale(const double p[3], const double target[3], double dtCoupling, double tau, double modulus, int axesMask, int iso, double mu[3]);
+int  comdSetBarostat(SimFlat* s, int on, const double targetGPa[3], double tauFs, double modulusGPa, int every, int axesMask, int iso);
+int  comdGetBarostat(SimFlat* s, double out8[8]);
+int  comdBarostatRefusal(const SimFlat* s, const double targetGPa[3], double tauFs, double modulusGPa, int every, int axesMask);      /* why comdSetBarostat would refuse, 0 = it would not */
 void deformListBudget(SimFlat* s);      /* *_nl: the skin left to the displacement test by the compression since the build; after a box change and after a list build */
 void redistributeAtoms(SimFlat* sim);
 void ensureInteriorForceLaunched(SimFlat* sim);
 
 /* ---- performanceTimers.h ---- */
 enum TimerHandle { totalTimer, loopTimer, timestepTimer, positionTimer, velocityTimer, redistributeTimer, atomHaloTimer,
-                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, cspTimer, cnaTimer, deformTimer, stressTimer, strainTimer, heatfluxTimer, numberOfTimers };
+                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, cspTimer, cnaTimer, deformTimer, stressTimer, strainTimer, heatfluxTimer, baroTimer, numberOfTimers };
 void profileStart(enum TimerHandle handle);
 void profileStop(enum TimerHandle handle);
 double getElapsedTime(enum TimerHandle handle);

@@ -108,6 +108,36 @@ int getNeighborBoxes(LinkCell* boxes, int iBox, int* nbrBoxes)
    return count;
 }
 
+/* The work list of computeVirialFdotr (not in the reference; comd_host.h): every (local cell, stencil cell) whose stencil cell is a halo cell filled with periodic
+ * images, with the sign of the shift its atoms carry per axis -- -1 below the grid on a rank at the lower edge of the process grid, +1 above it on a rank at the
+ * upper edge, 0 where the halo cell belongs to a neighbouring rank without a wrap.  In the order of the cell ids and of getNeighborBoxes. */
+int comdPeriodicFacePairs(SimFlat* s, int* out5, int cap)
+{
+   LinkCell* ll = s->boxes; const Domain* dd = s->domain;
+   int count = 0;
+   for (int iBox = 0; iBox < ll->nLocalBoxes; ++iBox) {
+      int t[3];
+      comdTupleFromBox(&ll->geom, iBox, &t[0], &t[1], &t[2]);
+      for (int i = t[0] - 1; i <= t[0] + 1; i++)
+         for (int j = t[1] - 1; j <= t[1] + 1; j++)
+            for (int k = t[2] - 1; k <= t[2] + 1; k++) {
+               const int c[3] = { i, j, k };
+               int sign[3], any = 0;
+               for (int a = 0; a < 3; ++a) {
+                  sign[a] = c[a] == -1 && dd->procCoord[a] == 0 ? -1 : c[a] == ll->gridSize[a] && dd->procCoord[a] == dd->procGrid[a] - 1 ? 1 : 0;
+                  any |= sign[a];
+               }
+               if (!any) continue;
+               if (out5 && count < cap) {
+                  int* row = out5 + 5 * (size_t)count;
+                  row[0] = iBox; row[1] = getBoxFromTuple(ll, i, j, k); row[2] = sign[0]; row[3] = sign[1]; row[4] = sign[2];
+               }
+               count++;
+            }
+   }
+   return count;
+}
+
 int maxOccupancy(LinkCell* boxes)
 {
    int localMax = 0, globalMax;

@@ -208,6 +208,26 @@ SimFlat* initSimulationHost(Command cmd)
    for (int a = 0; a < 3; ++a) sim->erate[a] = cmd.erate[a];
    sim->deformStart = cmd.deformStart; sim->deformReport = sim->deform;
    strcpy(sim->deformFile, cmd.deformFile);
+   /* --baro (not in the reference): the settings are checked here, before any step, by the rules of comdSetBarostat */
+   if (cmd.baro) {
+      int mask = 0, bad = cmd.baroAxes[0] == '\0';
+      for (const char* c = cmd.baroAxes; *c; ++c) { if (*c < 'x' || *c > 'z' || (mask >> (*c - 'x') & 1)) bad = 1; else mask |= 1 << (*c - 'x'); }
+      if (bad) { printf("Error: --baroAxes must be a non-empty subset of xyz without repeats (got '%s').\n", cmd.baroAxes); exit(-1); }
+      if (cmd.baroStart < 0) { printf("Error: --baroStart must be >= 0 (got %d).\n", cmd.baroStart); exit(-1); }
+      const double target[3] = { cmd.baroP, cmd.baroP, cmd.baroP };
+      switch (comdBarostatRefusal(sim, target, cmd.baroTau, cmd.baroModulus, cmd.baroEvery, mask)) {
+         case 0: break;
+         case 1: printf("Error: --baro cannot be combined with -s (profile mode does not redistribute the atoms).\n"); exit(-1);
+         case 2: printf("Error: --baroAxes %s names an axis that also has a non-zero --erate: an axis is strained or pressure-coupled, not both.\n", cmd.baroAxes); exit(-1);
+         case 3: printf("Error: --baroEvery must be >= 1 (got %d).\n", cmd.baroEvery); exit(-1);
+         default: printf("Error: the barostat needs a finite --baroP, --baroTau > 0 fs, --baroModulus > 0 GPa and --baroEvery * dt <= --baroTau (got %g GPa, %g fs, %g GPa, %d * %g fs).\n",
+                         cmd.baroP, cmd.baroTau, cmd.baroModulus, cmd.baroEvery, cmd.dt); exit(-1);
+      }
+      for (int a = 0; a < 3; ++a) sim->baroTarget[a] = cmd.baroP;
+      sim->baroTau = cmd.baroTau; sim->baroModulus = cmd.baroModulus; sim->baroEvery = cmd.baroEvery; sim->baroAxes = mask; sim->baroIso = cmd.baroIso != 0;
+      sim->baroStart = cmd.baroStart; sim->baro = sim->baroReport = 1;
+      strcpy(sim->baroFile, cmd.baroFile);
+   }
    sanityChecks(cmd, sim->pot->cutoff, latticeConstant, sim->pot->latticeType);
    sim->species = initSpecies(sim->pot);
 
@@ -314,6 +334,7 @@ void destroySimulation(SimFlat** ps)
    free(s->cspRows); free(s->cspLast); free(s->analysisStage);
    free(s->cnaRows); free(s->cnaLast);
    free(s->deformRows);
+   free(s->baroRows); free(s->facePairs);
    free(s->stressRows);
    free(s->strainRows);
    free(s->hfRows);
@@ -340,9 +361,9 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
       s->firstPrint = 0;
       fprintf(screenOut,
               "#                                                                                         Performance\n"
-              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms%s%s%s%s%s%s%s%s\n",
-              s->pressure ? "    Pressure(GPa)" : "", s->msd ? "         MSD(A^2)" : "", s->csp ? "      Defects" : "", s->cna ? "       NonFCC" : "",
-              s->deformReport ? "           V/V0         Sxx(GPa)" : "", s->stress ? "       MaxVM(GPa)" : "",
+              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms%s%s%s%s%s%s%s%s%s\n",
+              s->pressure || s->baroReport ? "    Pressure(GPa)" : "", s->msd ? "         MSD(A^2)" : "", s->csp ? "      Defects" : "", s->cna ? "       NonFCC" : "",
+              s->deformReport ? "           V/V0         Sxx(GPa)" : "", s->baroReport && !s->deformReport ? "           V/V0" : "", s->stress ? "       MaxVM(GPa)" : "",
               s->strain ? "         MaxShear" : "", s->heatflux ? "       Jx(eV/A^2/fs)" : "");
       fflush(screenOut);
    }
@@ -354,11 +375,12 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
    double timePerAtom = 1.0e6 * elapsedTime / (double)(nEval * s->atoms->nLocal);
    fprintf(screenOut, " %6d %10.2f %18.12f %18.12f %18.12f %12.4f %10.4f %12d",
            iStep, time, eTotal, eU, eK, Temp, timePerAtom, s->atoms->nGlobal);
-   if (s->pressure) fprintf(screenOut, " %16.10f", pressureOf(s) * eVperA3inGPa);
+   if (s->pressure || s->baroReport) fprintf(screenOut, " %16.10f", pressureOf(s) * eVperA3inGPa);
    if (s->msd) fprintf(screenOut, " %16.10e", s->msdNow);
    if (s->csp) fprintf(screenOut, " %12d", s->cspDefectsNow);
    if (s->cna) fprintf(screenOut, " %12lld", s->cnaNonFccNow);
    if (s->deformReport) fprintf(screenOut, " %14.10f %16.10f", (double)s->V / (s->box0[0] * s->box0[1] * s->box0[2]), -((double)s->K[0] + s->W[0]) / s->V * eVperA3inGPa);
+   if (s->baroReport && !s->deformReport) fprintf(screenOut, " %14.10f", (double)s->V / (s->box0[0] * s->box0[1] * s->box0[2]));
    if (s->stress) fprintf(screenOut, " %16.10f", s->stressMaxVmNow * eVperA3inGPa);
    if (s->strain) fprintf(screenOut, " %16.10f", s->strainMaxShearNow);
    if (s->heatflux) fprintf(screenOut, " %19.10e", s->hfJxNow);
@@ -670,6 +692,43 @@ static void writeDeform(FILE* yaml, SimFlat* s)
    fprintf(yaml, "  finalBox: [ %.12e, %.12e, %.12e ]\n", (double)L[0], (double)L[1], (double)L[2]);
    fprintf(yaml, "  file: %s\n", s->deformFile);
    fprintf(yaml, "  samples: %d\n", samples);
+   fprintf(yaml, "\n");
+   fflush(yaml);
+}
+
+/* --baro: the file: a header with the settings, then the rows timestep() has kept, one per coupling.  The YAML block gives the settings, the couplings, the final
+ * box and the mean of the fast pressure over the last half of the couplings. */
+static void writeBaro(FILE* yaml, SimFlat* s)
+{
+   if (!printRank()) return;
+   const int n = s->baroSamples;
+   char axes[4] = "", *c = axes;
+   for (int a = 0; a < 3; ++a) if (s->baroAxes >> a & 1) *c++ = (char)('x' + a);
+   *c = '\0';
+   FILE* f = fopen(s->baroFile, "w");
+   if (!f) { printf("Error: cannot write %s\n", s->baroFile); exit(-1); }
+   fprintf(f, "# Barostat: N %d target(GPa) %.17g tau(fs) %.17g modulus(GPa) %.17g every %d axes %s iso %d startStep %d couplings %d | columns: step, time (fs), "
+              "p xx yy zz (GPa, compressive positive, from the forces and the face pairs), mu x y z, L x y z (A) and V (A^3) the coupling asked for\n",
+           s->atoms->nGlobal, s->baroTarget[0], s->baroTau, s->baroModulus, s->baroEvery, axes, s->baroIso, s->baroStart, n);
+   for (int k = 0; k < n; ++k) {
+      const double* r = s->baroRows + 12 * (size_t)k;
+      fprintf(f, "%.0f %.17g", r[0], r[1]);
+      for (int i = 2; i < 12; ++i) fprintf(f, " %.17g", r[i]);
+      fprintf(f, "\n");
+   }
+   fclose(f);
+   if (!yaml) return;
+   double mean[3] = { 0.0, 0.0, 0.0 };
+   const int from = n / 2;
+   for (int k = from; k < n; ++k) for (int a = 0; a < 3; ++a) mean[a] += s->baroRows[12 * (size_t)k + 2 + a] / (double)(n - from);
+   const real_t* L = s->domain->globalExtent;
+   fprintf(yaml, "Barostat:\n");
+   fprintf(yaml, "  target: %.12e\n  pressureUnits: GPa\n  tau: %.12e\n  modulus: %.12e\n  every: %d\n  axes: %s\n  iso: %d\n  startStep: %d\n",
+           s->baroTarget[0], s->baroTau, s->baroModulus, s->baroEvery, axes, s->baroIso, s->baroStart);
+   fprintf(yaml, "  couplings: %d\n", n);
+   fprintf(yaml, "  finalBox: [ %.12e, %.12e, %.12e ]\n", (double)L[0], (double)L[1], (double)L[2]);
+   fprintf(yaml, "  meanPressureLastHalf: [ %.12e, %.12e, %.12e ]\n", mean[0], mean[1], mean[2]);
+   fprintf(yaml, "  file: %s\n", s->baroFile);
    fprintf(yaml, "\n");
    fflush(yaml);
 }
@@ -1010,7 +1069,7 @@ int comdMain(int argc, char** argv)
       startTimer(commReduceTimer);
       sumAtoms(sim);
       stopTimer(commReduceTimer);
-      if (sim->pressure || sim->deformReport) { startTimer(pressureTimer); computePressure(sim); stopTimer(pressureTimer); }
+      if (sim->pressure || sim->deformReport || sim->baroReport) { startTimer(pressureTimer); computePressure(sim); stopTimer(pressureTimer); }
       if (sim->deformReport) sampleDeform(sim, iStep);
       if (sim->rdfBins) { startTimer(rdfTimer); sampleRdf(sim); stopTimer(rdfTimer); }
       if (sim->msd && iStep >= sim->msdStart) { startTimer(msdTimer); if (iStep == sim->msdStart) startMsd(sim); sampleMsd(sim, iStep); stopTimer(msdTimer); }
@@ -1039,7 +1098,7 @@ int comdMain(int argc, char** argv)
    }
    profileStop(loopTimer);
    sumAtoms(sim);
-   if (sim->pressure || sim->deformReport) { startTimer(pressureTimer); computePressure(sim); stopTimer(pressureTimer); }
+   if (sim->pressure || sim->deformReport || sim->baroReport) { startTimer(pressureTimer); computePressure(sim); stopTimer(pressureTimer); }
    if (sim->deformReport) sampleDeform(sim, iStep);
    if (sim->rdfBins) { startTimer(rdfTimer); sampleRdf(sim); stopTimer(rdfTimer); }
    if (sim->msd && iStep >= sim->msdStart) { startTimer(msdTimer); if (iStep == sim->msdStart) startMsd(sim); sampleMsd(sim, iStep); stopTimer(msdTimer); }
@@ -1056,6 +1115,7 @@ int comdMain(int argc, char** argv)
    if (sim->csp) writeCsp(yamlFile, sim);
    if (sim->cna) writeCna(yamlFile, sim);
    if (sim->deformReport) writeDeform(yamlFile, sim);
+   if (sim->baroReport) writeBaro(yamlFile, sim);
    if (sim->stress) { startTimer(stressTimer); writeStress(yamlFile, sim, iStep); stopTimer(stressTimer); }
    if (sim->strain) { startTimer(strainTimer); writeStrain(yamlFile, sim, iStep); stopTimer(strainTimer); }
    if (sim->heatflux) { startTimer(heatfluxTimer); writeHeatFlux(yamlFile, sim); stopTimer(heatfluxTimer); }

@@ -29,13 +29,22 @@ static void extentsAt(const SimFlat* s, double t, double L[3])
    for (int a = 0; a < 3; ++a) L[a] = s->box0[a] * (1.0 + (s->deformEpsBase[a] + s->erate[a] * t / 1000.0));
 }
 
-/* One step's strain: the box is set from box0 and the strained time, never by multiplying up, so it is a pure function of the steps taken; the kernel gets
- * L_new / L_old.  A box the grid cannot follow ends the run here, before anything is launched. */
-static void deformStep(SimFlat* s, real_t dt)
+/* One step's box: the strained axes are set from box0 and the strained time, never by multiplying up, so they are a pure function of the steps taken; the barostat's
+ * axes take what the last coupling asked for; the kernel gets L_new / L_old.  With the barostat on, an axis without a rate keeps its extent (or takes the barostat's);
+ * without it every axis goes through extentsAt, as before the barostat existed.  A box the grid cannot follow ends the run here, before anything is launched. */
+static void deformStep(SimFlat* s, real_t dt, int strain)
 {
-   double L[3];
-   s->deformTime += (double)dt;
-   extentsAt(s, s->deformTime, L);
+   double L[3], E[3];
+   for (int a = 0; a < 3; ++a) L[a] = (double)s->domain->globalExtent[a];
+   if (strain) {
+      s->deformTime += (double)dt;
+      extentsAt(s, s->deformTime, E);
+      for (int a = 0; a < 3; ++a) if (!s->baro || s->erate[a] != 0.0) L[a] = E[a];
+   }
+   if (s->baroPending) {
+      for (int a = 0; a < 3; ++a) if (s->baroAxes >> a & 1) L[a] = s->baroNext[a];
+      s->baroPending = 0;
+   }
    if (comdSetBox(s, L) != 0) {
       if (printRank())
          printf("Error: at step %llu the box [ %g, %g, %g ] would make a link cell narrower than the %g Angstroms the grid was built for (or is not positive); "
@@ -43,8 +52,108 @@ static void deformStep(SimFlat* s, real_t dt)
       fflush(stdout);
       exit(-1);
    }
-   extentsAt(s, s->deformTime + (double)dt, s->nextExtent);
+   if (strain) {
+      extentsAt(s, s->deformTime + (double)dt, E);
+      for (int a = 0; a < 3; ++a) if (!s->baro || s->erate[a] != 0.0) s->nextExtent[a] = E[a];
+   }
    deformListBudget(s);
+}
+
+/* ---- Berendsen barostat (not in the reference; comd_host.h) ---- */
+/* the cube root of x > 0 to well within an ulp: the library's (which may be 2 ulp off) and one Newton step whose residual y^3 - x is formed with the exact error of y * y */
+static double cbrtRefined(double x)
+{
+   const double y = cbrt(x), y2 = y * y, e2 = fma(y, y, -y2);
+   const double residual = fma(y2, y, -x) + e2 * y;
+   return y - residual / (3.0 * y2);
+}
+
+int comdBerendsenScale(const double p[3], const double target[3], double dtCoupling, double tau, double modulus, int axesMask, int iso, double mu[3])
+{
+   for (int a = 0; a < 3; ++a) if (!isfinite(p[a]) || !isfinite(target[a])) return -1;
+   if (!isfinite(dtCoupling) || !isfinite(tau) || !isfinite(modulus)) return -1;
+   if (!(tau > 0.0) || !(modulus > 0.0) || dtCoupling > tau || dtCoupling < 0.0 || axesMask < 1 || axesMask > 7) return -1;
+   double m[3] = { 1.0, 1.0, 1.0 };
+   if (iso) {
+      double pm = 0.0, tm = 0.0; int n = 0;
+      for (int a = 0; a < 3; ++a) if (axesMask >> a & 1) { pm += p[a]; tm += target[a]; n++; }
+      pm /= n; tm /= n;
+      const double x = 1.0 - (dtCoupling / tau) * (tm - pm) / modulus;
+      if (!(x > 0.0)) return -1;
+      for (int a = 0; a < 3; ++a) if (axesMask >> a & 1) m[a] = cbrtRefined(x);
+   } else {
+      for (int a = 0; a < 3; ++a) if (axesMask >> a & 1) {
+         const double x = 1.0 - (dtCoupling / tau) * (target[a] - p[a]) / modulus;
+         if (!(x > 0.0)) return -1;
+         m[a] = cbrtRefined(x);
+      }
+   }
+   for (int a = 0; a < 3; ++a) mu[a] = m[a];
+   return 0;
+}
+
+/* why a setting is refused: 0 fine, 1 profile mode, 2 an axis that also strains, 3 every, 4 the mask, 5 the scale rule's own refusals */
+int comdBarostatRefusal(const SimFlat* s, const double targetGPa[3], double tauFs, double modulusGPa, int every, int axesMask)
+{
+   double mu[3];
+   if (s->gpuProfile) return 1;
+   if (axesMask < 1 || axesMask > 7) return 4;
+   for (int a = 0; a < 3; ++a) if ((axesMask >> a & 1) && s->erate[a] != 0.0) return 2;
+   if (every < 1) return 3;
+   if (comdBerendsenScale(targetGPa, targetGPa, (double)every * s->dt, tauFs, modulusGPa, axesMask, 0, mu) != 0) return 5;
+   return 0;
+}
+
+int comdSetBarostat(SimFlat* s, int on, const double targetGPa[3], double tauFs, double modulusGPa, int every, int axesMask, int iso)
+{
+   if (!on) {
+      /* a coupling whose box has not been set yet is dropped with the barostat */
+      if (s->baroPending) for (int a = 0; a < 3; ++a) if (s->baroAxes >> a & 1) s->nextExtent[a] = (double)s->domain->globalExtent[a];
+      s->baro = 0; s->baroPending = 0;
+      return 0;
+   }
+   if (!s->gpu.boxes.nAtoms || comdBarostatRefusal(s, targetGPa, tauFs, modulusGPa, every, axesMask) != 0) return -1;
+   for (int a = 0; a < 3; ++a) s->baroTarget[a] = targetGPa[a];
+   s->baroTau = tauFs; s->baroModulus = modulusGPa; s->baroEvery = every; s->baroAxes = axesMask; s->baroIso = iso != 0;
+   s->baroPending = 0;
+   s->baro = 1;
+   return 0;
+}
+
+int comdGetBarostat(SimFlat* s, double out8[8])
+{
+   for (int a = 0; a < 3; ++a) out8[a] = s->baroTarget[a];
+   out8[3] = s->baroTau; out8[4] = s->baroModulus; out8[5] = (double)s->baroEvery; out8[6] = (double)s->baroAxes; out8[7] = (double)s->baroIso;
+   return s->baro;
+}
+
+/* the step that has just closed (its forces and its closing half kick are done) couples: p from the fast evaluation, mu, and the box the remap of the coming step
+ * will set.  The list rule learns the coming extents here, a step ahead, as it does for strain rates. */
+static void baroCouple(SimFlat* s, real_t dt)
+{
+   double wk[13], p[3], mu[3];
+   comdVirialFdotr(s, wk);
+   for (int a = 0; a < 3; ++a) p[a] = (wk[6 + a] + wk[a]) / wk[12] * eVperA3inGPa;
+   if (comdBerendsenScale(p, s->baroTarget, (double)s->baroEvery * (double)dt, s->baroTau, s->baroModulus, s->baroAxes, s->baroIso, mu) != 0) {
+      if (printRank())
+         printf("Error: at step %llu the barostat cannot scale the box: pressure [ %g, %g, %g ] GPa, coupling interval %g fs against --baroTau %g fs.\n",
+                (unsigned long long)s->stepCount + 1, p[0], p[1], p[2], (double)s->baroEvery * (double)dt, s->baroTau);
+      fflush(stdout);
+      exit(-1);
+   }
+   for (int a = 0; a < 3; ++a) {
+      s->baroNext[a] = (double)s->domain->globalExtent[a] * mu[a];
+      if (s->baroAxes >> a & 1) s->nextExtent[a] = s->baroNext[a];
+   }
+   s->baroPending = 1;
+   deformListBudget(s);
+   if (s->baroReport) {
+      if (s->baroSamples == s->baroCap) { s->baroCap = s->baroCap ? 2 * s->baroCap : 64; s->baroRows = (double*)realloc(s->baroRows, 12 * (size_t)s->baroCap * sizeof(double)); }
+      double* row = s->baroRows + 12 * (size_t)s->baroSamples++;
+      row[0] = (double)(s->stepCount + 1); row[1] = row[0] * (double)dt;
+      for (int a = 0; a < 3; ++a) { row[2 + a] = p[a]; row[5 + a] = mu[a]; row[8 + a] = s->baroAxes >> a & 1 ? s->baroNext[a] : (double)s->domain->globalExtent[a]; }
+      row[11] = row[8] * row[9] * row[10];
+   }
 }
 
 /* Verlet lists under a changing box.  A pair further apart than rc + skin at the build is, after the box has been compressed to the share
@@ -105,6 +214,7 @@ int comdSetStrainRate(SimFlat* s, const double r[3])
    const int on = r[0] != 0.0 || r[1] != 0.0 || r[2] != 0.0;
    for (int a = 0; a < 3; ++a) if (!(r[a] == r[a]) || !(fabs(r[a]) < 1e300)) return -1;
    if (on && s->gpuProfile) return -1;
+   if (s->baro) for (int a = 0; a < 3; ++a) if (r[a] != 0.0 && (s->baroAxes >> a & 1)) return -1;      /* an axis is strained or pressure-coupled, not both */
    for (int a = 0; a < 3; ++a) {
       s->deformEpsBase[a] = (double)s->domain->globalExtent[a] / s->box0[a] - 1.0;
       s->erate[a] = r[a];
@@ -129,10 +239,11 @@ void comdLocalBounds(SimFlat* s, double out[6])
 double timestep(SimFlat* s, int nSteps, real_t dt)
 {
    const Langevin lv = langevinOf(s, dt);
+   int split = 1;      /* the step before did not carry this step's opening kick and drift: the first step of a call, and the step behind a coupling */
    for (int ii = 0; ii < nSteps; ++ii) {
       /* half kick + drift fused in one kernel (same arithmetic as advanceVelocity(dt/2) then advancePosition(dt)); from the second step
        * on they ride with the previous step's closing half kick (below) */
-      if (ii == 0) {
+      if (split) {
          startTimer(velocityTimer);
          startTimer(positionTimer);
          if (lv.on) advanceVelocityPositionLangevinGpu(&s->gpu, 0.5 * dt, 0.5 * dt, lv.c1, lv.c2, lv.kT, lv.seed, s->stepCount);
@@ -143,11 +254,16 @@ double timestep(SimFlat* s, int nSteps, real_t dt)
 
       /* box deformation: the remap sits behind the drift that has just run (the opening kernel above, or the fused closing kernel of the step before) and in front of
        * the redistribution, on the same stream: the re-binning, the halo images and -- with -a 1 -- the interior force work all see the final geometry */
-      if (s->deform && s->stepCount >= (uint64_t)s->deformStart) {
+      const int strain = s->deform && s->stepCount >= (uint64_t)s->deformStart;
+      if (strain || s->baroPending) {
          startTimer(deformTimer);
-         deformStep(s, dt);
+         deformStep(s, dt, strain);
          stopTimer(deformTimer);
       }
+      /* barostat: a coupling step ends unfused, the way the last step of a call does (the same roundings), so that the pressure is read between its closing half kick
+       * and the next step's opening one; couplings are counted by the global step, so step(4); step(6) couples where step(10) does */
+      const int couple = s->baro && s->stepCount + 1 > (uint64_t)s->baroStart && (s->stepCount + 1 - (uint64_t)s->baroStart) % (uint64_t)s->baroEvery == 0;
+      split = ii == nSteps - 1 || couple;
 
       /* e[] is read by kineticEnergyGpu below only: the last step's forces must carry energies, the others need not
        * (set before redistributeAtoms: with -a 1 it already launches the interior cells' force work) */
@@ -165,7 +281,7 @@ double timestep(SimFlat* s, int nSteps, real_t dt)
       comdPollStatus(&s->gpu, s->gpu.boundary_stream, "timestep");
 
       startTimer(velocityTimer);
-      if (ii == nSteps - 1) advanceVelocity(s, 0.5 * dt);
+      if (split) advanceVelocity(s, 0.5 * dt);
       else {
          /* closing half kick of this step + opening half kick and drift of the next: one pass over the atoms, the two kicks still two
           * separate roundings (bit-identical to the three calls of timestep.c:52-58, 95) */
@@ -175,6 +291,11 @@ double timestep(SimFlat* s, int nSteps, real_t dt)
          stopTimer(positionTimer);
       }
       stopTimer(velocityTimer);
+      if (couple) {
+         startTimer(baroTimer);
+         baroCouple(s, dt);
+         stopTimer(baroTimer);
+      }
       s->stepCount++;
    }
    kineticEnergyGpu(s);
@@ -248,7 +369,7 @@ static void redistributeAtomsNL(SimFlat* sim)
    static int deferred = -1;
    if (deferred < 0) { const char* e = getenv("COMD_NL_DEFERRED"); deferred = e && atoi(e) != 0; }
    /* a box that changes every step changes the thresholds every step: the blocking form */
-   int need = deferred && !sim->deform ? comdNeighborListUpdateDeferredGpu(g) : neighborListUpdateRequiredGpu(g), needAll = 0;
+   int need = deferred && !sim->deform && !sim->baro ? comdNeighborListUpdateDeferredGpu(g) : neighborListUpdateRequiredGpu(g), needAll = 0;
    startTimer(commReduceTimer);
    maxIntParallel(&need, &needAll, 1);
    stopTimer(commReduceTimer);

@@ -259,6 +259,9 @@ typedef struct SimGpuSt {
    double*      strainSumBuf;          /* device: the workgroups' rows for computeAtomStrainSummary, allocated with strainBuf */
    real_t*      heatFluxBuf;           /* device [9][nLocalBoxes*maxAtoms]: the planes jk, jp, jv (x y z each) of computeHeatFlux, allocated by its first call that stores them */
    double*      heatFluxSumBuf;        /* device: the workgroups' rows for the sums of computeHeatFlux, allocated by its first call that reduces */
+   double*      fdotrBuf;              /* device: the workgroups' rows for computeVirialFdotr (atoms kernel, face kernel, result), allocated by its first call */
+   int*         fdotrRows;             /* device [fdotrNRows][5]: its work list (local cell, periodic halo cell, sign x y z), uploaded by comdSetFacePairsGpu */
+   int          fdotrNRows;            /* rows of the list (0 is a valid list: a rank with no periodic face); fdotrRows == NULL: nothing uploaded yet */
 } SimGpu;
 
 /* Everything AllocateGpu needs to know about the rank's geometry and potential.
@@ -467,6 +470,18 @@ void comdSetListBudgetGpu(SimGpu* sim, double budget);
  * stream computeEnergy uses, after the force work of both streams of the overlap mode; deterministic two-stage reduction; reads r, p and
  * dfEmbed only.  Blocks until the result is on the host. */
 void computeVirial(SimGpu* sim, real_t* out12);
+/* Not in the reference: the same twelve numbers as computeVirial -- its contract, layout (W xx yy zz yz xz xy, then K), units and "this rank's share, the sum
+ * over ranks is the global tensor" rule -- from the forces the last force evaluation left in f (hip/fdotr_kernels.h has the identity):
+ *   W_ab = sum over local atoms of (r_i - box/2)_a F_i,b  -  1/2 sum over pairs (i local, j in a periodic-image halo cell) of s_ij,a f_ij,b,   s_ij,a = sign_a box[a],
+ * off-diagonals symmetrised.  The first sum is one pass over r, f and p, the second runs over the work list of comdSetFacePairsGpu only: a surface-sized share
+ * of the pair walk of computeVirial.  box[3] are the current global extents in Angstroms (the box changes: they are an argument of every call).  Valid when
+ * computeVirial is valid AND f is current: after timestep, computeForce.  The rounding differs from computeVirial's: sum r F cancels down from sum |r||F|.
+ * Same stream and ordering as computeVirial; no atomics, fixed grids, bit-reproducible; reads r, f, p, dfEmbed and the cell tables, writes only its own rows of
+ * partials (allocated by the first call, freed by DestroyGpu).  Blocks until the result is on the host.  Exits when no work list has been uploaded. */
+void computeVirialFdotr(SimGpu* sim, const double box[3], real_t* out12);
+/* The work list of computeVirialFdotr: nRows rows of 5 ints (local cell, halo cell that is a periodic image, sign x, sign y, sign z), the halo cell's atoms being
+ * stored at home position + sign_a * L_a.  Static (the cell count never changes): uploaded once.  nRows may be 0.  Exits on a cell id out of range. */
+void comdSetFacePairsGpu(SimGpu* sim, const int* rows5, int nRows);
 /* Not in the reference (CoMD has no structural analysis): this rank's histogram of pair distances, the raw material of g(r),
  *   outCounts[k] = number of ordered pairs (i a local atom, j a local or halo atom, j != i) with k dr <= r_ij < (k + 1) dr,  dr = rMax / nBins,
  * for k = 0 .. nBins - 1, 1 <= nBins <= 4096, in host memory.  Every unordered pair is seen once from each side (from two ranks or images when
