@@ -320,6 +320,10 @@ int* mkAtomCellList(LinkCell* boxes, enum HaloFaceOrder iFace, int nCells);
 int* mkForceSendCellList(LinkCell* boxes, int face, int nCells);
 int* mkForceRecvCellList(LinkCell* boxes, int face, int nCells);
 
+/* a table of samples that grows by doubling (the reports keep one row per sample, the barostat and the exchange one per event): n rows of the width its owner gives nextRow */
+typedef struct RowTableSt { void* rows; int n, cap; } RowTable;
+void* nextRow(RowTable* t, size_t rowBytes);      /* the next row, rowBytes wide: the table grows as needed (reports.c) */
+
 /* ---- simulation: CoMDTypes.h:75-135 ---- */
 typedef struct SimFlatSt {
    int nSteps, printRate;
@@ -347,7 +351,7 @@ typedef struct SimFlatSt {
    int nlBuilds;                    /* list builds so far (reported) */
    int quiet, cmdDoeam;
    int iStepPrev, firstPrint;       /* printThings state (static locals in CoMD.c:466-467) */
-   int pressure;                    /* --pressure: printThings shows the pressure computePressure left in W, K, V */
+   int pressure;                    /* --pressure: the Pressure(GPa) column of printThings and the YAML block, from what computePressure left in W, K, V */
    real_t W[6], K[6], V;            /* computePressure: global pair virial and kinetic tensor in eV (xx yy zz yz xz xy), volume in A^3 */
    int langevin;                    /* --langevin / comdSetLangevin: timestep() runs the BAOAB Langevin kernels */
    double langevinTemp, langevinDamp;   /* target (K) and damping time tau (fs) */
@@ -361,23 +365,20 @@ typedef struct SimFlatSt {
    int trackDisp;                   /* comdTrackDisplacement: the drift kernels add every atom's motion into the device records of its gid */
    int msd, msdStart;               /* --msd: comdMain tracks from global step msdStart on and samples the MSD at every printed step */
    char msdFile[1024];
-   double* msdRows;                 /* [msdSamples][8]: step, the seven values of comdMsd */
-   int msdSamples, msdCap;
+   RowTable msdRows;                /* [8] doubles: step, the seven values of comdMsd */
    double msdNow;                   /* the MSD(A^2) column of printThings: the last sample, 0 before the origin */
    double lat;                      /* the lattice constant the crystal was made with (-l, or the potential's) */
    int csp;                         /* --csp: comdMain samples the centro-symmetry parameter at every printed step */
    double cspThreshold, cspCoord;   /* defect threshold (A^2) and coordination radius (A), defaults resolved */
    char cspFile[1024], cspDump[1024];
-   double* cspRows;                 /* [cspSamples][7]: step, defects, atoms with fewer than 12 neighbours, mean and max of the finite csp, mean coordination, atoms with coordination != 12 */
-   int cspSamples, cspCap;
+   RowTable cspRows;                /* [7] doubles: step, defects, atoms with fewer than 12 neighbours, mean and max of the finite csp, mean coordination, atoms with coordination != 12 */
    double* cspLast;                 /* [2 nGlobal]: csp and coordination by gid of the last sample (--cspDump) */
    void* analysisStage;             /* the by-gid analyses (analysis.c): host staging for the by-slot results, the gids and the occupancies, kept between calls */
    size_t analysisStageBytes;
    int cspDefectsNow;               /* the Defects column of printThings: the last sample */
    int cna;                         /* --cna: comdMain samples the structure types at every printed step */
    char cnaFile[1024], cnaDump[1024];
-   long long* cnaRows;              /* [cnaSamples][5]: step, atoms of type OTHER, FCC, HCP, ICO */
-   int cnaSamples, cnaCap;
+   RowTable cnaRows;                /* [5] long longs: step, atoms of type OTHER, FCC, HCP, ICO */
    int* cnaLast;                    /* [nGlobal]: type by gid of the last sample (--cnaDump) */
    long long cnaNonFccNow;          /* the NonFCC column of printThings: the last sample */
    /* box deformation (--erateX/Y/Z, comdSetBox, comdSetStrainRate): the box is box0 (1 + strain), strain = deformEpsBase + erate * deformTime / 1000 */
@@ -391,28 +392,24 @@ typedef struct SimFlatSt {
    double listExtent[3];            /* *_nl: the global extents at the last list build */
    int boxChanged;                  /* comdSetBox has changed the box at least once: g(r) is normalised with the mean density of its samples */
    double rdfDensitySum;            /* sum over the g(r) samples of N / V */
-   int deformReport;                /* comdMain: V/V0 and Sxx(GPa) columns, the samples below, the file and the YAML block */
+   int deformReport;                /* the Deform report (reports.c): the V/V0 and Sxx(GPa) columns of printThings, the samples below, the file and the YAML block */
    char deformFile[1024];
-   double* deformRows;              /* [deformSamples][15]: step, time (fs), strain (3), extents (3), volume, stress xx yy zz yz xz xy (GPa), temperature (K) */
-   int deformSamples, deformCap;
+   RowTable deformRows;             /* [15] doubles: step, time (fs), strain (3), extents (3), volume, stress xx yy zz yz xz xy (GPa), temperature (K) */
    int stress;                      /* --stress: comdMain samples the per-atom stress summary at every printed step */
    char stressFile[1024], stressDump[1024];
    double stressDumpMin;            /* GPa */
-   double* stressRows;              /* [stressSamples][8]: step, the seven values of comdStressSummary (eV/A^3) */
-   int stressSamples, stressCap;
+   RowTable stressRows;             /* [8] doubles: step, the seven values of comdStressSummary (eV/A^3) */
    double stressMaxVmNow;           /* the MaxVM(GPa) column of printThings: the last sample, in eV/A^3 */
    int strainHasRef;                /* comdStrainReference: the device holds a reference table */
    double strainL0[3];              /* the global box when the reference was taken */
    int strain, strainRef;           /* --strain: comdMain takes the reference at global step strainRef and samples the summary at every printed step from then on */
    double strainCutoff, strainThreshold, strainDumpMin;      /* r_s (A, default resolved), the shear-strain threshold of the count, that of the dump */
    char strainFile[1024], strainDump[1024];
-   double* strainRows;              /* [strainSamples][10]: step, the nine values of comdStrainSummary */
-   int strainSamples, strainCap;
+   RowTable strainRows;             /* [10] doubles: step, the nine values of comdStrainSummary */
    double strainMaxShearNow;        /* the MaxShear column of printThings: the last sample, 0 before the reference */
    int heatflux, hfStart, hfWindow; /* --heatflux: comdMain samples comdHeatFlux at every printed step from global step hfStart on; lags of the autocorrelation (0 = half the samples) */
    char hfFile[1024], hfAcfFile[1024];
-   double* hfRows;                  /* [hfSamples][13]: step, time (fs), the nine sums of comdHeatFlux (eV A/fs), temperature (K), volume (A^3) */
-   int hfSamples, hfCap;
+   RowTable hfRows;                 /* [13] doubles: step, time (fs), the nine sums of comdHeatFlux (eV A/fs), temperature (K), volume (A^3) */
    double hfJxNow;                  /* the Jx column of printThings: the x component of the flux density of the last sample in eV/A^2/fs, 0 before hfStart */
    /* Berendsen barostat (--baro, comdSetBarostat): every baroEvery steps the step ends unfused, the pressure of comdVirialFdotr gives mu, and the next step's remap
     * sets the box the coupling asked for */
@@ -422,10 +419,9 @@ typedef struct SimFlatSt {
    int baroEvery, baroAxes, baroIso, baroStart;      /* axes: bit a = axis a is scaled */
    int baroPending;                 /* a coupling has set baroNext: the remap of the coming step applies it */
    double baroNext[3];              /* the extents that remap will set on the barostat's axes */
-   int baroReport;                  /* comdMain: the Pressure(GPa) and V/V0 columns, the file and the YAML block */
+   int baroReport;                  /* the Barostat report (reports.c): the Pressure(GPa) and V/V0 columns of printThings, the file and the YAML block */
    char baroFile[1024];
-   double* baroRows;                /* [baroSamples][12]: step, time (fs), p xx yy zz (GPa), mu x y z, L x y z (A), V (A^3) -- the box after the coupling */
-   int baroSamples, baroCap;
+   RowTable baroRows;               /* [12] doubles: step, time (fs), p xx yy zz (GPa), mu x y z, L x y z (A), V (A^3) -- the box after the coupling */
    int* facePairs;                  /* comdVirialFdotr: the rows of comdPeriodicFacePairs, built at its first call */
    int nFacePairs;
    /* slab profiles (--profile): comdMain adds comdSlabProfile's integer planes up at every printed step from global step profStart on */
@@ -441,10 +437,9 @@ typedef struct SimFlatSt {
    double mpExchanged;              /* eV carried from the cold to the hot slab by all exchanges so far (comdMullerPlatheSwap adds to it) */
    long long mpPairs, mpSkipped, mpExchanges;      /* pairs swapped, pairs asked for and not swapped, exchanges */
    double mpExchangedAtProfStart;   /* mpExchanged after the exchanges of the steps up to global step profStart */
-   int mpReport;                    /* comdMain: the dE(eV) column, the file and the YAML block */
+   int mpReport;                    /* the MullerPlathe report (reports.c): the dE(eV) column of printThings; the file and the YAML block come from the profile's writer */
    char mpFile[1024];
-   double* mpRows;                  /* [mpSamples][6]: step, time (fs), kept pairs, skipped pairs, dE (eV), cumulative E (eV) */
-   int mpSamples, mpCap;
+   RowTable mpRows;                 /* [6] doubles: step, time (fs), kept pairs, skipped pairs, dE (eV), cumulative E (eV) */
    double* mpTable;                 /* comdMullerPlatheSwap: the candidate table of all ranks and its staging, 2 x [2][nRanks * 64][6] */
 } SimFlat;
 
@@ -457,6 +452,14 @@ Validate* initValidate(SimFlat* s);
 void validateResult(const Validate* val, SimFlat* sim);
 void printSimulationDataYaml(FILE* file, SimFlat* s);
 void setBoundaryCellsHost(SimFlat* sim, HaloExchange* hh);
+
+/* ---- the run-time reports (not in the reference): reports.c, one table row each ---- */
+void reportsSample(SimFlat* s, int iStep);                     /* a printed step: every report that is on and has begun samples, each under its timer; collective */
+int  reportsNextStart(const SimFlat* s, int iStep, int end);   /* the first step in (iStep, end) at which a report takes its origin or reference; end when none does */
+void reportsStart(SimFlat* s, int iStep);                      /* ... and takes it: for such a step between two printed ones */
+void reportsColumns(const SimFlat* s, int header);             /* printThings: the reports' part of the header line (header != 0) or of a row */
+void reportsWrite(FILE* yaml, SimFlat* s, int iStep);          /* the end of the run: files and YAML blocks; collective */
+void reportsFree(SimFlat* s);                                  /* what the reports keep in SimFlat */
 
 /* ---- timestep.h ---- */
 double timestep(SimFlat* s, int n, real_t dt);

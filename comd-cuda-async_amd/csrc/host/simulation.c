@@ -1,7 +1,8 @@
 /* simulation.c -- simulation set-up/tear-down, the stdout report and the driver loop.
  * Follows CoMD.c: main (:86-187), initSimulation (:200-327), destroySimulation (:330-351), initValidate/validateResult
  * (:395-440), sumAtoms (:442-457), printThings (:463-494), printSimulationDataYaml (:498-552), sanityChecks (:555-604).
- * Table headers and number formats are the reference's, verbatim, because downstream scripts parse them. */
+ * Table headers and number formats are the reference's, verbatim, because downstream scripts parse them.  The run-time reports the reference lacks (--pressure,
+ * --rdf, --msd, ...) are the rows of the table in reports.c: comdMain and printThings reach them through reportsSample, reportsColumns and reportsWrite alone. */
 #include "comd_host.h"
 #include <math.h>
 #include <stdlib.h>
@@ -351,16 +352,8 @@ void destroySimulation(SimFlat** ps)
    destroyAtoms(s->atoms);
    free(s->boundary_cells_h); free(s->interior_cells_h); free(s->boundary1_cells_h);
    free(s->ljTable);
-   free(s->rdfSum);
-   free(s->msdRows);
-   free(s->cspRows); free(s->cspLast); free(s->analysisStage);
-   free(s->cnaRows); free(s->cnaLast);
-   free(s->deformRows);
-   free(s->baroRows); free(s->facePairs);
-   free(s->profSum); free(s->mpRows); free(s->mpTable);
-   free(s->stressRows);
-   free(s->strainRows);
-   free(s->hfRows);
+   reportsFree(s);
+   free(s->analysisStage); free(s->facePairs); free(s->mpTable);
    free(s->species); free(s->domain); free(s);
    *ps = NULL;
 }
@@ -384,10 +377,9 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
       s->firstPrint = 0;
       fprintf(screenOut,
               "#                                                                                         Performance\n"
-              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms%s%s%s%s%s%s%s%s%s%s\n",
-              s->pressure || s->baroReport ? "    Pressure(GPa)" : "", s->msd ? "         MSD(A^2)" : "", s->csp ? "      Defects" : "", s->cna ? "       NonFCC" : "",
-              s->deformReport ? "           V/V0         Sxx(GPa)" : "", s->baroReport && !s->deformReport ? "           V/V0" : "", s->stress ? "       MaxVM(GPa)" : "",
-              s->strain ? "         MaxShear" : "", s->heatflux ? "       Jx(eV/A^2/fs)" : "", s->mpReport ? "              dE(eV)" : "");
+              "#  Loop   Time(fs)       Total Energy   Potential Energy     Kinetic Energy  Temperature   (us/atom)     # Atoms");
+      reportsColumns(s, 1);
+      fprintf(screenOut, "\n");
       fflush(screenOut);
    }
    real_t time = iStep * s->dt;
@@ -398,691 +390,8 @@ void printThings(SimFlat* s, int iStep, double elapsedTime)
    double timePerAtom = 1.0e6 * elapsedTime / (double)(nEval * s->atoms->nLocal);
    fprintf(screenOut, " %6d %10.2f %18.12f %18.12f %18.12f %12.4f %10.4f %12d",
            iStep, time, eTotal, eU, eK, Temp, timePerAtom, s->atoms->nGlobal);
-   if (s->pressure || s->baroReport) fprintf(screenOut, " %16.10f", pressureOf(s) * eVperA3inGPa);
-   if (s->msd) fprintf(screenOut, " %16.10e", s->msdNow);
-   if (s->csp) fprintf(screenOut, " %12d", s->cspDefectsNow);
-   if (s->cna) fprintf(screenOut, " %12lld", s->cnaNonFccNow);
-   if (s->deformReport) fprintf(screenOut, " %14.10f %16.10f", (double)s->V / (s->box0[0] * s->box0[1] * s->box0[2]), -((double)s->K[0] + s->W[0]) / s->V * eVperA3inGPa);
-   if (s->baroReport && !s->deformReport) fprintf(screenOut, " %14.10f", (double)s->V / (s->box0[0] * s->box0[1] * s->box0[2]));
-   if (s->stress) fprintf(screenOut, " %16.10f", s->stressMaxVmNow * eVperA3inGPa);
-   if (s->strain) fprintf(screenOut, " %16.10f", s->strainMaxShearNow);
-   if (s->heatflux) fprintf(screenOut, " %19.10e", s->hfJxNow);
-   if (s->mpReport) fprintf(screenOut, " %19.10e", s->mpExchanged);
+   reportsColumns(s, 0);
    fprintf(screenOut, "\n");
-}
-
-/* --pressure: the final pressure and tensor (K + W) / V, components xx yy zz yz xz xy */
-static void printPressureYaml(FILE* file, SimFlat* s)
-{
-   if (!printRank() || !file) return;
-   static const char* name[6] = { "xx", "yy", "zz", "yz", "xz", "xy" };
-   fprintf(file, "Pressure:\n");
-   fprintf(file, "  Units: GPa\n");
-   fprintf(file, "  Pressure: %.12e\n", pressureOf(s) * eVperA3inGPa);
-   for (int c = 0; c < 6; ++c) fprintf(file, "  P%s: %.12e\n", name[c], ((double)s->K[c] + s->W[c]) / s->V * eVperA3inGPa);
-   fprintf(file, "\n");
-   fflush(file);
-}
-
-/* --rdf: one more sample of the global pair histogram into rdfSum */
-static void sampleRdf(SimFlat* s)
-{
-   double* counts = (double*)malloc((size_t)s->rdfBins * sizeof(double));
-   if (comdPairHistogram(s, s->rdfBins, s->rdfMax, counts) != 0) { printf("Error: --rdf %d --rdfMax %g was refused.\n", s->rdfBins, s->rdfMax); exit(-1); }
-   for (int k = 0; k < s->rdfBins; ++k) s->rdfSum[k] += counts[k];
-   s->rdfDensitySum += (double)s->atoms->nGlobal / ((double)s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2]);
-   s->rdfSamples++;
-   free(counts);
-}
-
-/* --rdf: g_k = counts_k / (samples (N/2) (N/V) (4 pi/3) ((k + 1)^3 - k^3) dr^3), the ideal-gas count of unordered pairs in the shell of bin k; with a box
- * that changed during the run (--erateX/Y/Z) N/V is the mean over the samples, and the header's V is N over that mean.
- * The file: a header line, then per bin its centre, g, the running coordination number n(r) = 2 sum counts / (samples N) up to the bin's upper edge and the
- * mean pair count per sample.  The YAML block names the file and the position of the highest peak. */
-static void writeRdf(FILE* yaml, SimFlat* s)
-{
-   if (!printRank()) return;
-   const int nBins = s->rdfBins, samples = s->rdfSamples;
-   const double N = (double)s->atoms->nGlobal;
-   const double V = s->boxChanged && samples > 0 ? N / (s->rdfDensitySum / samples) : (double)s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2];
-   const double dr = s->rdfMax / nBins, shell = 4.0 * M_PI / 3.0 * dr * dr * dr;
-   FILE* f = fopen(s->rdfFile, "w");
-   if (!f) { printf("Error: cannot write %s\n", s->rdfFile); exit(-1); }
-   fprintf(f, "# g(r): bins %d rMax %.17g samples %d N %d V %.17g | columns: r (A), g(r), n(r), pairs per sample\n", nBins, s->rdfMax, samples, s->atoms->nGlobal, V);
-   double running = 0.0, gTop = -1.0, rTop = 0.0;
-   for (int k = 0; k < nBins; ++k) {
-      const double k0 = (double)k, k1 = (double)k + 1.0;
-      const double g = s->rdfSum[k] / ((double)samples * (0.5 * N) * (N / V) * shell * (k1 * k1 * k1 - k0 * k0 * k0));
-      running += s->rdfSum[k];
-      fprintf(f, "%.17g %.17g %.17g %.17g\n", (k0 + 0.5) * dr, g, 2.0 * running / ((double)samples * N), s->rdfSum[k] / (double)samples);
-      if (g > gTop) { gTop = g; rTop = (k0 + 0.5) * dr; }
-   }
-   fclose(f);
-   if (!yaml) return;
-   fprintf(yaml, "RDF:\n");
-   fprintf(yaml, "  bins: %d\n", nBins);
-   fprintf(yaml, "  rMax: %.12e\n", s->rdfMax);
-   fprintf(yaml, "  samples: %d\n", samples);
-   fprintf(yaml, "  file: %s\n", s->rdfFile);
-   fprintf(yaml, "  rOfHighestG: %.12e\n", rTop);
-   fprintf(yaml, "\n");
-   fflush(yaml);
-}
-
-/* --msd: the origin: tracking on (or, were it on already, zeroed again) */
-static void startMsd(SimFlat* s)
-{
-   if (comdTrackDisplacement(s, 1) != 0) { printf("Error: --msd: no device memory for the displacement records of %d atoms.\n", s->atoms->nGlobal); exit(-1); }
-}
-
-/* positions by gid over all ranks, [nGlobal][3], malloc'd: collective */
-static double* positionsByGid(SimFlat* s)
-{
-   const size_t n = (size_t)s->atoms->nGlobal;
-   double* mine = (double*)calloc(n ? 3 * n : 1, sizeof(double));
-   double* pos = (double*)malloc((n ? 3 * n : 1) * sizeof(double));
-   comdGatherByGid(s, 0, mine);
-   addDoubleParallelLong(mine, pos, 3 * n);
-   free(mine);
-   return pos;
-}
-
-/* the next row of a table of samples that grows by doubling: rows[cap][width] elements of `size` bytes */
-static void* nextRow(void* rowsPtr, int* cap, int* samples, size_t width, size_t size)
-{
-   void* rows;
-   memcpy(&rows, rowsPtr, sizeof rows);          /* rowsPtr: the address of a double* or a long long* */
-   if (*samples == *cap) { *cap = *cap ? 2 * *cap : 64; rows = realloc(rows, (size_t)*cap * width * size); memcpy(rowsPtr, &rows, sizeof rows); }
-   return (char*)rows + width * size * (size_t)(*samples)++;
-}
-
-/* --msd: one more row {step, sum d (3), sum d^2 (3), N} */
-static void sampleMsd(SimFlat* s, int iStep)
-{
-   double* row = (double*)nextRow(&s->msdRows, &s->msdCap, &s->msdSamples, 8, sizeof(double));
-   row[0] = (double)iStep;
-   if (comdMsd(s, row + 1) != 0) { printf("Error: --msd: the displacements could not be summed.\n"); exit(-1); }
-   s->msdNow = (row[4] + row[5] + row[6]) / row[7];
-}
-
-/* --msd: the file: a header line, then per sample the time since the origin in fs, MSD = sum |d|^2 / N, its x, y, z parts and the MSD with the drift of the
- * centre of mass removed, sum |d|^2 / N - |sum d / N|^2 (a Langevin thermostat does not conserve momentum: the centre of mass walks).  The YAML block names
- * the file and gives D = slope / 6 of a least-squares line through the drift-removed MSD of the samples in the second half of the tracked interval. */
-static void writeMsd(FILE* yaml, SimFlat* s)
-{
-   if (!printRank()) return;
-   const int samples = s->msdSamples;
-   FILE* f = fopen(s->msdFile, "w");
-   if (!f) { printf("Error: cannot write %s\n", s->msdFile); exit(-1); }
-   fprintf(f, "# MSD: N %d dt %.17g originStep %d samples %d | columns: t - t0 (fs), MSD (A^2), MSD_x, MSD_y, MSD_z, MSD without the centre-of-mass drift\n",
-           s->atoms->nGlobal, s->dt, s->msdStart, samples);
-   double tLast = 0.0, msdLast = 0.0, freeLast = 0.0;
-   double st = 0.0, sy = 0.0, stt = 0.0, sty = 0.0; int m = 0;
-   if (samples > 0) tLast = (s->msdRows[8 * (size_t)(samples - 1)] - s->msdStart) * s->dt;
-   for (int k = 0; k < samples; ++k) {
-      const double* row = s->msdRows + 8 * (size_t)k;
-      const double N = row[7], t = (row[0] - s->msdStart) * s->dt;
-      const double mx = row[4] / N, my = row[5] / N, mz = row[6] / N;
-      const double cx = row[1] / N, cy = row[2] / N, cz = row[3] / N;
-      msdLast = mx + my + mz; freeLast = msdLast - (cx * cx + cy * cy + cz * cz);
-      fprintf(f, "%.17g %.17g %.17g %.17g %.17g %.17g\n", t, msdLast, mx, my, mz, freeLast);
-      if (t >= 0.5 * tLast) { st += t; sy += freeLast; stt += t * t; sty += t * freeLast; m++; }
-   }
-   fclose(f);
-   if (!yaml) return;
-   fprintf(yaml, "MSD:\n");
-   fprintf(yaml, "  originStep: %d\n", s->msdStart);
-   fprintf(yaml, "  samples: %d\n", samples);
-   fprintf(yaml, "  finalMSD: %.12e\n", msdLast);
-   fprintf(yaml, "  finalMSDNoDrift: %.12e\n", freeLast);
-   fprintf(yaml, "  Units: Angstroms^2\n");
-   fprintf(yaml, "  file: %s\n", s->msdFile);
-   const double det = m * stt - st * st;
-   if (m >= 3 && det > 0.0) {
-      const double D = (m * sty - st * sy) / det / 6.0;
-      fprintf(yaml, "  D: %.12e\n", D);
-      fprintf(yaml, "  DUnits: Angstroms^2/fs\n");
-      fprintf(yaml, "  D_cm2_per_s: %.12e\n", 0.1 * D);
-      fprintf(yaml, "  fitSamples: %d\n", m);
-   } else fprintf(yaml, "  D: n/a\n");
-   fprintf(yaml, "\n");
-   fflush(yaml);
-}
-
-/* --csp: one more row {step, defects, atoms with fewer than 12 neighbours, mean and max of the finite csp, mean coordination, atoms with coordination != 12} */
-static void sampleCsp(SimFlat* s, int iStep)
-{
-   const size_t n = (size_t)s->atoms->nGlobal;
-   if (!s->cspLast) s->cspLast = (double*)malloc((n ? 2 * n : 1) * sizeof(double));
-   if (comdCentroSymmetry(s, s->cspCoord, s->cspLast, s->cspLast + n) != 0) { printf("Error: --csp --cspCoord %g was refused.\n", s->cspCoord); exit(-1); }
-   double* row = (double*)nextRow(&s->cspRows, &s->cspCap, &s->cspSamples, 7, sizeof(double));
-   double defects = 0.0, few = 0.0, sum = 0.0, top = 0.0, coordSum = 0.0, not12 = 0.0;
-   for (size_t g = 0; g < n; ++g) {
-      const double c = s->cspLast[g], z = s->cspLast[n + g];
-      if (c > s->cspThreshold) defects += 1.0;
-      if (isinf(c)) few += 1.0; else { sum += c; if (c > top) top = c; }
-      coordSum += z;
-      if (z != 12.0) not12 += 1.0;
-   }
-   row[0] = (double)iStep; row[1] = defects; row[2] = few;
-   row[3] = n > few ? sum / ((double)n - few) : 0.0; row[4] = top;
-   row[5] = n ? coordSum / (double)n : 0.0; row[6] = not12;
-   s->cspDefectsNow = (int)defects;
-}
-
-/* --csp: the file: a header line, then the rows of sampleCsp.  --cspDump: the defect atoms of the last sample as extended XYZ, Cu x y z csp coordination gid,
- * the positions gathered by gid over the ranks as the results are.  The YAML block names the file and gives the last sample's defects and mean csp. */
-static void writeCsp(FILE* yaml, SimFlat* s)
-{
-   const size_t n = (size_t)s->atoms->nGlobal;
-   double* pos = NULL;
-   if (s->cspDump[0]) {          /* collective: before the other ranks leave */
-      pos = positionsByGid(s);
-   }
-   if (!printRank()) { free(pos); return; }
-   const int samples = s->cspSamples;
-   FILE* f = fopen(s->cspFile, "w");
-   if (!f) { printf("Error: cannot write %s\n", s->cspFile); exit(-1); }
-   fprintf(f, "# CSP: N %d threshold %.17g rCoord %.17g samples %d | columns: step, defects (csp > threshold), atoms with fewer than 12 neighbours, "
-              "mean csp (A^2, finite ones), max csp, mean coordination, atoms with coordination != 12\n", s->atoms->nGlobal, s->cspThreshold, s->cspCoord, samples);
-   const double* last = NULL;
-   for (int k = 0; k < samples; ++k) {
-      last = s->cspRows + 7 * (size_t)k;
-      fprintf(f, "%.0f %.0f %.0f %.17g %.17g %.17g %.0f\n", last[0], last[1], last[2], last[3], last[4], last[5], last[6]);
-   }
-   fclose(f);
-   if (pos && s->cspLast) {
-      f = fopen(s->cspDump, "w");
-      if (!f) { printf("Error: cannot write %s\n", s->cspDump); exit(-1); }
-      const real_t* L = s->domain->globalExtent;
-      fprintf(f, "%.0f\n", last ? last[1] : 0.0);
-      fprintf(f, "Lattice=\"%.17g 0 0 0 %.17g 0 0 0 %.17g\" Properties=species:S:1:pos:R:3:csp:R:1:coordination:I:1:gid:I:1 step=%.0f threshold=%.17g rCoord=%.17g\n",
-              (double)L[0], (double)L[1], (double)L[2], last ? last[0] : 0.0, s->cspThreshold, s->cspCoord);
-      for (size_t g = 0; g < n; ++g)
-         if (s->cspLast[g] > s->cspThreshold)
-            fprintf(f, "Cu %.17g %.17g %.17g %.17g %d %zu\n", pos[3 * g], pos[3 * g + 1], pos[3 * g + 2], s->cspLast[g], (int)s->cspLast[n + g], g);
-      fclose(f);
-   }
-   free(pos);
-   if (!yaml) return;
-   fprintf(yaml, "CSP:\n");
-   fprintf(yaml, "  threshold: %.12e\n", s->cspThreshold);
-   fprintf(yaml, "  rCoord: %.12e\n", s->cspCoord);
-   fprintf(yaml, "  samples: %d\n", samples);
-   fprintf(yaml, "  file: %s\n", s->cspFile);
-   fprintf(yaml, "  finalDefects: %.0f\n", last ? last[1] : 0.0);
-   fprintf(yaml, "  finalMeanCsp: %.12e\n", last ? last[3] : 0.0);
-   fprintf(yaml, "\n");
-   fflush(yaml);
-}
-
-/* --cna: one more row {step, atoms of type OTHER, FCC, HCP, ICO} */
-static void sampleCna(SimFlat* s, int iStep)
-{
-   const size_t n = (size_t)s->atoms->nGlobal;
-   if (!s->cnaLast) s->cnaLast = (int*)malloc((n ? n : 1) * sizeof(int));
-   long long counts[5];
-   comdCommonNeighbors(s, s->cnaLast, counts);
-   long long* row = (long long*)nextRow(&s->cnaRows, &s->cnaCap, &s->cnaSamples, 5, sizeof(long long));
-   row[0] = iStep; row[1] = counts[COMD_CNA_OTHER]; row[2] = counts[COMD_CNA_FCC]; row[3] = counts[COMD_CNA_HCP]; row[4] = counts[COMD_CNA_ICO];
-   s->cnaNonFccNow = (long long)n - counts[COMD_CNA_FCC];
-}
-
-/* --cna: the file: a header line, then the rows of sampleCna.  --cnaDump: the non-FCC atoms of the last sample as extended XYZ, Cu x y z type gid, the
- * positions gathered by gid over the ranks as the types are.  The YAML block names the file and gives the last sample's counts and HCP fraction. */
-static void writeCna(FILE* yaml, SimFlat* s)
-{
-   const size_t n = (size_t)s->atoms->nGlobal;
-   double* pos = NULL;
-   if (s->cnaDump[0]) {          /* collective: before the other ranks leave */
-      pos = positionsByGid(s);
-   }
-   if (!printRank()) { free(pos); return; }
-   const int samples = s->cnaSamples;
-   FILE* f = fopen(s->cnaFile, "w");
-   if (!f) { printf("Error: cannot write %s\n", s->cnaFile); exit(-1); }
-   fprintf(f, "# CNA: N %d samples %d | columns: step, atoms of type other (0), FCC (1), HCP (2), ICO (4)\n", s->atoms->nGlobal, samples);
-   const long long zero[5] = { 0, 0, 0, 0, 0 };
-   const long long* last = zero;
-   for (int k = 0; k < samples; ++k) {
-      last = s->cnaRows + 5 * (size_t)k;
-      fprintf(f, "%lld %lld %lld %lld %lld\n", last[0], last[1], last[2], last[3], last[4]);
-   }
-   fclose(f);
-   const long long nonFcc = samples ? (long long)n - last[2] : 0;
-   if (pos && s->cnaLast) {
-      f = fopen(s->cnaDump, "w");
-      if (!f) { printf("Error: cannot write %s\n", s->cnaDump); exit(-1); }
-      const real_t* L = s->domain->globalExtent;
-      fprintf(f, "%lld\n", nonFcc);
-      fprintf(f, "Lattice=\"%.17g 0 0 0 %.17g 0 0 0 %.17g\" Properties=species:S:1:pos:R:3:type:I:1:gid:I:1 step=%lld\n",
-              (double)L[0], (double)L[1], (double)L[2], last[0]);
-      for (size_t g = 0; g < n; ++g)
-         if (s->cnaLast[g] != COMD_CNA_FCC)
-            fprintf(f, "Cu %.17g %.17g %.17g %d %zu\n", pos[3 * g], pos[3 * g + 1], pos[3 * g + 2], s->cnaLast[g], g);
-      fclose(f);
-   }
-   free(pos);
-   if (!yaml) return;
-   fprintf(yaml, "CNA:\n");
-   fprintf(yaml, "  samples: %d\n", samples);
-   fprintf(yaml, "  file: %s\n", s->cnaFile);
-   fprintf(yaml, "  finalOther: %lld\n", last[1]);
-   fprintf(yaml, "  finalFCC: %lld\n", last[2]);
-   fprintf(yaml, "  finalHCP: %lld\n", last[3]);
-   fprintf(yaml, "  finalICO: %lld\n", last[4]);
-   fprintf(yaml, "  finalHCPFraction: %.12e\n", n ? (double)last[3] / (double)n : 0.0);
-   fprintf(yaml, "\n");
-   fflush(yaml);
-}
-
-/* --erateX/Y/Z: one more row {step, time, strain (3), extents (3), volume, stress = -(K + W) / V in GPa (xx yy zz yz xz xy; tension positive), temperature} from
- * the tensors computePressure has just left in W, K, V */
-static void sampleDeform(SimFlat* s, int iStep)
-{
-   double* row = (double*)nextRow(&s->deformRows, &s->deformCap, &s->deformSamples, 15, sizeof(double));
-   row[0] = (double)iStep; row[1] = iStep * s->dt;
-   for (int a = 0; a < 3; ++a) { row[5 + a] = (double)s->domain->globalExtent[a]; row[2 + a] = row[5 + a] / s->box0[a] - 1.0; }
-   row[8] = (double)s->V;
-   for (int c = 0; c < 6; ++c) row[9 + c] = -((double)s->K[c] + s->W[c]) / s->V * eVperA3inGPa;
-   row[14] = (s->eKinetic / s->atoms->nGlobal) / (kB_eV * 1.5);
-}
-
-/* --erateX/Y/Z: the file: a header with N, the initial box and the rates, then the rows of sampleDeform.  The YAML block gives the rates, the start step, the
- * final strains and box, the file and the number of samples. */
-static void writeDeform(FILE* yaml, SimFlat* s)
-{
-   if (!printRank()) return;
-   const int samples = s->deformSamples;
-   FILE* f = fopen(s->deformFile, "w");
-   if (!f) { printf("Error: cannot write %s\n", s->deformFile); exit(-1); }
-   fprintf(f, "# Deform: N %d L0 %.17g %.17g %.17g rates(1/ps) %.17g %.17g %.17g startStep %d samples %d | columns: step, time (fs), strain x y z, L x y z (A), V (A^3), "
-              "stress xx yy zz yz xz xy (GPa, tension positive), T (K)\n",
-           s->atoms->nGlobal, s->box0[0], s->box0[1], s->box0[2], s->erate[0], s->erate[1], s->erate[2], s->deformStart, samples);
-   for (int k = 0; k < samples; ++k) {
-      const double* r = s->deformRows + 15 * (size_t)k;
-      fprintf(f, "%.0f %.17g", r[0], r[1]);
-      for (int c = 2; c < 15; ++c) fprintf(f, " %.17g", r[c]);
-      fprintf(f, "\n");
-   }
-   fclose(f);
-   if (!yaml) return;
-   const real_t* L = s->domain->globalExtent;
-   fprintf(yaml, "Deform:\n");
-   fprintf(yaml, "  rates: [ %.12e, %.12e, %.12e ]\n", s->erate[0], s->erate[1], s->erate[2]);
-   fprintf(yaml, "  rateUnits: 1/ps\n");
-   fprintf(yaml, "  startStep: %d\n", s->deformStart);
-   fprintf(yaml, "  finalStrain: [ %.12e, %.12e, %.12e ]\n", (double)L[0] / s->box0[0] - 1.0, (double)L[1] / s->box0[1] - 1.0, (double)L[2] / s->box0[2] - 1.0);
-   fprintf(yaml, "  finalBox: [ %.12e, %.12e, %.12e ]\n", (double)L[0], (double)L[1], (double)L[2]);
-   fprintf(yaml, "  file: %s\n", s->deformFile);
-   fprintf(yaml, "  samples: %d\n", samples);
-   fprintf(yaml, "\n");
-   fflush(yaml);
-}
-
-/* --baro: the file: a header with the settings, then the rows timestep() has kept, one per coupling.  The YAML block gives the settings, the couplings, the final
- * box and the mean of the fast pressure over the last half of the couplings. */
-static void writeBaro(FILE* yaml, SimFlat* s)
-{
-   if (!printRank()) return;
-   const int n = s->baroSamples;
-   char axes[4] = "", *c = axes;
-   for (int a = 0; a < 3; ++a) if (s->baroAxes >> a & 1) *c++ = (char)('x' + a);
-   *c = '\0';
-   FILE* f = fopen(s->baroFile, "w");
-   if (!f) { printf("Error: cannot write %s\n", s->baroFile); exit(-1); }
-   fprintf(f, "# Barostat: N %d target(GPa) %.17g tau(fs) %.17g modulus(GPa) %.17g every %d axes %s iso %d startStep %d couplings %d | columns: step, time (fs), "
-              "p xx yy zz (GPa, compressive positive, from the forces and the face pairs), mu x y z, L x y z (A) and V (A^3) the coupling asked for\n",
-           s->atoms->nGlobal, s->baroTarget[0], s->baroTau, s->baroModulus, s->baroEvery, axes, s->baroIso, s->baroStart, n);
-   for (int k = 0; k < n; ++k) {
-      const double* r = s->baroRows + 12 * (size_t)k;
-      fprintf(f, "%.0f %.17g", r[0], r[1]);
-      for (int i = 2; i < 12; ++i) fprintf(f, " %.17g", r[i]);
-      fprintf(f, "\n");
-   }
-   fclose(f);
-   if (!yaml) return;
-   double mean[3] = { 0.0, 0.0, 0.0 };
-   const int from = n / 2;
-   for (int k = from; k < n; ++k) for (int a = 0; a < 3; ++a) mean[a] += s->baroRows[12 * (size_t)k + 2 + a] / (double)(n - from);
-   const real_t* L = s->domain->globalExtent;
-   fprintf(yaml, "Barostat:\n");
-   fprintf(yaml, "  target: %.12e\n  pressureUnits: GPa\n  tau: %.12e\n  modulus: %.12e\n  every: %d\n  axes: %s\n  iso: %d\n  startStep: %d\n",
-           s->baroTarget[0], s->baroTau, s->baroModulus, s->baroEvery, axes, s->baroIso, s->baroStart);
-   fprintf(yaml, "  couplings: %d\n", n);
-   fprintf(yaml, "  finalBox: [ %.12e, %.12e, %.12e ]\n", (double)L[0], (double)L[1], (double)L[2]);
-   fprintf(yaml, "  meanPressureLastHalf: [ %.12e, %.12e, %.12e ]\n", mean[0], mean[1], mean[2]);
-   fprintf(yaml, "  file: %s\n", s->baroFile);
-   fprintf(yaml, "\n");
-   fflush(yaml);
-}
-
-/* --profile: the planes of this printed step are added to the sums; integers, so the time average does not depend on the order either */
-static void sampleProfile(SimFlat* s, int iStep)
-{
-   const int n = s->profBins;
-   int64_t* now = (int64_t*)malloc(6 * (size_t)n * sizeof(int64_t));
-   if (comdSlabProfile(s, s->profAxis, n, now) != 0) { printf("Error: --profile needs the device state.\n"); exit(-1); }
-   for (int k = 0; k < 6 * n; ++k) s->profSum[k] += now[k];
-   free(now);
-   const real_t* L = s->domain->globalExtent;
-   if (s->profSamples == 0) s->profFirstStep = iStep;
-   s->profLastStep = iStep;
-   s->profSamples++;
-   s->profLSum += (double)L[s->profAxis];
-   s->profAreaSum += (double)L[(s->profAxis + 1) % 3] * (double)L[(s->profAxis + 2) % 3];
-}
-
-#define COMD_PROFILE_UNIT (1.0 / 4294967296.0)      /* eV, eV fs/A per unit of the device sums */
-
-/* --profile, --mp: the files and the YAML blocks.  profFile: a header with N, the axis, the bins, the mean extent and the samples, then per bin the centre (A), the
- * mean count per sample, the time-averaged temperature T = 2 sum KE / (3 kB sum count) (K), the mean KE and e per atom (eV) and the mean velocity x y z (A/fs); an
- * empty bin prints nan.  mpFile: a row per exchange.  The conductivity: q = E / (2 A t) with E the energy exchanged since global step profStart (the exchanges
- * of the steps after it) and t the time from that step to the last sample, A the mean cross-section, the gradient from comdFourierKappa. */
-static void writeProfile(FILE* yaml, SimFlat* s)
-{
-   if (!printRank()) return;
-   const int n = s->profBins, samples = s->profSamples;
-   const double meanL = samples ? s->profLSum / samples : (double)s->domain->globalExtent[s->profAxis], width = meanL / n;
-   const double mass = (double)s->species[0].mass;
-   double* T = (double*)malloc((size_t)n * sizeof(double));
-   double tMin = NAN, tMax = NAN;
-   FILE* f = fopen(s->profFile, "w");
-   if (!f) { printf("Error: cannot write %s\n", s->profFile); exit(-1); }
-   fprintf(f, "# Profile: N %d axis %c bins %d meanL %.17g A samples %d startStep %d | columns: bin centre (A), mean count per sample, T (K), KE per atom (eV), "
-              "e per atom (eV), mean velocity x y z (A/fs)\n", s->atoms->nGlobal, 'x' + s->profAxis, n, meanL, samples, s->profStart);
-   for (int b = 0; b < n; ++b) {
-      const double count = (double)s->profSum[b];
-      if (count > 0.0) {
-         const double ke = (double)s->profSum[4 * n + b] * COMD_PROFILE_UNIT;
-         T[b] = 2.0 * ke / (3.0 * kB_eV * count);
-         if (!(tMin <= T[b])) tMin = T[b];
-         if (!(tMax >= T[b])) tMax = T[b];
-         fprintf(f, "%.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", (b + 0.5) * width, count / samples, T[b], ke / count,
-                 (double)s->profSum[5 * n + b] * COMD_PROFILE_UNIT / count, (double)s->profSum[n + b] * COMD_PROFILE_UNIT / count / mass,
-                 (double)s->profSum[2 * n + b] * COMD_PROFILE_UNIT / count / mass, (double)s->profSum[3 * n + b] * COMD_PROFILE_UNIT / count / mass);
-      } else {
-         T[b] = NAN;
-         fprintf(f, "%.17g %.17g nan nan nan nan nan nan\n", (b + 0.5) * width, 0.0);
-      }
-   }
-   fclose(f);
-   if (yaml) {
-      fprintf(yaml, "Profile:\n");
-      fprintf(yaml, "  axis: %c\n  bins: %d\n  startStep: %d\n  samples: %d\n  file: %s\n", 'x' + s->profAxis, n, s->profStart, samples, s->profFile);
-      if (tMin == tMin) fprintf(yaml, "  minTemperature: %.12e\n  maxTemperature: %.12e\n", tMin, tMax); else fprintf(yaml, "  minTemperature: n/a\n  maxTemperature: n/a\n");
-      fprintf(yaml, "  temperatureUnits: K\n\n");
-      fflush(yaml);
-   }
-   if (s->mpReport) {
-      f = fopen(s->mpFile, "w");
-      if (!f) { printf("Error: cannot write %s\n", s->mpFile); exit(-1); }
-      fprintf(f, "# MullerPlathe: N %d axis %c bins %d every %d swaps %d startStep %d exchanges %d | columns: step, time (fs), kept pairs, skipped pairs, dE (eV), "
-                 "cumulative E (eV)\n", s->atoms->nGlobal, 'x' + s->mpAxis, s->mpBins, s->mpEvery, s->mpSwaps, s->mpStart, s->mpSamples);
-      for (int k = 0; k < s->mpSamples; ++k) {
-         const double* r = s->mpRows + 6 * (size_t)k;
-         fprintf(f, "%.0f %.17g %.0f %.0f %.17g %.17g\n", r[0], r[1], r[2], r[3], r[4], r[5]);
-      }
-      fclose(f);
-      if (yaml) {
-         const double E = s->mpExchanged - s->mpExchangedAtProfStart, time = samples ? (double)(s->profLastStep - s->profStart) * s->dt : 0.0;
-         const double area = samples ? s->profAreaSum / samples : 0.0;
-         double gradient = 0.0, kappa = 0.0;
-         const int rc = samples >= 2 ? comdFourierKappa(T, n, width, area, E, time, &gradient, &kappa) : -1;
-         fprintf(yaml, "MullerPlathe:\n");
-         fprintf(yaml, "  axis: %c\n  bins: %d\n  every: %d\n  swaps: %d\n  startStep: %d\n  file: %s\n", 'x' + s->mpAxis, s->mpBins, s->mpEvery, s->mpSwaps, s->mpStart, s->mpFile);
-         fprintf(yaml, "  exchanges: %lld\n  keptPairs: %lld\n  skippedPairs: %lld\n", s->mpExchanges, s->mpPairs, s->mpSkipped);
-         fprintf(yaml, "  exchangedSinceProfStart: %.12e\n  energyUnits: eV\n", E);
-         if (time > 0.0 && area > 0.0) fprintf(yaml, "  heatFlux: %.12e\n", E / (2.0 * area * time)); else fprintf(yaml, "  heatFlux: n/a\n");
-         fprintf(yaml, "  heatFluxUnits: eV/A^2/fs\n");
-         if (rc >= 0) fprintf(yaml, "  gradient: %.12e\n", gradient); else fprintf(yaml, "  gradient: n/a\n");
-         fprintf(yaml, "  gradientUnits: K/A\n");
-         if (rc == 0) fprintf(yaml, "  kappa: %.12e\n", kappa); else fprintf(yaml, "  kappa: n/a\n");
-         fprintf(yaml, "  kappaUnits: W/m/K\n\n");
-         fflush(yaml);
-      }
-   }
-   free(T);
-}
-
-/* --stress: one more row {step, mean / min / max hydrostatic pressure, mean / max von Mises stress, the gid of the max, N} from the device reduction (eV/A^3) */
-static void sampleStress(SimFlat* s, int iStep)
-{
-   double* row = (double*)nextRow(&s->stressRows, &s->stressCap, &s->stressSamples, 8, sizeof(double));
-   row[0] = (double)iStep;
-   if (comdStressSummary(s, 1, row + 1) != 0) { printf("Error: --stress needs the device state.\n"); exit(-1); }
-   s->stressMaxVmNow = row[5];
-}
-
-/* --stress: the file: a header line, then the rows of sampleStress in GPa.  --stressDump: the tensors of the last step as extended XYZ, Cu x y z sxx syy szz syz
- * sxz sxy vm gid in GPa (the tensor over the uniform atomic volume), the atoms whose von Mises stress is at least --stressDumpMin; the positions gathered by gid
- * over the ranks as the tensors are.  The YAML block names the file and gives the last sample's mean pressure and mean and max von Mises stress. */
-static void writeStress(FILE* yaml, SimFlat* s, int iStep)
-{
-   const size_t n = (size_t)s->atoms->nGlobal;
-   const double omega = (double)s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2] / (n ? (double)n : 1.0);
-   double *pos = NULL, *ten = NULL;
-   if (s->stressDump[0]) {          /* collective: before the other ranks leave */
-      pos = positionsByGid(s);
-      ten = (double*)malloc((n ? 6 * n : 1) * sizeof(double));
-      if (comdAtomStress(s, 1, ten) != 0) { printf("Error: --stressDump needs the device state.\n"); exit(-1); }
-   }
-   if (!printRank()) { free(pos); free(ten); return; }
-   const int samples = s->stressSamples;
-   FILE* f = fopen(s->stressFile, "w");
-   if (!f) { printf("Error: cannot write %s\n", s->stressFile); exit(-1); }
-   fprintf(f, "# Stress: N %d atomic volume %.17g A^3 (V / N of the last sample) samples %d | columns: step, mean / min / max hydrostatic pressure (GPa), "
-              "mean / max von Mises stress (GPa), gid of the max\n", s->atoms->nGlobal, omega, samples);
-   const double* last = NULL;
-   for (int k = 0; k < samples; ++k) {
-      last = s->stressRows + 8 * (size_t)k;
-      fprintf(f, "%.0f %.17g %.17g %.17g %.17g %.17g %.0f\n", last[0], last[1] * eVperA3inGPa, last[2] * eVperA3inGPa, last[3] * eVperA3inGPa,
-              last[4] * eVperA3inGPa, last[5] * eVperA3inGPa, last[6]);
-   }
-   fclose(f);
-   if (pos && ten) {
-      f = fopen(s->stressDump, "w");
-      if (!f) { printf("Error: cannot write %s\n", s->stressDump); exit(-1); }
-      const real_t* L = s->domain->globalExtent;
-      const double toGPa = eVperA3inGPa / omega;
-      double* vm = (double*)malloc((n ? n : 1) * sizeof(double));
-      size_t kept = 0;
-      for (size_t g = 0; g < n; ++g) {
-         const double* t = ten + 6 * g;
-         const double d0 = t[0] - t[1], d1 = t[1] - t[2], d2 = t[2] - t[0];
-         vm[g] = sqrt(0.5 * ((d0 * d0 + d1 * d1) + d2 * d2) + 3.0 * ((t[3] * t[3] + t[4] * t[4]) + t[5] * t[5])) * toGPa;
-         if (vm[g] >= s->stressDumpMin) kept++;
-      }
-      fprintf(f, "%zu\n", kept);
-      fprintf(f, "Lattice=\"%.17g 0 0 0 %.17g 0 0 0 %.17g\" Properties=species:S:1:pos:R:3:stress:R:6:vm:R:1:gid:I:1 step=%d units=GPa atomicVolume=%.17g minVM=%.17g\n",
-              (double)L[0], (double)L[1], (double)L[2], iStep, omega, s->stressDumpMin);
-      for (size_t g = 0; g < n; ++g)
-         if (vm[g] >= s->stressDumpMin) {
-            const double* t = ten + 6 * g;
-            fprintf(f, "Cu %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %zu\n", pos[3 * g], pos[3 * g + 1], pos[3 * g + 2],
-                    t[0] * toGPa, t[1] * toGPa, t[2] * toGPa, t[3] * toGPa, t[4] * toGPa, t[5] * toGPa, vm[g], g);
-         }
-      free(vm);
-      fclose(f);
-   }
-   free(pos); free(ten);
-   if (!yaml) return;
-   fprintf(yaml, "Stress:\n");
-   fprintf(yaml, "  Units: GPa\n");
-   fprintf(yaml, "  samples: %d\n", samples);
-   fprintf(yaml, "  file: %s\n", s->stressFile);
-   fprintf(yaml, "  finalMeanPressure: %.12e\n", last ? last[1] * eVperA3inGPa : 0.0);
-   fprintf(yaml, "  finalMeanVonMises: %.12e\n", last ? last[4] * eVperA3inGPa : 0.0);
-   fprintf(yaml, "  finalMaxVonMises: %.12e\n", last ? last[5] * eVperA3inGPa : 0.0);
-   fprintf(yaml, "\n");
-   fflush(yaml);
-}
-
-/* --strain: the state at the end of global step strainRef becomes the reference */
-static void startStrain(SimFlat* s)
-{
-   const int rc = comdStrainReference(s, 1);
-   if (rc < 0) { printf("Error: --strain needs the device state.\n"); exit(-1); }
-   if (rc > 0) { printf("Error: --strain: no device memory for the reference positions of %d atoms.\n", s->atoms->nGlobal); exit(-1); }
-}
-
-/* --strain: one more row {step, atoms, invalid atoms, mean / max shear strain, the gid of the max, mean volumetric strain, mean / max D^2min, atoms at or above
- * the threshold} from the device reduction */
-static void sampleStrain(SimFlat* s, int iStep)
-{
-   double* row = (double*)nextRow(&s->strainRows, &s->strainCap, &s->strainSamples, 10, sizeof(double));
-   row[0] = (double)iStep;
-   if (comdStrainSummary(s, s->strainCutoff, s->strainThreshold, row + 1) != 0) { printf("Error: --strain needs the device state and a reference.\n"); exit(-1); }
-   s->strainMaxShearNow = row[4];
-}
-
-static double shearOf(const double* e)
-{
-   const double d0 = e[0] - e[1], d1 = e[1] - e[2], d2 = e[2] - e[0];
-   return sqrt(((e[3] * e[3] + e[4] * e[4]) + e[5] * e[5]) + ((d0 * d0 + d1 * d1) + d2 * d2) / 6.0);
-}
-
-/* --strain: the file: a header line, then the rows of sampleStrain.  --strainDump: the tensors of the last step as extended XYZ, Cu x y z exx eyy ezz eyz exz
- * exy shear vol d2min n gid, the atoms whose shear strain is at least --strainDumpMin (0: all atoms, the invalid ones with their NaNs included); the positions
- * gathered by gid over the ranks as the tensors are.  The YAML block names the file and gives the last sample. */
-static void writeStrain(FILE* yaml, SimFlat* s, int iStep)
-{
-   const size_t n = (size_t)s->atoms->nGlobal;
-   double *pos = NULL, *ten = NULL;
-   int* cnt = NULL;
-   if (s->strainDump[0]) {          /* collective: before the other ranks leave */
-      pos = positionsByGid(s);
-      ten = (double*)malloc((n ? 7 * n : 1) * sizeof(double));
-      cnt = (int*)malloc((n ? n : 1) * sizeof(int));
-      if (comdAtomStrain(s, s->strainCutoff, ten, cnt) != 0) { printf("Error: --strainDump needs the device state and a reference.\n"); exit(-1); }
-   }
-   if (!printRank()) { free(pos); free(ten); free(cnt); return; }
-   const int samples = s->strainSamples;
-   FILE* f = fopen(s->strainFile, "w");
-   if (!f) { printf("Error: cannot write %s\n", s->strainFile); exit(-1); }
-   fprintf(f, "# Strain: N %d L0 %.17g %.17g %.17g reference step %d cutoff %.17g A threshold %.17g samples %d | columns: step, mean / max shear strain, "
-              "gid of the max, mean volumetric strain, mean / max D2min (A^2), atoms at or above the threshold, invalid atoms\n",
-           s->atoms->nGlobal, s->strainL0[0], s->strainL0[1], s->strainL0[2], s->strainRef, s->strainCutoff, s->strainThreshold, samples);
-   const double* last = NULL;
-   for (int k = 0; k < samples; ++k) {
-      last = s->strainRows + 10 * (size_t)k;
-      fprintf(f, "%.0f %.17g %.17g %.0f %.17g %.17g %.17g %.0f %.0f\n", last[0], last[3], last[4], last[5], last[6], last[7], last[8], last[9], last[2]);
-   }
-   fclose(f);
-   if (pos && ten) {
-      f = fopen(s->strainDump, "w");
-      if (!f) { printf("Error: cannot write %s\n", s->strainDump); exit(-1); }
-      const real_t* L = s->domain->globalExtent;
-      const int all = !(s->strainDumpMin > 0.0);
-      size_t kept = 0;
-      for (size_t g = 0; g < n; ++g) if (all || shearOf(ten + 7 * g) >= s->strainDumpMin) kept++;
-      fprintf(f, "%zu\n", kept);
-      fprintf(f, "Lattice=\"%.17g 0 0 0 %.17g 0 0 0 %.17g\" Properties=species:S:1:pos:R:3:strain:R:6:shear:R:1:vol:R:1:d2min:R:1:n:I:1:gid:I:1 step=%d "
-                 "referenceStep=%d cutoff=%.17g minShear=%.17g\n", (double)L[0], (double)L[1], (double)L[2], iStep, s->strainRef, s->strainCutoff, s->strainDumpMin);
-      for (size_t g = 0; g < n; ++g) {
-         const double* t = ten + 7 * g;
-         const double shear = shearOf(t);
-         if (all || shear >= s->strainDumpMin)
-            fprintf(f, "Cu %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %d %zu\n", pos[3 * g], pos[3 * g + 1], pos[3 * g + 2],
-                    t[0], t[1], t[2], t[3], t[4], t[5], shear, ((t[0] + t[1]) + t[2]) / 3.0, t[6], cnt[g], g);
-      }
-      fclose(f);
-   }
-   free(pos); free(ten); free(cnt);
-   if (!yaml) return;
-   fprintf(yaml, "Strain:\n");
-   fprintf(yaml, "  referenceStep: %d\n", s->strainRef);
-   fprintf(yaml, "  cutoff: %.12e\n", s->strainCutoff);
-   fprintf(yaml, "  threshold: %.12e\n", s->strainThreshold);
-   fprintf(yaml, "  samples: %d\n", samples);
-   fprintf(yaml, "  file: %s\n", s->strainFile);
-   fprintf(yaml, "  finalMeanShear: %.12e\n", last ? last[3] : 0.0);
-   fprintf(yaml, "  finalMaxShear: %.12e\n", last ? last[4] : 0.0);
-   fprintf(yaml, "  finalMeanVolumetric: %.12e\n", last ? last[6] : 0.0);
-   fprintf(yaml, "  finalMeanD2min: %.12e\n", last ? last[7] : 0.0);
-   fprintf(yaml, "  finalMaxD2min: %.12e\n", last ? last[8] : 0.0);
-   fprintf(yaml, "  finalAboveThreshold: %.0f\n", last ? last[9] : 0.0);
-   fprintf(yaml, "  finalInvalid: %.0f\n", last ? last[2] : 0.0);
-   fprintf(yaml, "\n");
-   fflush(yaml);
-}
-
-/* --heatflux: one more row {step, time, the nine sums of comdHeatFlux, temperature, volume}.  Only at a printed step are the per-atom energies those of the
- * current positions: timestep() asks the force kernels for them on its last step alone */
-static void sampleHeatFlux(SimFlat* s, int iStep)
-{
-   double* row = (double*)nextRow(&s->hfRows, &s->hfCap, &s->hfSamples, 13, sizeof(double));
-   row[0] = (double)iStep; row[1] = iStep * s->dt;
-   if (comdHeatFlux(s, row + 2) != 0) { printf("Error: --heatflux needs the device state.\n"); exit(-1); }
-   row[11] = (s->eKinetic / s->atoms->nGlobal) / (kB_eV * 1.5);
-   row[12] = (double)s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2];
-   s->hfJxNow = ((row[2] + row[5]) + row[8]) / row[12];
-}
-
-#define eVperFsAKinWperMK 1.602176634e6      /* 1 eV/(fs A K) in W/(m K) */
-
-/* --heatflux: the two files and the YAML block.  hfFile: a header with N, V, the time between samples, the start step and the number of samples, then per
- * sample the step, the time, J V = jk + jp + jv, its convective part jk + jp and its virial part jv (eV A/fs).  hfAcfFile: per lag k < M the time k dt, the
- * autocorrelation C_x, C_y, C_z of J V (comdHeatFluxAcf) and the running conductivity kappa(k) = dt trapezoid_0^k (C_x + C_y + C_z) / (3 V kB T^2) in W/(m K),
- * with T and V the means over the samples (V: the box may strain). */
-static void writeHeatFlux(FILE* yaml, SimFlat* s)
-{
-   if (!printRank()) return;
-   const int samples = s->hfSamples;
-   const double dtSample = (double)s->printRate * s->dt;
-   double meanT = 0.0, meanV = 0.0, meanJ[3] = { 0.0, 0.0, 0.0 };
-   double* jv = (double*)malloc((samples ? 3 * (size_t)samples : 1) * sizeof(double));
-   for (int k = 0; k < samples; ++k) {
-      const double* r = s->hfRows + 13 * (size_t)k;
-      for (int a = 0; a < 3; ++a) { jv[3 * (size_t)k + a] = (r[2 + a] + r[5 + a]) + r[8 + a]; meanJ[a] += jv[3 * (size_t)k + a]; }
-      meanT += r[11]; meanV += r[12];
-   }
-   if (samples) { meanT /= samples; meanV /= samples; for (int a = 0; a < 3; ++a) meanJ[a] /= samples; }
-   else meanV = (double)s->domain->globalExtent[0] * s->domain->globalExtent[1] * s->domain->globalExtent[2];
-   FILE* f = fopen(s->hfFile, "w");
-   if (!f) { printf("Error: cannot write %s\n", s->hfFile); exit(-1); }
-   fprintf(f, "# HeatFlux: N %d V %.17g A^3 (mean of the samples) dt %.17g fs between samples startStep %d samples %d | columns: step, time (fs), "
-              "J V x y z (eV A/fs), convective part x y z, virial part x y z\n", s->atoms->nGlobal, meanV, dtSample, s->hfStart, samples);
-   for (int k = 0; k < samples; ++k) {
-      const double* r = s->hfRows + 13 * (size_t)k;
-      fprintf(f, "%.0f %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", r[0], r[1], jv[3 * (size_t)k], jv[3 * (size_t)k + 1], jv[3 * (size_t)k + 2],
-              r[2] + r[5], r[3] + r[6], r[4] + r[7], r[8], r[9], r[10]);
-   }
-   fclose(f);
-   int window = s->hfWindow > 0 ? s->hfWindow : samples / 2;
-   const int clipped = window > samples;
-   if (clipped) window = samples;
-   if (window < 1) window = samples > 0 ? 1 : 0;
-   double* acf = (double*)malloc((3 * (size_t)window + 1) * sizeof(double));
-   if (window > 0) comdHeatFluxAcf(jv, samples, window, acf);
-   f = fopen(s->hfAcfFile, "w");
-   if (!f) { printf("Error: cannot write %s\n", s->hfAcfFile); exit(-1); }
-   fprintf(f, "# HeatFluxACF: N %d V %.17g A^3 T %.17g K (means of the samples) dt %.17g fs samples %d window %d%s | columns: lag time (fs), "
-              "C x y z of J V (eV^2 A^2/fs^2), running kappa (W/m/K)\n", s->atoms->nGlobal, meanV, meanT, dtSample, samples, window,
-           clipped ? " (clipped to the samples)" : "");
-   const double unit = meanT > 0.0 ? eVperFsAKinWperMK / (3.0 * meanV * kB_eV * meanT * meanT) : 0.0;
-   double integral = 0.0, kappa = 0.0;
-   for (int k = 0; k < window; ++k) {
-      const double* c = acf + 3 * (size_t)k;
-      if (k > 0) integral += 0.5 * (((c[-3] + c[-2]) + c[-1]) + ((c[0] + c[1]) + c[2])) * dtSample;
-      kappa = unit * integral;
-      fprintf(f, "%.17g %.17g %.17g %.17g %.17g\n", k * dtSample, c[0], c[1], c[2], kappa);
-   }
-   fclose(f);
-   free(acf); free(jv);
-   if (!yaml) return;
-   fprintf(yaml, "HeatFlux:\n");
-   fprintf(yaml, "  startStep: %d\n", s->hfStart);
-   fprintf(yaml, "  samples: %d\n", samples);
-   fprintf(yaml, "  window: %d\n", window);
-   fprintf(yaml, "  file: %s\n", s->hfFile);
-   fprintf(yaml, "  acfFile: %s\n", s->hfAcfFile);
-   fprintf(yaml, "  meanJV: [ %.12e, %.12e, %.12e ]\n", meanJ[0], meanJ[1], meanJ[2]);
-   fprintf(yaml, "  fluxUnits: eV A/fs\n");
-   if (samples >= 2) fprintf(yaml, "  kappa: %.12e\n", kappa); else fprintf(yaml, "  kappa: n/a\n");
-   fprintf(yaml, "  kappaUnits: W/m/K\n");
-   fprintf(yaml, "\n");
-   fflush(yaml);
 }
 
 Validate* initValidate(SimFlat* sim)
@@ -1152,6 +461,13 @@ void printSimulationDataYaml(FILE* file, SimFlat* s)
    fflush(file);
 }
 
+/* --deviceTimers, COMD_DEVICE_TIMERS=1: HIP-event timing of the phases of timestep() */
+static void useDeviceTimers(const Command* cmd, SimFlat* sim)
+{
+   if (cmd->deviceTimers || (getenv("COMD_DEVICE_TIMERS") && atoi(getenv("COMD_DEVICE_TIMERS")) != 0))
+      timersUseDevice(1, sim->gpu.boundary_stream, cmd->doeam ? 176.0 * sizeof(real_t) / 8.0 : 56.0 * sizeof(real_t) / 8.0);      /* force bytes per atom */
+}
+
 /* ---- the reference's main(), as a callable (CoMD.c:86-187) -------------------------------------------------- */
 int comdMain(int argc, char** argv)
 {
@@ -1165,8 +481,7 @@ int comdMain(int argc, char** argv)
    printCmdYaml(screenOut, &cmd);
 
    SimFlat* sim = initSimulation(cmd);
-   if (cmd.deviceTimers || (getenv("COMD_DEVICE_TIMERS") && atoi(getenv("COMD_DEVICE_TIMERS")) != 0))
-      timersUseDevice(1, sim->gpu.boundary_stream, cmd.doeam ? 176.0 * sizeof(real_t) / 8.0 : 56.0 * sizeof(real_t) / 8.0);      /* force bytes per atom */
+   useDeviceTimers(&cmd, sim);
    sumAtoms(sim);
    printSimulationDataYaml(yamlFile, sim);
    printSimulationDataYaml(screenOut, sim);
@@ -1181,59 +496,25 @@ int comdMain(int argc, char** argv)
       startTimer(commReduceTimer);
       sumAtoms(sim);
       stopTimer(commReduceTimer);
-      if (sim->pressure || sim->deformReport || sim->baroReport) { startTimer(pressureTimer); computePressure(sim); stopTimer(pressureTimer); }
-      if (sim->deformReport) sampleDeform(sim, iStep);
-      if (sim->rdfBins) { startTimer(rdfTimer); sampleRdf(sim); stopTimer(rdfTimer); }
-      if (sim->msd && iStep >= sim->msdStart) { startTimer(msdTimer); if (iStep == sim->msdStart) startMsd(sim); sampleMsd(sim, iStep); stopTimer(msdTimer); }
-      if (sim->csp) { startTimer(cspTimer); sampleCsp(sim, iStep); stopTimer(cspTimer); }
-      if (sim->cna) { startTimer(cnaTimer); sampleCna(sim, iStep); stopTimer(cnaTimer); }
-      if (sim->stress) { startTimer(stressTimer); sampleStress(sim, iStep); stopTimer(stressTimer); }
-      if (sim->strain && iStep >= sim->strainRef) { startTimer(strainTimer); if (iStep == sim->strainRef) startStrain(sim); sampleStrain(sim, iStep); stopTimer(strainTimer); }
-      if (sim->heatflux && iStep >= sim->hfStart) { startTimer(heatfluxTimer); sampleHeatFlux(sim, iStep); stopTimer(heatfluxTimer); }
-      if (sim->profile && iStep >= sim->profStart) { startTimer(profileTimer); sampleProfile(sim, iStep); stopTimer(profileTimer); }
+      reportsSample(sim, iStep);
       printThings(sim, iStep, getElapsedTime(timestepTimer));
-      /* --msdStart between two printed steps: the interval is taken as two timestep() calls (which give the bits of one) with the origin in between */
-      const int toOrigin = sim->msd && sim->msdStart > iStep && sim->msdStart < iStep + printRate ? sim->msdStart - iStep : 0;
-      /* --strainRef between two printed steps: the same, the reference taken in between */
-      const int toRef = sim->strain && sim->strainRef > iStep && sim->strainRef < iStep + printRate ? sim->strainRef - iStep : 0;
+      /* a report whose origin falls between two printed steps: the interval is taken as several timestep() calls (which give the bits of one) with the origin in between */
       startTimer(timestepTimer);
-      for (int done = 0; done < printRate;) {
-         int next = printRate;
-         if (toOrigin > done && toOrigin < next) next = toOrigin;
-         if (toRef > done && toRef < next) next = toRef;
+      for (int done = iStep, end = iStep + printRate; done < end;) {
+         const int next = reportsNextStart(sim, done, end);
          timestep(sim, next - done, sim->dt);
          done = next;
-         if (done == toOrigin) startMsd(sim);
-         if (done == toRef) startStrain(sim);
+         if (done < end) reportsStart(sim, done);
       }
       stopTimer(timestepTimer);
       iStep += printRate;
    }
    profileStop(loopTimer);
    sumAtoms(sim);
-   if (sim->pressure || sim->deformReport || sim->baroReport) { startTimer(pressureTimer); computePressure(sim); stopTimer(pressureTimer); }
-   if (sim->deformReport) sampleDeform(sim, iStep);
-   if (sim->rdfBins) { startTimer(rdfTimer); sampleRdf(sim); stopTimer(rdfTimer); }
-   if (sim->msd && iStep >= sim->msdStart) { startTimer(msdTimer); if (iStep == sim->msdStart) startMsd(sim); sampleMsd(sim, iStep); stopTimer(msdTimer); }
-   if (sim->csp) { startTimer(cspTimer); sampleCsp(sim, iStep); stopTimer(cspTimer); }
-   if (sim->cna) { startTimer(cnaTimer); sampleCna(sim, iStep); stopTimer(cnaTimer); }
-   if (sim->stress) { startTimer(stressTimer); sampleStress(sim, iStep); stopTimer(stressTimer); }
-   if (sim->strain && iStep >= sim->strainRef) { startTimer(strainTimer); if (iStep == sim->strainRef) startStrain(sim); sampleStrain(sim, iStep); stopTimer(strainTimer); }
-   if (sim->heatflux && iStep >= sim->hfStart) { startTimer(heatfluxTimer); sampleHeatFlux(sim, iStep); stopTimer(heatfluxTimer); }
-   if (sim->profile && iStep >= sim->profStart) { startTimer(profileTimer); sampleProfile(sim, iStep); stopTimer(profileTimer); }
+   reportsSample(sim, iStep);
    printThings(sim, iStep, getElapsedTime(timestepTimer));
    timestampBarrier("Ending simulation\n");
-   if (sim->pressure) printPressureYaml(yamlFile, sim);
-   if (sim->rdfBins) writeRdf(yamlFile, sim);
-   if (sim->msd) writeMsd(yamlFile, sim);
-   if (sim->csp) writeCsp(yamlFile, sim);
-   if (sim->cna) writeCna(yamlFile, sim);
-   if (sim->deformReport) writeDeform(yamlFile, sim);
-   if (sim->baroReport) writeBaro(yamlFile, sim);
-   if (sim->stress) { startTimer(stressTimer); writeStress(yamlFile, sim, iStep); stopTimer(stressTimer); }
-   if (sim->strain) { startTimer(strainTimer); writeStrain(yamlFile, sim, iStep); stopTimer(strainTimer); }
-   if (sim->heatflux) { startTimer(heatfluxTimer); writeHeatFlux(yamlFile, sim); stopTimer(heatfluxTimer); }
-   if (sim->profile) { startTimer(profileTimer); writeProfile(yamlFile, sim); stopTimer(profileTimer); }
+   reportsWrite(yamlFile, sim, iStep);
 
    validateResult(validate, sim);
    profileStop(totalTimer);
@@ -1251,8 +532,7 @@ SimFlat* comdCreate(int argc, char** argv)
 {
    Command cmd = parseCommandLine(argc, argv);
    SimFlat* sim = initSimulation(cmd);
-   if (cmd.deviceTimers || (getenv("COMD_DEVICE_TIMERS") && atoi(getenv("COMD_DEVICE_TIMERS")) != 0))
-      timersUseDevice(1, sim->gpu.boundary_stream, cmd.doeam ? 176.0 * sizeof(real_t) / 8.0 : 56.0 * sizeof(real_t) / 8.0);      /* force bytes per atom */
+   useDeviceTimers(&cmd, sim);
    sumAtoms(sim);
    return sim;
 }

@@ -148,8 +148,7 @@ static void baroCouple(SimFlat* s, real_t dt)
    s->baroPending = 1;
    deformListBudget(s);
    if (s->baroReport) {
-      if (s->baroSamples == s->baroCap) { s->baroCap = s->baroCap ? 2 * s->baroCap : 64; s->baroRows = (double*)realloc(s->baroRows, 12 * (size_t)s->baroCap * sizeof(double)); }
-      double* row = s->baroRows + 12 * (size_t)s->baroSamples++;
+      double* row = (double*)nextRow(&s->baroRows, 12 * sizeof(double));
       row[0] = (double)(s->stepCount + 1); row[1] = row[0] * (double)dt;
       for (int a = 0; a < 3; ++a) { row[2 + a] = p[a]; row[5 + a] = mu[a]; row[8 + a] = s->baroAxes >> a & 1 ? s->baroNext[a] : (double)s->domain->globalExtent[a]; }
       row[11] = row[8] * row[9] * row[10];
@@ -182,8 +181,7 @@ static void mpExchange(SimFlat* s, real_t dt)
    /* --mp: the energy of the exchanges up to global step profStart is not part of the flux the profile answers */
    if (s->profile && s->stepCount + 1 <= (uint64_t)s->profStart) s->mpExchangedAtProfStart = s->mpExchanged;
    if (s->mpReport) {
-      if (s->mpSamples == s->mpCap) { s->mpCap = s->mpCap ? 2 * s->mpCap : 64; s->mpRows = (double*)realloc(s->mpRows, 6 * (size_t)s->mpCap * sizeof(double)); }
-      double* row = s->mpRows + 6 * (size_t)s->mpSamples++;
+      double* row = (double*)nextRow(&s->mpRows, 6 * sizeof(double));
       row[0] = (double)(s->stepCount + 1); row[1] = row[0] * (double)dt; row[2] = (double)kept; row[3] = (double)skipped; row[4] = dE; row[5] = s->mpExchanged;
    }
 }
