@@ -1,5 +1,5 @@
 // analysis_launch.h -- the launch layer of the analyses, computeVirial ... comdMullerPlatheApplyGpu (comd_hip.h): none of them is in the reference.  Host code,
-// part of comd_device.hip's translation unit (it uses HIP_CHECK, LAUNCH_CHECK, S, dalloc, allowDynamicLds, ceilDiv, makeLjArgs and ljTableView of that file).
+// part of comd_device.hip's translation unit (it uses HIP_CHECK, LAUNCH_CHECK, S, dalloc, allowDynamicLds, ceilDiv, of that file, makeLjArgs and ljTableView of lj_launch.h).
 #pragma once
 
 // The entry points of the chunk walk (stencil_walk.h) share their prologue and the fields of the walk.

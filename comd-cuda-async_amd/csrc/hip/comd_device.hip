@@ -679,282 +679,11 @@ extern "C" int comdReadDeviceInt(const int* d_ptr, comdStream_t stream)
 }
 
 // ---- force -------------------------------------------------------------------------------------------------------
-static NlView nlView(SimGpu* sim)
-{
-   NeighborListGpu* n = &sim->atoms.neighborList;
-   if (!n->list && !n->list16) { fprintf(stderr, "the *_nl methods need Verlet lists: allocate with GpuConfig.skinDistance > 0\n"); exit(-1); }
-   if (n->nBuilds == 0) { fprintf(stderr, "the *_nl methods need buildNeighborListGpu before the first force call\n"); exit(-1); }
-   NlView v; v.list = n->list; v.count = n->nNeighbors; v.maxNbr = n->maxNeighbors;
-   return v;
-}
-
-static LjArgs makeLjArgs(SimGpu* sim, int num_cells, int* cells_list)
-{
-   LjArgs a;
-   a.rx = sim->atoms.r.x; a.ry = sim->atoms.r.y; a.rz = sim->atoms.r.z;
-   a.fx = sim->atoms.f.x; a.fy = sim->atoms.f.y; a.fz = sim->atoms.f.z; a.e = sim->atoms.e;
-   a.nAtoms = sim->boxes.nAtoms; a.nbr = sim->neighbor_cells; a.cells = cells_list;
-   a.nCells = num_cells; a.cap = sim->maxAtoms;
-   const double sigma = sim->lj_pot.sigma, rc = sim->lj_pot.cutoff;
-   a.rc2 = rc * rc;
-   a.s6 = sigma * sigma * sigma * sigma * sigma * sigma;
-   a.s6x2 = 2.0 * (sigma * sigma * sigma * sigma * sigma * sigma);
-   const double rc6 = a.s6 / (a.rc2 * a.rc2 * a.rc2);
-   a.eShift = rc6 * (rc6 - 1.0);                 // POT_SHIFT 1.0
-   a.eps = sim->lj_pot.epsilon;
-   return a;
-}
-
 // Per-atom energies are consumed only by computeEnergy.  The host announces with comdSetEnergyNeeded(0) that the coming
 // force evaluations feed no energy read (all but the last step of a timestep() call); the default is 1 (always compute).
 extern "C" void comdSetEnergyNeeded(SimGpu* sim, int on) { sim->needEnergy = on; }
 
-// Margins of the point-to-box pruning test (LJ_WaveCandidates, LJ_Force_cta_cell_boxes): the test may keep a candidate it need not, never drop one a
-// lane would accept.  A relative margin on rc^2 and on the half widths covers the arithmetic of the distance; the box CENTRE is formed from absolute
-// coordinates, whose ulp grows with the box (float: 3e-5 A at 289 A, 1.2e-4 A beyond 1024 A -- ADVICE r2), so the cutoff is also pushed out by eight
-// ulps of the largest coordinate this rank can see (local domain + one halo cell), per axis.
-static void ljBoxMargins(const SimGpu* sim, real_t rc2, real_t* rc2Box, real_t* grow)
-{
-   const double rel = sizeof(real_t) == 8 ? 1e-12 : 1e-5, eps = sizeof(real_t) == 8 ? 2.220446049250313e-16 : 1.1920929e-07;
-   double big = 0.0;
-   for (int a = 0; a < 3; ++a) {
-      const double cellW = 1.0 / sim->boxes.invBoxSize[a];
-      const double lo = fabs((double)sim->boxes.localMin[a] - cellW), hi = fabs((double)sim->boxes.localMax[a] + cellW);
-      if (lo > big) big = lo;
-      if (hi > big) big = hi;
-   }
-   const double rc = sqrt((double)rc2) * (1.0 + rel) + 8.0 * 1.7320508 * eps * big;
-   *rc2Box = (real_t)(rc * rc);
-   *grow = (real_t)(1.0 + rel);
-}
-
-// The list build of thread_atom (LJ_WaveCandidates) makes the same test in SINGLE precision on positions relative to the corner of the local domain
-// (LJ_PackPositions): the conversion moves a coordinate by half an ulp of the largest relative coordinate (local domain + one halo cell on either side),
-// the arithmetic of the box distance is good to ~1e-6 relative -- the cutoff is pushed out by 1e-5 relative + eight such ulps per axis.
-static void ljBoxMarginsF(const SimGpu* sim, real_t rc2, float* rc2Box, float* grow)
-{
-   const double rel = 1e-5, eps = 1.1920929e-07;
-   double big = 0.0;
-   for (int a = 0; a < 3; ++a) {
-      const double ext = (double)sim->boxes.localMax[a] - (double)sim->boxes.localMin[a] + 2.0 / sim->boxes.invBoxSize[a];
-      if (ext > big) big = ext;
-   }
-   const double rc = sqrt((double)rc2) * (1.0 + rel) + 8.0 * 1.7320508 * eps * big;
-   *rc2Box = (float)(rc * rc * (1.0 + 2.0 * eps));
-   *grow = (float)(1.0 + rel);
-}
-
-// The grid and the candidate lists of a thread_atom force call, shared by the analytic and the table kernel
-struct LjThreadAtomLaunch { int w, wavesPerBlock; unsigned nBlocks; bool prune; LjWaveLists wl; };
-
-// thread_atom (the BASELINE-named kernel): candidate lists (launched here), and the grid the force kernel needs
-static LjThreadAtomLaunch prepareLjThreadAtom(SimGpu* sim, const LjArgs& a, int num_cells, int* cells_list, comdStream_t stream)
-{
-   // Measured on MI355X (LJ 80^3): a workgroup of the 3 live waves per cell runs the kernel in 3.94 ms, cap/64 = 4 waves per cell (the
-   // tail wave exits at once) in 4.72 ms, single-wave workgroups in 5.64 ms.
-   // waves per cell: sized to the occupancy the host last saw (+16 atoms of slack), never more than cap/64.  Cells that outgrow the
-   // estimate stay correct (their waves take extra chunks).  COMD_LJ_WAVES=k forces k (tests use 1 to exercise the extra-chunk path).
-   int w = sim->maxAtoms / 64;
-   if (sim->max_atoms_cell > 0 && (sim->max_atoms_cell + 16 + 63) / 64 < w) w = (sim->max_atoms_cell + 16 + 63) / 64;
-   const ComdTuning& tune = tuningOf(sim);
-   if (tune.ljWaves && tune.ljWaves < w) w = tune.ljWaves;
-   const int wavesPerBlock = w <= 4 ? w : 4;
-   const unsigned nBlocks = w <= 4 ? (unsigned)num_cells : (unsigned)ceilDiv((long)num_cells * w, 4);
-   // candidate lists of the waves (lj_kernels.h): rows sized for 70 % of the fullest stencil the host has seen -- the part of 27 cells
-   // within the cutoff of a whole cell's box is 76 %, of a 64-atom slab of it 61 % -- and a wave whose row is too short walks the stencil.
-   // COMD_LJ_PRUNE=0 switches the lists off (A/B measurements); COMD_LJ_LIST_CAP=n forces rows of n entries (tests: the fallback).
-   const bool pruneEnv = tune.ljPrune;
-   LjPotentialGpu* lj = &sim->lj_pot;
-   if (pruneEnv && !lj->waveCand && lj->packedCap == 0) {
-      // the fullest cell right now (one blocking read, once per simulation; SimGpu.max_atoms_cell may not have been filled in yet)
-      std::vector<int> counts((size_t)sim->boxes.nTotalBoxes);
-      HIP_CHECK(hipMemcpyAsync(counts.data(), sim->boxes.nAtoms, counts.size() * sizeof(int), hipMemcpyDeviceToHost, S(stream)));
-      HIP_CHECK(hipStreamSynchronize(S(stream)));
-      int fullest = sim->max_atoms_cell;
-      for (int c : counts) if (c > fullest) fullest = c;
-      const int occ = fullest + 16 < sim->maxAtoms ? fullest + 16 : sim->maxAtoms;
-      lj->waveCandWaves = w;
-      lj->waveCandCap = ((int)(0.70 * 27 * occ) + 7) & ~7;
-      if (tune.ljListCap) lj->waveCandCap = tune.ljListCap;
-      lj->packedCap = ((occ + 7) & ~7) < sim->maxAtoms ? ((occ + 7) & ~7) : sim->maxAtoms;     // a stencil with a fuller cell falls back to the walk
-      // list entries are 32-bit byte offsets into the packed records
-      // ~250 B of list per atom (18 GB at 256^3) + the packed records (2.9 GB each): when that does not fit what the device has free (keeping 2 GB
-      // for everything allocated later), or the 32-bit offsets cannot reach the records, this simulation walks the stencil as round 1 did
-      const double listBytes = (double)sim->boxes.nLocalBoxes * lj->waveCandWaves * lj->waveCandCap * 4.0 + (double)sim->boxes.nLocalBoxes * lj->waveCandWaves * 8.0
-                               + (sim->interior_stream ? 2.0 : 1.0) * (double)sim->boxes.nTotalBoxes * lj->packedCap * (sizeof(LjPos4) + sizeof(float4));
-      size_t freeB = 0, totalB = 0;
-      HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
-      if ((double)sim->boxes.nTotalBoxes * lj->packedCap * sizeof(LjPos4) >= 4294967296.0) lj->packedCap = -1;     // no lists for this simulation
-      else if (listBytes + 2.0e9 > (double)freeB || listBytes > 1.0e6 * tune.ljListBudgetMb) {
-         fprintf(stderr, "Rank %d: LJ candidate lists need %.1f GB, %.1f GB are free: running without them (the plain 27-cell walk, ~1.4x slower)\n",
-                 g_rank, listBytes / 1e9, (double)freeB / 1e9);
-         lj->packedCap = -1;
-      } else {
-         // Everything the lists need is allocated HERE, and a refusal is not fatal: ranks that share a device can all see the memory free and then not all
-         // get it -- whoever is refused runs the plain walk, and says so (bench.py records force_path.lj_candidate_lists_active).
-         auto tryAlloc = [](size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 8) != hipSuccess) { (void)hipGetLastError(); p = nullptr; } return p; };
-         const size_t recs = (size_t)sim->boxes.nTotalBoxes * lj->packedCap * 4;
-         lj->waveCand = (unsigned*)tryAlloc((size_t)sim->boxes.nLocalBoxes * lj->waveCandWaves * lj->waveCandCap * sizeof(unsigned));
-         lj->waveCandCount = (int*)tryAlloc((size_t)sim->boxes.nLocalBoxes * lj->waveCandWaves * 2 * sizeof(int));
-         bool ok = lj->waveCand && lj->waveCandCount;
-         for (int k = 0; k < (sim->interior_stream ? 2 : 1) && ok; ++k) {
-            lj->packedR[k] = (real_t*)tryAlloc(recs * sizeof(real_t));
-            lj->packedF[k] = (float*)tryAlloc(recs * sizeof(float));
-            ok = lj->packedR[k] && lj->packedF[k];
-         }
-         if (!ok) {
-            void* ps[6] = { lj->waveCand, lj->waveCandCount, lj->packedR[0], lj->packedF[0], lj->packedR[1], lj->packedF[1] };
-            for (void* q : ps) if (q) (void)hipFree(q);
-            lj->waveCand = nullptr; lj->waveCandCount = nullptr; lj->packedR[0] = lj->packedR[1] = nullptr; lj->packedF[0] = lj->packedF[1] = nullptr;
-            fprintf(stderr, "Rank %d: the device refused the %.1f GB of the LJ candidate lists: running without them (the plain 27-cell walk, ~1.4x slower)\n", g_rank, listBytes / 1e9);
-            lj->packedCap = -1;
-         }
-      }
-   }
-   const bool prune = pruneEnv && lj->waveCand;
-   LjWaveLists wl; memset(&wl, 0, sizeof wl);
-   if (prune) {
-      // the force may be split over two streams (-a 1: interior cells while the halo exchange is in flight, boundary cells after it):
-      // each stream packs the positions it is about to read into its own array
-      const int which = (cells_list && stream != sim->interior_stream) ? 1 : 0;
-      if (!lj->packedR[which]) {
-         lj->packedR[which] = dalloc<real_t>((size_t)sim->boxes.nTotalBoxes * lj->packedCap * 4, false);
-         lj->packedF[which] = dalloc<float>((size_t)sim->boxes.nTotalBoxes * lj->packedCap * 4, false);
-      }
-      wl.cand = lj->waveCand; wl.pos = (const LjPos4*)lj->packedR[which]; wl.posF = (const float4*)lj->packedF[which]; wl.count = (int2*)lj->waveCandCount;
-      wl.candCap = lj->waveCandCap; wl.wavesMax = lj->waveCandWaves; wl.capP = lj->packedCap;
-      ljBoxMarginsF(sim, a.rc2, &wl.rc2BoxF, &wl.growF);
-      // interior cells never have a halo cell in their stencil, and the halo cells are being filled while they run
-      const int packCells = (cells_list && stream == sim->interior_stream) ? sim->boxes.nLocalBoxes : sim->boxes.nTotalBoxes;
-      ForceTimer aux(sim, S(stream), 1);               // the list build of this evaluation (bench.py: force_evaluation_ms = kernel + this)
-      hipLaunchKernelGGL(LJ_PackPositions, dim3((unsigned)ceilDiv((long)packCells * lj->packedCap, 256)), dim3(256), 0, S(stream),
-                         a.rx, a.ry, a.rz, a.nAtoms, (LjPos4*)lj->packedR[which], (float4*)lj->packedF[which], a.cap, lj->packedCap, packCells, a.rc2,
-                         sim->boxes.localMin[0], sim->boxes.localMin[1], sim->boxes.localMin[2]);
-      hipLaunchKernelGGL(LJ_WaveCandidates, dim3((unsigned)ceilDiv(num_cells, 4)), dim3(256), 0, S(stream), a, wl, w);
-   }
-   LjThreadAtomLaunch L; L.w = w; L.wavesPerBlock = wavesPerBlock; L.nBlocks = nBlocks; L.prune = prune; L.wl = wl;
-   return L;
-}
-
-static TableView ljTableView(const SimGpu* sim)
-{
-   const InterpolationObjectGpu& t = sim->lj_pot.lj_interpolation;
-   TableView tv; tv.v = t.values; tv.x0 = t.x0; tv.xn = t.xn; tv.invDx = t.invDx; tv.invDxHalf = t.invDxHalf; tv.invDxXx0 = t.invDxXx0;
-   return tv;
-}
-
-// table: the -I kernel (lj_table_kernels.h) on the same grid and lists
-static void launchLjThreadAtom(SimGpu* sim, const LjArgs& a, int num_cells, int* cells_list, comdStream_t stream, bool table)
-{
-   const LjThreadAtomLaunch L = prepareLjThreadAtom(sim, a, num_cells, cells_list, stream);
-   const int w = L.w, wavesPerBlock = L.wavesPerBlock;
-   const unsigned nBlocks = L.nBlocks;
-   const bool prune = L.prune;
-   const LjWaveLists& wl = L.wl;
-   const bool prefetch = prune && !table && tuningOf(sim).ljPrefetch;      // (the -I kernel has a list loop of its own, without the prefetch)
-   { ForceLegs& legs = legsOf(sim); legs.ljWaves = w; legs.ljLists = prune; legs.ljListCap = prune ? wl.candCap : 0; legs.ljPrefetch = prefetch; }
-   ForceTimer timer(sim, S(stream));                     // the force kernel proper (bench.py's roofline line; rocprof must agree with it)
-   if (table) {
-      const TableView tv = ljTableView(sim);
-#define LAUNCH_TABLE(E, LISTED) hipLaunchKernelGGL((LJ_Force_thread_atom_table<E, LISTED>), dim3(nBlocks), dim3(64 * wavesPerBlock), 0, S(stream), a, w, wl, tv)
-      if (prune) { if (sim->needEnergy) LAUNCH_TABLE(true, true);  else LAUNCH_TABLE(false, true); }
-      else       { if (sim->needEnergy) LAUNCH_TABLE(true, false); else LAUNCH_TABLE(false, false); }
-#undef LAUNCH_TABLE
-   } else {
-#define LAUNCH_LJ(K) hipLaunchKernelGGL((K), dim3(nBlocks), dim3(64 * wavesPerBlock), 0, S(stream), a, w, wl)
-      if (prefetch)   { if (sim->needEnergy) LAUNCH_LJ((LJ_Force_thread_atom<true, true>));   else LAUNCH_LJ((LJ_Force_thread_atom<false, true>)); }
-      else if (prune) { if (sim->needEnergy) LAUNCH_LJ(LJ_Force_thread_atom_plain<true>);     else LAUNCH_LJ(LJ_Force_thread_atom_plain<false>); }
-      else            { if (sim->needEnergy) LAUNCH_LJ((LJ_Force_thread_atom<true, false>));  else LAUNCH_LJ((LJ_Force_thread_atom<false, false>)); }
-#undef LAUNCH_LJ
-   }
-   LAUNCH_CHECK();
-}
-
-// table: -I (lj_pot.lj_interpolation), thread_atom and both list formats of thread_atom_nl
-static void ljForce(SimGpu* sim, int num_cells, int* cells_list, int method, comdStream_t stream, bool table)
-{
-   if (num_cells <= 0) return;
-   LjArgs a = makeLjArgs(sim, num_cells, cells_list);
-   if (table) {
-      if (!sim->lj_pot.lj_interpolation.values) { fprintf(stderr, "ljForceGpu: interpolation requested but there is no LJ table: call initLJinterpolation first\n"); exit(-1); }
-      if (method == CTA_CELL) { fprintf(stderr, "ljForceGpu: interpolated LJ (-I) runs with thread_atom and thread_atom_nl, not cta_cell\n"); exit(-1); }
-   }
-   if (method != THREAD_ATOM_NL && method != WARP_ATOM_NL && method != CTA_CELL) { launchLjThreadAtom(sim, a, num_cells, cells_list, stream, table); return; }
-   ForceTimer timer(sim, S(stream));
-   if ((method == THREAD_ATOM_NL || method == WARP_ATOM_NL) && sim->atoms.neighborList.slabFormat) {
-      NeighborListGpu* n = &sim->atoms.neighborList;
-      (void)nlView(sim);
-      NlSlabView v; v.list = n->list16; v.count = n->nNeighbors; v.rows = n->slabRows;
-      const int threads = ((n->maxCellAtoms + 63) / 64) * 64;
-      const size_t lds = (size_t)3 * n->maxSlabAtoms * sizeof(real_t);
-      if (table) {
-         const TableView tv = ljTableView(sim);
-         allowDynamicLds((const void*)LJ_Force_nl_slabs_table<true>, lds);
-         allowDynamicLds((const void*)LJ_Force_nl_slabs_table<false>, lds);
-         if (sim->needEnergy) hipLaunchKernelGGL(LJ_Force_nl_slabs_table<true>, dim3(num_cells), dim3(threads), lds, S(stream), a, v, n->maxSlabAtoms, tv);
-         else              hipLaunchKernelGGL(LJ_Force_nl_slabs_table<false>, dim3(num_cells), dim3(threads), lds, S(stream), a, v, n->maxSlabAtoms, tv);
-         LAUNCH_CHECK();
-         return;
-      }
-      allowDynamicLds((const void*)LJ_Force_nl_slabs<true>, lds);
-      allowDynamicLds((const void*)LJ_Force_nl_slabs<false>, lds);
-      if (sim->needEnergy) hipLaunchKernelGGL(LJ_Force_nl_slabs<true>, dim3(num_cells), dim3(threads), lds, S(stream), a, v, n->maxSlabAtoms);
-      else              hipLaunchKernelGGL(LJ_Force_nl_slabs<false>, dim3(num_cells), dim3(threads), lds, S(stream), a, v, n->maxSlabAtoms);
-   } else if (method == THREAD_ATOM_NL || method == WARP_ATOM_NL) {
-      const NlView nl = nlView(sim);
-      const unsigned nBlocks = (unsigned)ceilDiv((long)num_cells * sim->maxAtoms, 256);
-      if (table) {
-         const TableView tv = ljTableView(sim);
-         if (sim->needEnergy) hipLaunchKernelGGL(LJ_Force_thread_atom_nl_table<true>, dim3(nBlocks), dim3(256), 0, S(stream), a, nl, tv);
-         else              hipLaunchKernelGGL(LJ_Force_thread_atom_nl_table<false>, dim3(nBlocks), dim3(256), 0, S(stream), a, nl, tv);
-      }
-      else if (sim->needEnergy) hipLaunchKernelGGL(LJ_Force_thread_atom_nl<true>, dim3(nBlocks), dim3(256), 0, S(stream), a, nl);
-      else              hipLaunchKernelGGL(LJ_Force_thread_atom_nl<false>, dim3(nBlocks), dim3(256), 0, S(stream), a, nl);
-   } else if (method == CTA_CELL) {
-      const size_t lds = ljCtaLdsBytes(sim->maxAtoms);
-      allowDynamicLds((const void*)LJ_Force_cta_cell<0, true>, lds); allowDynamicLds((const void*)LJ_Force_cta_cell<0, false>, lds);
-      allowDynamicLds((const void*)LJ_Force_cta_cell<1, true>, lds); allowDynamicLds((const void*)LJ_Force_cta_cell<1, false>, lds);
-      allowDynamicLds((const void*)LJ_Force_cta_cell<2, true>, lds); allowDynamicLds((const void*)LJ_Force_cta_cell<2, false>, lds);
-      // threads = atoms of the fullest cell the host has seen (+16), rounded to whole waves, at most 256; each thread can own two atoms
-      int threads = sim->maxAtoms < 256 ? sim->maxAtoms : 256;
-      // (not with pairlists: their bits are per wave, so the thread -> atom map must not change between the generating call and the users)
-      if (sim->atoms.neighborList.slabFormat != 3 && sim->max_atoms_cell > 0 && ((sim->max_atoms_cell + 16 + 63) / 64) * 64 < threads)
-         threads = ((sim->max_atoms_cell + 16 + 63) / 64) * 64;
-      if (sim->maxAtoms > 2 * threads) { fprintf(stderr, "ljForceGpu: cta_cell supports at most 512 atoms per cell\n"); exit(-1); }
-      NeighborListGpu* n = &sim->atoms.neighborList;
-      LjPairlist pl; pl.words = n->pairlist; pl.wavesMax = n->pairlistWaves;
-      pl.plCut2 = (sim->lj_pot.cutoff + n->skinDistance) * (sim->lj_pot.cutoff + n->skinDistance);
-#define LAUNCH_CTA(PLV) do { if (sim->needEnergy) hipLaunchKernelGGL((LJ_Force_cta_cell<PLV, true>), dim3(num_cells), dim3(threads), lds, S(stream), a, sim->status, pl); \
-                            else              hipLaunchKernelGGL((LJ_Force_cta_cell<PLV, false>), dim3(num_cells), dim3(threads), lds, S(stream), a, sim->status, pl); } while (0)
-      legsOf(sim).ljCtaForm = n->slabFormat == 3 ? 3 : tuningOf(sim).ljCtaSlabs ? 2 : 1;
-      if (n->slabFormat != 3 && !tuningOf(sim).ljCtaSlabs) {
-         // the default form: every wave stages its own box-pruned candidates (COMD_LJ_CTA_SLABS=1: the slab kernel, for A/B runs)
-         real_t rc2Box, grow;
-         ljBoxMargins(sim, a.rc2, &rc2Box, &grow);
-         const size_t ldsB = ljCtaBoxesLdsBytes(threads);
-         if (sim->needEnergy) hipLaunchKernelGGL(LJ_Force_cta_cell_boxes<true>, dim3(num_cells), dim3(threads), ldsB, S(stream), a, rc2Box, grow);
-         else                 hipLaunchKernelGGL(LJ_Force_cta_cell_boxes<false>, dim3(num_cells), dim3(threads), ldsB, S(stream), a, rc2Box, grow);
-      }
-      else if (n->slabFormat != 3)               LAUNCH_CTA(0);
-      else if (n->nBuilds == 0) { fprintf(stderr, "ljForceGpu: -L needs buildNeighborListGpu before the first force call\n"); exit(-1); }
-      else if (n->pairlistBuildId != n->nBuilds) LAUNCH_CTA(1);
-      else                                       LAUNCH_CTA(2);
-#undef LAUNCH_CTA
-   }
-   LAUNCH_CHECK();
-}
-
-extern "C" void ljForceGpuAsync(SimGpu* sim, int num_cells, int* cells_list, int method, comdStream_t stream)
-{
-   ljForce(sim, num_cells, cells_list, method, stream, sim->lj_pot.lj_interpolation.values != nullptr);
-}
-
-extern "C" void ljForceGpu(SimGpu* sim, int interpolation, int num_cells, int* cells_list, real_t plcutoff, int method)
-{
-   (void)plcutoff;
-   ljForce(sim, num_cells, cells_list, method, nullptr, interpolation != 0);
-}
-
+#include "lj_launch.h"       // the LJ launch layer: nlView, makeLjArgs ... ljForceGpu
 #include "eam_launch.h"      // the EAM launch layer: makeEamArgs ... eamForce3Gpu
 
 // what the force wrappers decided for this simulation (bench.py records it beside the numbers): {LJ thread_atom candidate lists in use (0: the 27-cell walk),

@@ -41,9 +41,31 @@ __device__ __forceinline__ void ljPair(real_t dx, real_t dy, real_t dz, real_t r
 }
 #define LJ_FORCE_SCALE(a) (R(24.0) * (a).eps * (a).s6)
 
+// The pair policy P of the thread_atom and Verlet-list kernels (here and in nl_kernels.h): what is done with an accepted pair, and how an atom's sums are
+// stored.  Everything else in those kernels -- the walks, the lists, the replicated tail wave -- is the same for every pair function.
+//    pr.pair<ENERGY>(a, dx, dy, dz, r2, fx, fy, fz, e)     one accepted pair
+//    pr.store<ENERGY>(a, iOff, fx, fy, fz, e)              the final store of one atom
+//    pr.r2ExtraChunk(dx, dy, dz)                           r^2 in the extra chunks of thread_atom (ljChunkGeneric<P, ENERGY, true>): see LjTablePair
+// LjAnalyticPair is ljPair with its constant factors applied at the store; LjTablePair (lj_table_kernels.h) is the -I table.
+struct LjAnalyticPair {
+   template <bool ENERGY>
+   __device__ __forceinline__ void pair(const LjArgs& a, real_t dx, real_t dy, real_t dz, real_t r2, real_t& fx, real_t& fy, real_t& fz, real_t& e) const
+   {
+      ljPair<ENERGY>(dx, dy, dz, r2, a, fx, fy, fz, e);
+   }
+   __device__ __forceinline__ real_t r2ExtraChunk(real_t dx, real_t dy, real_t dz) const { return dx*dx + dy*dy + dz*dz; }
+   template <bool ENERGY>
+   __device__ __forceinline__ void store(const LjArgs& a, size_t iOff, real_t fx, real_t fy, real_t fz, real_t e) const
+   {
+      const real_t fs = LJ_FORCE_SCALE(a);
+      a.fx[iOff] = fx * fs; a.fy[iOff] = fy * fs; a.fz[iOff] = fz * fs;
+      if (ENERGY) a.e[iOff] = e * R(2.0) * a.eps;          // 4 eps * 1/2 per pair
+   }
+};
+
 // one neighbour cell against the wave's 64 i atoms; SELF adds the r2 > 0 guard of the own cell
-template <bool SELF, bool ENERGY>
-__device__ __forceinline__ void ljCellLoop(const LjArgs& a, int jBox, real_t xi, real_t yi, real_t zi,
+template <class P, bool SELF, bool ENERGY>
+__device__ __forceinline__ void ljCellLoop(const P& pr, const LjArgs& a, int jBox, real_t xi, real_t yi, real_t zi,
                                            real_t& fx, real_t& fy, real_t& fz, real_t& e)
 {
    const int nj = uniform(a.nAtoms[jBox]);
@@ -61,14 +83,14 @@ __device__ __forceinline__ void ljCellLoop(const LjArgs& a, int jBox, real_t xi,
          real_t dx = xi - xs[u], dy = yi - ys[u], dz = zi - zs[u];
          real_t r2 = dx*dx + dy*dy + dz*dz;
          bool hit = SELF ? (r2 <= a.rc2 && r2 > R(0.0)) : (r2 <= a.rc2);
-         if (hit) ljPair<ENERGY>(dx, dy, dz, r2, a, fx, fy, fz, e);
+         if (hit) pr.template pair<ENERGY>(a, dx, dy, dz, r2, fx, fy, fz, e);
       }
    }
    for (; j < nj; ++j) {
       real_t dx = xi - px[j], dy = yi - py[j], dz = zi - pz[j];
       real_t r2 = dx*dx + dy*dy + dz*dz;
       bool hit = SELF ? (r2 <= a.rc2 && r2 > R(0.0)) : (r2 <= a.rc2);
-      if (hit) ljPair<ENERGY>(dx, dy, dz, r2, a, fx, fy, fz, e);
+      if (hit) pr.template pair<ENERGY>(a, dx, dy, dz, r2, fx, fy, fz, e);
    }
 }
 
@@ -99,8 +121,8 @@ struct LjWaveLists {
 // soffset form, no address arithmetic per candidate)
 __device__ __forceinline__ LjPos4 atByte(const LjPos4* __restrict__ base, unsigned byteOff) { return *(const LjPos4*)((const char*)base + byteOff); }
 
-template <bool SELF, bool ENERGY>
-__device__ __forceinline__ void ljListTest(const LjArgs& a, const LjPos4& q, real_t xi, real_t yi, real_t zi, real_t& fx, real_t& fy, real_t& fz, real_t& e)
+template <class P, bool SELF, bool ENERGY>
+__device__ __forceinline__ void ljListTest(const P& pr, const LjArgs& a, const LjPos4& q, real_t xi, real_t yi, real_t zi, real_t& fx, real_t& fy, real_t& fz, real_t& e)
 {
    real_t dx = xi - q.x, dy = yi - q.y, dz = zi - q.z;
    // r^2 = dx dx + dy dy + dz dz with its roundings written out.  Left to -ffp-contract=fast, hipcc fused it one way in the float kernel without the
@@ -116,7 +138,7 @@ __device__ __forceinline__ void ljListTest(const LjArgs& a, const LjPos4& q, rea
 #endif
    }
    bool hit = SELF ? (r2 <= q.rc2 && r2 > R(0.0)) : (r2 <= q.rc2);        // (the record's own copy of rc^2: see LjPos4)
-   if (hit) ljPair<ENERGY>(dx, dy, dz, r2, a, fx, fy, fz, e);
+   if (hit) pr.template pair<ENERGY>(a, dx, dy, dz, r2, fx, fy, fz, e);
 }
 
 // L2 prefetch of the list loop (PREFETCH): the scalar loads of a batch wait for the slowest of them, and a row is read exactly once (cold by
@@ -134,8 +156,8 @@ __device__ __forceinline__ void ljListTest(const LjArgs& a, const LjPos4& q, rea
 #define LJ_PREFETCH_D 64                      // candidates the entry loads run ahead (a multiple of 64, at least 64: the touches follow one period behind)
 #endif
 
-template <bool SELF, bool ENERGY, bool PREFETCH>
-__device__ __forceinline__ void ljListLoop(const LjArgs& a, const LjPos4* __restrict__ pos, const unsigned* __restrict__ L, int p, int pEnd, int nAll, int lane,
+template <class P, bool SELF, bool ENERGY, bool PREFETCH>
+__device__ __forceinline__ void ljListLoop(const P& pr, const LjArgs& a, const LjPos4* __restrict__ pos, const unsigned* __restrict__ L, int p, int pEnd, int nAll, int lane,
                                            real_t xi, real_t yi, real_t zi, real_t& fx, real_t& fy, real_t& fz, real_t& e, unsigned& sink)
 {
    // The list is wave-uniform: eight offsets per s_load_dwordx8, one s_load_dwordx8 per candidate record.  The offsets of batch b + 1 are
@@ -169,7 +191,7 @@ __device__ __forceinline__ void ljListLoop(const LjArgs& a, const LjPos4* __rest
 #pragma unroll
          for (int u = 0; u < 8; ++u) idn[u] = L[pn + u];
 #pragma unroll
-         for (int u = 0; u < 8; ++u) ljListTest<SELF, ENERGY>(a, q[u], xi, yi, zi, fx, fy, fz, e);
+         for (int u = 0; u < 8; ++u) ljListTest<P, SELF, ENERGY>(pr, a, q[u], xi, yi, zi, fx, fy, fz, e);
 #pragma unroll
          for (int u = 0; u < 8; ++u) id[u] = idn[u];
          if (PREFETCH && (b & 7) == 7) {                     // a period ends: fold what it asked for, ask for the next
@@ -181,7 +203,7 @@ __device__ __forceinline__ void ljListLoop(const LjArgs& a, const LjPos4* __rest
       }
       if (PREFETCH) sink |= touched;
    }
-   for (; p < pEnd; ++p) ljListTest<SELF, ENERGY>(a, atByte(pos, L[p]), xi, yi, zi, fx, fy, fz, e);
+   for (; p < pEnd; ++p) ljListTest<P, SELF, ENERGY>(pr, a, atByte(pos, L[p]), xi, yi, zi, fx, fy, fz, e);
 }
 
 // x, y, z of every occupied slot side by side, so that one scalar load fetches a candidate
@@ -330,9 +352,9 @@ void LJ_WaveCandidates(LjArgs a, LjWaveLists w, int wavesPerCell)
 // G = 64/m (<= 4) times across the lanes and replica g takes the stencil cells k = g, g+G, g+2G, ..., so the wave finishes in
 // ~1/G of the neighbour iterations; replicas are summed with ds_bpermute.  The neighbour is not wave-uniform here, so
 // positions come through per-lane loads.  Used for the under-filled tail wave of a cell (20 of 64 lanes for 148 atoms)
-// and for chunks beyond the host's occupancy estimate.
-template <bool ENERGY>
-__device__ __forceinline__ void ljChunkGeneric(const LjArgs& a, int iBox, int ni, int chunk, int lane)
+// and for chunks beyond the host's occupancy estimate (EXTRA: those take r^2 from the policy).
+template <class P, bool ENERGY, bool EXTRA = false>
+__device__ __forceinline__ void ljChunkGeneric(const P& pr, const LjArgs& a, int iBox, int ni, int chunk, int lane)
 {
    const int* __restrict__ nb = a.nbr + (size_t)iBox * 27;
    const int m = ni - chunk * 64 < 64 ? ni - chunk * 64 : 64;
@@ -351,8 +373,8 @@ __device__ __forceinline__ void ljChunkGeneric(const LjArgs& a, int iBox, int ni
       for (int j = 0; __any(j < nj); ++j) {
          if (j < nj) {
             const real_t dx = xi - a.rx[base + j], dy = yi - a.ry[base + j], dz = zi - a.rz[base + j];
-            const real_t r2 = dx*dx + dy*dy + dz*dz;
-            if (r2 <= a.rc2 && r2 > R(0.0)) ljPair<ENERGY>(dx, dy, dz, r2, a, fx, fy, fz, e);
+            const real_t r2 = EXTRA ? pr.r2ExtraChunk(dx, dy, dz) : dx*dx + dy*dy + dz*dz;
+            if (r2 <= a.rc2 && r2 > R(0.0)) pr.template pair<ENERGY>(a, dx, dy, dz, r2, fx, fy, fz, e);
          }
       }
    }
@@ -362,17 +384,13 @@ __device__ __forceinline__ void ljChunkGeneric(const LjArgs& a, int iBox, int ni
       tx += bpermuteR(fx, src); ty += bpermuteR(fy, src); tz += bpermuteR(fz, src);
       if (ENERGY) te += bpermuteR(e, src);
    }
-   if (lane < m) {
-      const real_t fs = LJ_FORCE_SCALE(a);
-      a.fx[iOff] = tx * fs; a.fy[iOff] = ty * fs; a.fz[iOff] = tz * fs;
-      if (ENERGY) a.e[iOff] = te * R(2.0) * a.eps;
-   }
+   if (lane < m) pr.template store<ENERGY>(a, iOff, tx, ty, tz, te);
 }
 
 // The generic chunk with a candidate list: replica g takes the g-th part of the list (parts of a multiple of four entries, so that a lane
 // fetches four offsets with one 16-byte load), candidates arrive through per-lane loads of the packed records.
-template <bool ENERGY>
-__device__ __forceinline__ void ljChunkListed(const LjArgs& a, const LjPos4* __restrict__ pos, const unsigned* __restrict__ L, int nAll,
+template <class P, bool ENERGY>
+__device__ __forceinline__ void ljChunkListed(const P& pr, const LjArgs& a, const LjPos4* __restrict__ pos, const unsigned* __restrict__ L, int nAll,
                                               int iBox, int ni, int chunk, int lane)
 {
    const int m = ni - chunk * 64 < 64 ? ni - chunk * 64 : 64;
@@ -397,7 +415,7 @@ __device__ __forceinline__ void ljChunkListed(const LjArgs& a, const LjPos4* __r
       for (int u = 0; u < 4; ++u) {
          const real_t dx = xi - q[u].x, dy = yi - q[u].y, dz = zi - q[u].z;
          const real_t r2 = dx*dx + dy*dy + dz*dz;
-         if (it + u < mine && r2 <= a.rc2 && r2 > R(0.0)) ljPair<ENERGY>(dx, dy, dz, r2, a, fx, fy, fz, e);
+         if (it + u < mine && r2 <= a.rc2 && r2 > R(0.0)) pr.template pair<ENERGY>(a, dx, dy, dz, r2, fx, fy, fz, e);
       }
    }
    real_t tx = fx, ty = fy, tz = fz, te = e;
@@ -406,11 +424,7 @@ __device__ __forceinline__ void ljChunkListed(const LjArgs& a, const LjPos4* __r
       tx += bpermuteR(fx, src); ty += bpermuteR(fy, src); tz += bpermuteR(fz, src);
       if (ENERGY) te += bpermuteR(e, src);
    }
-   if (lane < m) {
-      const real_t fs = LJ_FORCE_SCALE(a);
-      a.fx[iOff] = tx * fs; a.fy[iOff] = ty * fs; a.fz[iOff] = tz * fs;
-      if (ENERGY) a.e[iOff] = te * R(2.0) * a.eps;
-   }
+   if (lane < m) pr.template store<ENERGY>(a, iOff, tx, ty, tz, te);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -423,8 +437,8 @@ __device__ __forceinline__ void ljChunkListed(const LjArgs& a, const LjPos4* __r
 // SGPRs: 106 in double (hipcc: 7 waves per SIMD), as before the prefetch.  The list loop holds seven records (56 SGPRs), eight entries and ~25 of loop and
 // wave state; with the six the hardware adds that is the 96 an eighth wave allows at best, and hipcc bounded to it (__launch_bounds__(256, 7 or 8)) spills
 // 40-120 SGPRs, reloaded inside the list loop.  DESIGN.md section 6 has the attempts.
-template <bool ENERGY, bool LISTED, bool PREFETCH>
-__device__ __forceinline__ void ljForceThreadAtom(const LjArgs& a, const int wavesPerCell, const LjWaveLists& w)
+template <class P, bool ENERGY, bool LISTED, bool PREFETCH>
+__device__ __forceinline__ void ljForceThreadAtom(const P& pr, const LjArgs& a, const int wavesPerCell, const LjWaveLists& w)
 {
    const int lane = threadIdx.x & 63;
    // one workgroup per cell when wavesPerCell <= 4 (blockDim = 64 * wavesPerCell); otherwise 4-wave workgroups laid flat over (cell, chunk)
@@ -444,8 +458,8 @@ __device__ __forceinline__ void ljForceThreadAtom(const LjArgs& a, const int wav
    }
    const unsigned* __restrict__ L = LISTED ? w.cand + (size_t)(iBox * w.wavesMax + chunk) * w.candCap : nullptr;
    if (m <= 32) {
-      if (LISTED && nAll >= 0) ljChunkListed<ENERGY>(a, w.pos, L, nAll, iBox, ni, chunk, lane);
-      else                     ljChunkGeneric<ENERGY>(a, iBox, ni, chunk, lane);
+      if (LISTED && nAll >= 0) ljChunkListed<P, ENERGY>(pr, a, w.pos, L, nAll, iBox, ni, chunk, lane);
+      else                     ljChunkGeneric<P, ENERGY>(pr, a, iBox, ni, chunk, lane);
    } else {
       // full wave: neighbour j is wave-uniform -> positions arrive through the scalar unit
       const int* __restrict__ nb = a.nbr + (size_t)iBox * 27;
@@ -458,34 +472,30 @@ __device__ __forceinline__ void ljForceThreadAtom(const LjArgs& a, const int wav
       // two batches in SGPRs -- measured 9 % slower: 4.30 vs 3.95 ms; the 8-wide batches below rely on the other waves for latency cover)
       unsigned sink = 0u;                                    // the prefetch loads of ljListLoop end here
       if (LISTED && nAll >= 0) {
-         ljListLoop<true, ENERGY, PREFETCH>(a, w.pos, L, 0, nSelf, nAll, lane, xi, yi, zi, fx, fy, fz, e, sink);
-         ljListLoop<false, ENERGY, PREFETCH>(a, w.pos, L, nSelf, nAll, nAll, lane, xi, yi, zi, fx, fy, fz, e, sink);
+         ljListLoop<P, true, ENERGY, PREFETCH>(pr, a, w.pos, L, 0, nSelf, nAll, lane, xi, yi, zi, fx, fy, fz, e, sink);
+         ljListLoop<P, false, ENERGY, PREFETCH>(pr, a, w.pos, L, nSelf, nAll, nAll, lane, xi, yi, zi, fx, fy, fz, e, sink);
       } else {
-         ljCellLoop<true, ENERGY>(a, iBox, xi, yi, zi, fx, fy, fz, e);
-         for (int k = 1; k < 27; ++k) ljCellLoop<false, ENERGY>(a, uniform(nb[k]), xi, yi, zi, fx, fy, fz, e);
+         ljCellLoop<P, true, ENERGY>(pr, a, iBox, xi, yi, zi, fx, fy, fz, e);
+         for (int k = 1; k < 27; ++k) ljCellLoop<P, false, ENERGY>(pr, a, uniform(nb[k]), xi, yi, zi, fx, fy, fz, e);
       }
-      if (active) {
-         const real_t fs = LJ_FORCE_SCALE(a);
-         a.fx[iOff] = fx * fs; a.fy[iOff] = fy * fs; a.fz[iOff] = fz * fs;
-         if (ENERGY) a.e[iOff] = e * R(2.0) * a.eps;          // 4 eps * 1/2 per pair
-      }
+      if (active) pr.template store<ENERGY>(a, iOff, fx, fy, fz, e);
       // where the prefetch ends: no cell has a negative capacity, so this store never executes, and it stands behind the force stores
       if (LISTED && PREFETCH && a.cap < 0) a.fx[iOff] = (real_t)sink;
    }
    // NOTE: no store may precede the scalar-path loads above on any path through this kernel, or the compiler gives up proving the
    // position arrays unclobbered and silently replaces the s_load_dwordx16 stream by per-lane global_load (measured: 4.7 -> 6.2 ms).
    // Everything below runs after the wave's first chunk is stored.  Check `grep -c s_load_dwordx16` in the ISA after edits here.
-   for (int c = chunk + wavesPerCell; c * 64 < ni; c += wavesPerCell) ljChunkGeneric<ENERGY>(a, iBox, ni, c, lane);
+   for (int c = chunk + wavesPerCell; c * 64 < ni; c += wavesPerCell) ljChunkGeneric<P, ENERGY, true>(pr, a, iBox, ni, c, lane);
 }
 
 // the kernel as launched: with lists it prefetches; LJ_Force_thread_atom_plain is the listed kernel without the prefetch (COMD_LJ_PREFETCH=0)
 template <bool ENERGY, bool LISTED>
 __global__ __launch_bounds__(256)
-void LJ_Force_thread_atom(LjArgs a, int wavesPerCell, LjWaveLists w) { ljForceThreadAtom<ENERGY, LISTED, LISTED>(a, wavesPerCell, w); }
+void LJ_Force_thread_atom(LjArgs a, int wavesPerCell, LjWaveLists w) { ljForceThreadAtom<LjAnalyticPair, ENERGY, LISTED, LISTED>(LjAnalyticPair(), a, wavesPerCell, w); }
 
 template <bool ENERGY>
 __global__ __launch_bounds__(256)
-void LJ_Force_thread_atom_plain(LjArgs a, int wavesPerCell, LjWaveLists w) { ljForceThreadAtom<ENERGY, true, false>(a, wavesPerCell, w); }
+void LJ_Force_thread_atom_plain(LjArgs a, int wavesPerCell, LjWaveLists w) { ljForceThreadAtom<LjAnalyticPair, ENERGY, true, false>(LjAnalyticPair(), a, wavesPerCell, w); }
 
 // ---------------------------------------------------------------------------------------------------
 // CTA per link cell (the reference's LJ_Force_cta_cell shape, gpu_lj_cta_cell.h:29-122): one workgroup per cell, one thread

@@ -79,10 +79,9 @@ void NeighborListUpdateRequired(const real_t* __restrict__ rx, const real_t* __r
    if (dx*dx + dy*dy + dz*dz > skinHalf2) *flag = 1;
 }
 
-// ---- LJ over the list ----------------------------------------------------------------------------------------------------
-template <bool ENERGY>
-__global__ __launch_bounds__(256)
-void LJ_Force_thread_atom_nl(LjArgs a, NlView nl)
+// ---- LJ over the list (P: the pair policy, see LjAnalyticPair in lj_kernels.h) ----------------------------------------------
+template <class P, bool ENERGY>
+__device__ __forceinline__ void ljForceThreadAtomNl(const P& pr, const LjArgs& a, const NlView& nl)
 {
    int iBox, i;
    if (!nlSlot(a.cells, a.nAtoms, a.nCells, a.cap, iBox, i)) return;
@@ -101,19 +100,21 @@ void LJ_Force_thread_atom_nl(LjArgs a, NlView nl)
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
          const real_t r2 = dx[u]*dx[u] + dy[u]*dy[u] + dz[u]*dz[u];
-         if (r2 <= a.rc2) ljPair<ENERGY>(dx[u], dy[u], dz[u], r2, a, fx, fy, fz, e);
+         if (r2 <= a.rc2) pr.template pair<ENERGY>(a, dx[u], dy[u], dz[u], r2, fx, fy, fz, e);
       }
    }
    for (; k < n; ++k) {
       const int j = row[(size_t)k * a.cap];
       const real_t dx = xi - a.rx[j], dy = yi - a.ry[j], dz = zi - a.rz[j];
       const real_t r2 = dx*dx + dy*dy + dz*dz;
-      if (r2 <= a.rc2) ljPair<ENERGY>(dx, dy, dz, r2, a, fx, fy, fz, e);
+      if (r2 <= a.rc2) pr.template pair<ENERGY>(a, dx, dy, dz, r2, fx, fy, fz, e);
    }
-   const real_t fs = LJ_FORCE_SCALE(a);
-   a.fx[iSlot] = fx * fs; a.fy[iSlot] = fy * fs; a.fz[iSlot] = fz * fs;
-   if (ENERGY) a.e[iSlot] = e * R(2.0) * a.eps;
+   pr.template store<ENERGY>(a, iSlot, fx, fy, fz, e);
 }
+
+template <bool ENERGY>
+__global__ __launch_bounds__(256)
+void LJ_Force_thread_atom_nl(LjArgs a, NlView nl) { ljForceThreadAtomNl<LjAnalyticPair, ENERGY>(LjAnalyticPair(), a, nl); }
 
 // ---- EAM passes 1 and 3 over the list; tables in LDS when they fit (funcfl), else through L2 (setfl) ----------------------------
 template <int STEP, bool LDS_TABLES, bool SPLINE>
@@ -331,13 +332,12 @@ void BuildNeighborListSlabs(const real_t* __restrict__ rx, const real_t* __restr
 }
 
 // workgroup per cell, thread per atom; blockDim.x = fullest cell rounded up to whole waves (<= 512); LDS = 3 * groupAtoms doubles
-template <bool ENERGY>
-__global__ __launch_bounds__(512)
-void LJ_Force_nl_slabs(LjArgs a, NlSlabView nl, int groupAtoms)
+// (P: the pair policy, see LjAnalyticPair in lj_kernels.h)
+template <class P, bool ENERGY>
+__device__ __forceinline__ void ljForceNlSlabs(const P& pr, const LjArgs& a, const NlSlabView& nl)
 {
    extern __shared__ __attribute__((aligned(16))) real_t ldsPos[];      // {x, y, z} records: one address per neighbour, ds_read offsets 0/8/16
    real_t* __restrict__ sp = ldsPos;
-   (void)groupAtoms;
    const int iBox = a.cells ? a.cells[blockIdx.x] : blockIdx.x;
    const int tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6);
    const int ni = uniform(a.nAtoms[iBox]);
@@ -399,14 +399,14 @@ void LJ_Force_nl_slabs(LjArgs a, NlSlabView nl, int groupAtoms)
 #pragma unroll
             for (int u = 0; u < NL_BATCH; ++u) {
                const real_t r2 = dx[u]*dx[u] + dy[u]*dy[u] + dz[u]*dz[u];
-               if (r2 <= a.rc2) ljPair<ENERGY>(dx[u], dy[u], dz[u], r2, a, fx, fy, fz, e);      // (evaluating all 8 branch-free, misses weighted 0: 2.09 vs 2.07 ms)
+               if (r2 <= a.rc2) pr.template pair<ENERGY>(a, dx[u], dy[u], dz[u], r2, fx, fy, fz, e);      // (evaluating all 8 branch-free, misses weighted 0: 2.09 vs 2.07 ms)
             }
          }
          for (; k < n; ++k) {
             const int j = row[(size_t)k * step];
             const real_t dx = xi - sp[j], dy = yi - sp[j + 1], dz = zi - sp[j + 2];
             const real_t r2 = dx*dx + dy*dy + dz*dz;
-            if (r2 <= a.rc2) ljPair<ENERGY>(dx, dy, dz, r2, a, fx, fy, fz, e);
+            if (r2 <= a.rc2) pr.template pair<ENERGY>(a, dx, dy, dz, r2, fx, fy, fz, e);
          }
       }
    }
@@ -420,12 +420,12 @@ void LJ_Force_nl_slabs(LjArgs a, NlSlabView nl, int groupAtoms)
       }
       fx = tx; fy = ty; fz = tz; e = te;
    }
-   if (active && g == 0) {
-      const real_t fs = LJ_FORCE_SCALE(a);
-      a.fx[iSlot] = fx * fs; a.fy[iSlot] = fy * fs; a.fz[iSlot] = fz * fs;
-      if (ENERGY) a.e[iSlot] = e * R(2.0) * a.eps;
-   }
+   if (active && g == 0) pr.template store<ENERGY>(a, iSlot, fx, fy, fz, e);
 }
+
+template <bool ENERGY>
+__global__ __launch_bounds__(512)
+void LJ_Force_nl_slabs(LjArgs a, NlSlabView nl, int groupAtoms) { (void)groupAtoms; ljForceNlSlabs<LjAnalyticPair, ENERGY>(LjAnalyticPair(), a, nl); }
 
 // ====================================================================================================================
 // EAM: ~57 listed neighbours per atom (Cu_u6, skin 10 %), ~14 atoms per cell: the whole 27-cell stencil is 373 atoms, 9-12 KB as
