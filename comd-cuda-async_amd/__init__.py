@@ -209,6 +209,14 @@ def lib_host():
         lib.comdGetMullerPlathe.restype = ctypes.c_int
         lib.comdFourierKappa.argtypes = [c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_double_p, c_double_p]
         lib.comdFourierKappa.restype = ctypes.c_int
+        lib.comdStructureFactorRefusal.argtypes = [ctypes.c_int, c_int_p]
+        lib.comdStructureFactorRefusal.restype = ctypes.c_int
+        lib.comdStructureFactor.argtypes = [vp, ctypes.c_int, c_int_p, c_double_p]
+        lib.comdStructureFactor.restype = ctypes.c_int
+        lib.comdStructureFactorRadial.argtypes = [c_double_p, ctypes.c_int, c_int_p, c_double_p, ctypes.c_int, c_double_p, c_double_p, c_double_p]
+        lib.comdStructureFactorRadial.restype = ctypes.c_int
+        lib.comdBraggOrder.argtypes = [vp, c_double_p]
+        lib.comdBraggOrder.restype = ctypes.c_int
         lib.comdLocalBounds.argtypes = [vp, c_double_p]
         lib.comdSetLangevin.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_int]
         lib.comdSetLangevin.restype = ctypes.c_int
@@ -642,6 +650,49 @@ class Simulation:
         on = self.lib.comdGetMullerPlathe(self.ptr, out)
         return {"on": bool(on), "axis": "xyz"[int(out[0])], "n_bins": int(out[1]), "every": int(out[2]), "swaps": int(out[3]), "start": int(out[4]),
                 "exchanged_ev": out[5], "pairs": int(out[6]), "skipped": int(out[7])}
+
+    # --- static structure factor and Bragg order (not in the reference: comd-hip --sk, --skStride, --skBins, --skStart, --skFile) ---
+    def structure_factor(self, k_max=8, stride=1):
+        """The static structure factor of the current state on the half grid of wave vectors k = 2 pi (sx h / Lx, sy k / Ly, sz l / Lz), h in [0, k_max], k, l in
+        [-k_max, k_max] (S(-k) = S(k)), on the current box: {"index" int32 (K, 3) the (h, k, l), "k" float64 (K, 3) in 1/Angstrom, "rho" complex128 (K,) the density
+        amplitudes sum_j exp(-i k . r_j) over the atoms of all ranks, "s" float64 (K,) = |rho|^2 / N, "shape" (k_max + 1, 2 k_max + 1, 2 k_max + 1) the C order of
+        the K rows}; (0, 0, 0) is kept and its rho is N exactly.  `stride` is an int or (sx, sy, sz): with the unit cells of -x -y -z the grid is the reciprocal
+        lattice of the conventional cubic cell, where a perfect FCC crystal has S = N for h, k, l all even or all odd and 0 elsewhere.  1 <= k_max <= 64, strides
+        >= 1 with stride k_max <= 65536.  Summed on the device by computeStructureFactor and over the ranks (every rank gets the global result).  Each amplitude
+        component is within N eps (16 + 2 pi max|stride index|) of the exact sum, eps that of the build's real type; one configuration gives the same bits at every
+        call, but methods, cell orders and rank counts add the atoms in different orders and differ within that bound.  ValueError before anything is launched
+        for a refused grid, RuntimeError on a host-only simulation."""
+        np = self._np
+        m, st = _sk_grid("structure_factor", k_max, stride)
+        if self.host_only:
+            raise RuntimeError("structure_factor: a host-only simulation has no device state")
+        w = 2 * m + 1
+        raw = np.zeros(((m + 1) * w * w, 2), dtype=np.float64)
+        if self.lib.comdStructureFactor(self.ptr, m, st.ctypes.data_as(c_int_p), raw.ctypes.data_as(c_double_p)) != 0:
+            raise RuntimeError("structure_factor: comdStructureFactor failed")
+        index = _sk_index(np, m)
+        rho = raw[:, 0] + 1j * raw[:, 1]
+        return {"index": index, "k": 2.0 * np.pi * (index * st[None, :]) / self.box[None, :], "rho": rho, "s": (raw[:, 0] ** 2 + raw[:, 1] ** 2) / float(self.n_global),
+                "shape": (m + 1, w, w)}
+
+    def structure_factor_radial(self, k_max=8, stride=1, n_bins=50):
+        """(k centres in 1/Angstrom, S, counts): the powder average of structure_factor(k_max, stride) in n_bins uniform |k| bins up to the largest sphere inside
+        the grid -- the module function structure_factor_radial() on this state's amplitudes and box."""
+        _sk_grid("structure_factor_radial", k_max, stride)
+        if not 1 <= int(n_bins) <= 4096:
+            raise ValueError(f"structure_factor_radial: n_bins must lie in 1..4096 (got {n_bins})")
+        return structure_factor_radial(self.structure_factor(k_max, stride)["rho"], k_max, stride, self.box, n_bins)
+
+    def bragg_order(self):
+        """The Bragg order parameter: the mean over the reflections (1, +-1, +-1) of S / N at the strides (nx, ny, nz) of -x -y -z -- the {111} peaks of the
+        conventional cell.  1 on the perfect lattice, the Debye-Waller factor of a warm crystal, of the order 1/N in the melt; the indices follow the box, so an
+        affine strain leaves it at 1.  One comdStructureFactor call with k_max = 1.  RuntimeError on a host-only simulation."""
+        if self.host_only:
+            raise RuntimeError("bragg_order: a host-only simulation has no device state")
+        out = ctypes.c_double(0.0)
+        if self.lib.comdBraggOrder(self.ptr, ctypes.byref(out)) != 0:
+            raise RuntimeError("bragg_order: comdBraggOrder failed")
+        return out.value
 
     def pressure_tensor(self):
         """(K + W) / V in eV/A^3, V the volume of the global domain (positive: compressive).  1 eV/A^3 = 160.21766208 GPa."""
@@ -1128,6 +1179,53 @@ def fourier_conductivity(temperature, width, area, energy, time):
     if rc < 0:
         return None, None
     return g.value, (kappa.value if rc == 0 else None)
+
+
+_SK_WHY = {1: "k_max must lie in 1..64", 2: "every stride must be >= 1", 3: "stride * k_max must not exceed 65536"}
+
+
+def _sk_grid(what, k_max, stride):
+    """(k_max, int32 strides (3,)) after the refusals of comdStructureFactorRefusal, which come before any launch"""
+    import numpy as np
+    st = np.asarray(stride)
+    if st.shape not in ((), (3,)) or not np.issubdtype(st.dtype, np.integer) or int(k_max) != k_max or np.any(np.abs(st) > 2 ** 30):
+        raise ValueError(f"{what}: k_max is an int and stride an int or (sx, sy, sz) of ints (got {k_max!r}, {stride!r})")
+    st = np.ascontiguousarray(np.broadcast_to(st, (3,)), dtype=np.int32)
+    m = int(k_max) if abs(int(k_max)) < 2 ** 30 else 0      # beyond a C int: refused as 0 is
+    why = lib_host().comdStructureFactorRefusal(m, st.ctypes.data_as(c_int_p))
+    if why:
+        raise ValueError(f"{what}: {_SK_WHY[why]} (got k_max {k_max}, stride {stride})")
+    return m, st
+
+
+def _sk_index(np, m):
+    """int32 (K, 3): the (h, k, l) of the rows of the half grid in their C order"""
+    h, k, l = np.meshgrid(np.arange(m + 1), np.arange(-m, m + 1), np.arange(-m, m + 1), indexing="ij")
+    return np.stack([h.ravel(), k.ravel(), l.ravel()], axis=1).astype(np.int32)
+
+
+def structure_factor_radial(rho, k_max, stride, box, n_bins):
+    """(k centres, S, counts): the powder average of the density amplitudes `rho`, complex (K,) or any shape of K = (k_max + 1) (2 k_max + 1)^2 values in the C order of
+    Simulation.structure_factor, on a box of extents `box` (comdStructureFactorRadial of the host library; no device).  S = |rho|^2 / N with N = Re rho(0, 0, 0).
+    n_bins uniform |k| bins up to k_top = min_a 2 pi stride_a k_max / box_a: a vector with 0 < |k| <= k_top is in bin min(floor(|k| / (k_top / n_bins)), n_bins - 1)
+    and counts twice when h > 0 (it stands for -k as well), once when h = 0; k = 0 is left out.  S is the weighted mean per bin, NaN where counts is 0.  ValueError
+    for a refused grid, n_bins outside 1..4096, another number of amplitudes, a box extent or an N that is not positive."""
+    import numpy as np
+    m, st = _sk_grid("structure_factor_radial", k_max, stride)
+    n = int(n_bins)
+    amp = np.ascontiguousarray(rho, dtype=np.complex128).ravel()
+    ext = np.ascontiguousarray(box, dtype=np.float64).ravel()
+    if amp.shape[0] != (m + 1) * (2 * m + 1) ** 2 or ext.shape[0] != 3:
+        raise ValueError(f"structure_factor_radial: need {(m + 1) * (2 * m + 1) ** 2} amplitudes and 3 box extents (got {amp.shape[0]}, {ext.shape[0]})")
+    if not 1 <= n <= 4096:
+        raise ValueError(f"structure_factor_radial: n_bins must lie in 1..4096 (got {n_bins})")
+    raw = np.ascontiguousarray(np.stack([amp.real, amp.imag], axis=1))
+    centres, s, counts = np.zeros(n), np.zeros(n), np.zeros(n)
+    rc = lib_host().comdStructureFactorRadial(raw.ctypes.data_as(c_double_p), m, st.ctypes.data_as(c_int_p), ext.ctypes.data_as(c_double_p), n,
+                                              centres.ctypes.data_as(c_double_p), s.ctypes.data_as(c_double_p), counts.ctypes.data_as(c_double_p))
+    if rc != 0:
+        raise ValueError(f"structure_factor_radial: refused ({rc}): the box extents and N = Re rho(0, 0, 0) = {amp[(m * (2 * m + 1) + m)].real} must be positive")
+    return centres, s, counts.astype(np.int64)
 
 
 def run_main(args):

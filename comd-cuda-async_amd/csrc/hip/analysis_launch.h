@@ -1,4 +1,4 @@
-// analysis_launch.h -- the launch layer of the analyses, computeVirial ... comdMullerPlatheApplyGpu (comd_hip.h): none of them is in the reference.  Host code,
+// analysis_launch.h -- the launch layer of the analyses, computeVirial ... computeStructureFactor (comd_hip.h): none of them is in the reference.  Host code,
 // part of comd_device.hip's translation unit (it uses HIP_CHECK, LAUNCH_CHECK, S, dalloc, allowDynamicLds, ceilDiv, of that file, makeLjArgs and ljTableView of lj_launch.h).
 #pragma once
 
@@ -474,5 +474,60 @@ extern "C" void comdMullerPlatheApplyGpu(SimGpu* sim, int n, const long long* sl
    HIP_CHECK(hipMemcpyAsync(dP, p3, (size_t)3 * n * sizeof(real_t), hipMemcpyHostToDevice, st));
    hipLaunchKernelGGL(MP_apply, dim3(1), dim3(128), 0, st, n, (const long long*)dSlots, (const real_t*)dP, sim->atoms.p.x, sim->atoms.p.y, sim->atoms.p.z);
    LAUNCH_CHECK();
+   HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// Not in the reference: the density amplitudes of the structure factor (sk_kernels.h).  One instance for every potential and method: it reads r and the cell tables only
+extern "C" void computeStructureFactor(SimGpu* sim, int M, const int* stride3, const double* extent3, double* outKx2)
+{
+   hipStream_t st = analysisStream(sim);
+   bool ok = M >= 1 && M <= SK_MAX_M;
+   for (int a = 0; a < 3; ++a) ok = ok && stride3[a] >= 1 && (long)stride3[a] * M <= SK_MAX_HM && extent3[a] > 0.0;
+   if (!ok) {
+      fprintf(stderr, "computeStructureFactor: M %d (1..%d), strides %d %d %d (>= 1, stride M <= %d), extents %g %g %g\n", M, SK_MAX_M, stride3[0], stride3[1], stride3[2], SK_MAX_HM,
+              extent3[0], extent3[1], extent3[2]);
+      exit(-1);
+   }
+   SkArgs v;
+   v.rx = sim->atoms.r.x; v.ry = sim->atoms.r.y; v.rz = sim->atoms.r.z; v.nAtoms = sim->boxes.nAtoms;
+   v.nLocalBoxes = sim->boxes.nLocalBoxes; v.cap = sim->maxAtoms;
+   v.M = M; v.W = 2 * M + 1; v.lbNeg = ceilDiv(M, SK_LB); v.nLB = v.lbNeg + M / SK_LB + 1;
+   v.nItems = (M + 1) * v.W * v.nLB;
+   v.sx = stride3[0]; v.sy = stride3[1]; v.sz = stride3[2];
+   v.Lx = extent3[0]; v.Ly = extent3[1]; v.Lz = extent3[2];
+   const int nTiles = ceilDiv(v.nItems, 256);
+   int tableMax = 0;
+   for (int tile = 0; tile < nTiles; ++tile) {
+      const SkTile t = skTileOf(tile, v.nItems, v.nLB, v.W, M);
+      if (t.nH + t.nKa > tableMax) tableMax = t.nH + t.nKa;
+   }
+   auto ldsOf = [&](int batch) { return (size_t)3 * batch * sizeof(double) + (size_t)batch * (tableMax + v.nLB + 1) * sizeof(real2); };
+   v.batch = ldsOf(SK_BATCH_MAX) <= SK_LDS_FOR_64 ? SK_BATCH_MAX : SK_BATCH_MAX / 2;
+   const size_t lds = ldsOf(v.batch);
+   if (lds > 65536) { fprintf(stderr, "computeStructureFactor: %zu bytes of LDS\n", lds); exit(-1); }
+   // the chunks: a few workgroups per CU in all; one when the tiles alone fill the device
+   int dev = 0, cus = 0;
+   HIP_CHECK(hipGetDevice(&dev));
+   HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+   const int nLocal = v.nLocalBoxes > 0 ? v.nLocalBoxes : 1;
+   int chunks = tuningOf(sim).skChunks ? tuningOf(sim).skChunks : ceilDiv((long)4 * cus, nTiles);
+   if (chunks > nLocal) chunks = nLocal;
+   if (chunks > 65535) chunks = 65535;
+   if (chunks < 1) chunks = 1;
+   v.cellsPerChunk = ceilDiv(nLocal, chunks);
+   chunks = ceilDiv(nLocal, v.cellsPerChunk);
+   const size_t n = (size_t)2 * (M + 1) * v.W * v.W, need = ((size_t)chunks + 1) * n;
+   if (need > sim->skCap) {
+      if (sim->skBuf) { HIP_CHECK(hipStreamSynchronize(st)); HIP_CHECK(hipFree(sim->skBuf)); }
+      sim->skBuf = dalloc<double>(need, false);
+      sim->skCap = need;
+   }
+   v.partial = sim->skBuf;
+   double* out = sim->skBuf + (size_t)chunks * n;
+   allowDynamicLds((const void*)SK_amplitudes, lds);
+   hipLaunchKernelGGL(SK_amplitudes, dim3(nTiles, chunks), dim3(256), lds, st, v);
+   hipLaunchKernelGGL(SK_sum, dim3(ceilDiv((long)n, 256)), dim3(256), 0, st, (const double*)sim->skBuf, chunks, n, out);
+   LAUNCH_CHECK();
+   HIP_CHECK(hipMemcpyAsync(outKx2, out, n * sizeof(double), hipMemcpyDeviceToHost, st));
    HIP_CHECK(hipStreamSynchronize(st));
 }

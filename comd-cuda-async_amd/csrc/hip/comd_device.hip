@@ -24,6 +24,7 @@
 #include "fdotr_kernels.h"
 #include "profile_kernels.h"
 #include "mp_kernels.h"
+#include "sk_kernels.h"
 #include "rdf_kernels.h"
 #include "csp_kernels.h"
 #include "cna_kernels.h"
@@ -90,6 +91,7 @@ struct ComdTuning {
    bool   eamListsEveryBuild;  // COMD_EAM_LISTS_EVERY_BUILD (set)  the brick lists of the EAM list method remade at every list build                      kept while they fit
    bool   nlBankOrder;         // COMD_NL_BANK_ORDER=1          LJ Verlet rows ordered by LDS bank class at build time (an experiment)                      off
    double nlMargin;            // COMD_NL_MARGIN=x (0 <= x < 1) the deferred test's margin as a fraction of skin/2 (tests: force the stop); < 0 = unset     4 / list life
+   int    skChunks;            // COMD_SK_CHUNKS=n (> 0)        atom chunks of computeStructureFactor, clamped to the local cells (tests: the sum over chunks)  fills the device
 };
 static ComdTuning readTuning()
 {
@@ -124,6 +126,7 @@ static ComdTuning readTuning()
    t.eamListsEveryBuild = env("COMD_EAM_LISTS_EVERY_BUILD") != nullptr;
    t.nlBankOrder = num("COMD_NL_BANK_ORDER") != 0;
    t.nlMargin = env("COMD_NL_MARGIN") && atof(env("COMD_NL_MARGIN")) >= 0.0 && atof(env("COMD_NL_MARGIN")) < 1.0 ? atof(env("COMD_NL_MARGIN")) : -1.0;
+   t.skChunks = num("COMD_SK_CHUNKS") > 0 ? num("COMD_SK_CHUNKS") : 0;
    return t;
 }
 // AllocateGpu fills SimGpu.tuning; a SimGpu that reaches a launch wrapper without it gets its record here
@@ -613,7 +616,7 @@ extern "C" void DestroyGpu(SimGpu* sim)
                     sim->eam_pot.pairRows, sim->eam_pot.pairRowCount, sim->eam_pot.cellSel, sim->eam_pot.brickGroup, sim->eam_pot.brickList, sim->eam_pot.brickSel, sim->eam_pot.brickStats, sim->eam_pot.atomRows, sim->eam_pot.atomRowCount, sim->eam_pot.atomBrickSel,
                     sim->atoms.neighborList.brickRows, sim->atoms.neighborList.brickRowCount, sim->adapterScan, sim->lj_pot.waveCand, sim->lj_pot.waveCandCount, sim->lj_pot.packedR[0], sim->lj_pot.packedR[1], sim->lj_pot.packedF[0], sim->lj_pot.packedF[1],
                     sim->lj_pot.lj_interpolation.values, sim->virialBuf, sim->pairHistBuf, sim->dispBuf, sim->dispSumBuf, sim->cspBuf, sim->cspCoordBuf, sim->cnaBuf, sim->stressBuf, sim->stressSumBuf,
-                    sim->strainRefBuf, sim->strainBuf, sim->strainCountBuf, sim->strainSumBuf, sim->heatFluxBuf, sim->heatFluxSumBuf, sim->fdotrBuf, sim->fdotrRows, sim->profileBuf, sim->mpBuf, sim->mpRows };
+                    sim->strainRefBuf, sim->strainBuf, sim->strainCountBuf, sim->strainSumBuf, sim->heatFluxBuf, sim->heatFluxSumBuf, sim->fdotrBuf, sim->fdotrRows, sim->profileBuf, sim->mpBuf, sim->mpRows, sim->skBuf };
    for (void* p : ptrs) if (p) HIP_CHECK(hipFree(p));
    if (sim->statusEvent) (void)hipEventDestroy((hipEvent_t)sim->statusEvent);
    if (sim->pinned) HIP_CHECK(hipHostFree(sim->pinned));

@@ -1,5 +1,5 @@
 /* analysis.c -- the host entries of the analyses (not in the reference; comd_host.h): pressure, g(r), centro-symmetry, common neighbour analysis, per-atom
- * stress and strain, heat flux and its autocorrelation, displacements, slab profiles and the Mueller-Plathe exchange.  Each is a call into include/comd_hip.h for this rank's share and a sum over the ranks. */
+ * stress and strain, heat flux and its autocorrelation, displacements, slab profiles, the Mueller-Plathe exchange and the structure factor.  Each is a call into include/comd_hip.h for this rank's share and a sum over the ranks. */
 #include "comd_host.h"
 #include "slot_gather.h"
 #include <math.h>
@@ -524,5 +524,78 @@ int comdFourierKappa(const double* T, int nBins, double width, double area, doub
    *gradient = g;
    if (!(g > 0.0) || !(area > 0.0) || !(time > 0.0)) return 1;
    *kappa = energy / (2.0 * area * time) / g * 1.602176634e6;
+   return 0;
+}
+
+/* ---- static structure factor (not in the reference; comd_host.h) ---- */
+int comdStructureFactorRefusal(int M, const int stride[3])
+{
+   if (M < 1 || M > COMD_SK_MAX_M) return 1;
+   for (int a = 0; a < 3; ++a) if (stride[a] < 1) return 2;
+   for (int a = 0; a < 3; ++a) if ((long long)stride[a] * M > COMD_SK_MAX_HM) return 3;
+   return 0;
+}
+
+int comdStructureFactor(SimFlat* s, int M, const int stride[3], double* outKx2)
+{
+   const int why = comdStructureFactorRefusal(M, stride);
+   if (why) return why;
+   if (!s->gpu.boxes.nAtoms) return -1;
+   const double extent[3] = { (double)s->domain->globalExtent[0], (double)s->domain->globalExtent[1], (double)s->domain->globalExtent[2] };
+   computeStructureFactor(&s->gpu, M, stride, extent, outKx2);
+   if (getNRanks() == 1) return 0;
+   const size_t n = (size_t)2 * (M + 1) * (2 * M + 1) * (2 * M + 1);
+   double* mine = (double*)malloc(n * sizeof(double));
+   memcpy(mine, outKx2, n * sizeof(double));
+   startTimer(commReduceTimer);
+   addDoubleParallelLong(mine, outKx2, n);
+   stopTimer(commReduceTimer);
+   free(mine);
+   return 0;
+}
+
+#define SK_TWO_PI 6.283185307179586
+
+int comdStructureFactorRadial(const double* rhoKx2, int M, const int stride[3], const double box[3], int nBins, double* kCentre, double* sMean, double* count)
+{
+   const int why = comdStructureFactorRefusal(M, stride);
+   if (why) return why;
+   if (nBins < 1 || nBins > COMD_SK_MAX_BINS) return 4;
+   const int W = 2 * M + 1;
+   const double nAtoms = rhoKx2[2 * ((size_t)M * W + M)];      /* rho(0, 0, 0) */
+   for (int a = 0; a < 3; ++a) if (!(box[a] > 0.0) || !(box[a] < INFINITY)) return 5;
+   if (!(nAtoms > 0.0) || !(nAtoms < INFINITY)) return 5;
+   double kMax = INFINITY;
+   for (int a = 0; a < 3; ++a) { const double k = (SK_TWO_PI * (double)(stride[a] * M)) / box[a]; if (k < kMax) kMax = k; }
+   const double dk = kMax / nBins;
+   for (int b = 0; b < nBins; ++b) { kCentre[b] = (b + 0.5) * dk; sMean[b] = 0.0; count[b] = 0.0; }
+   for (int h = 0; h <= M; ++h)
+      for (int k = -M; k <= M; ++k)
+         for (int l = -M; l <= M; ++l) {
+            if (h == 0 && k == 0 && l == 0) continue;
+            const double kx = (SK_TWO_PI * (double)(stride[0] * h)) / box[0], ky = (SK_TWO_PI * (double)(stride[1] * k)) / box[1], kz = (SK_TWO_PI * (double)(stride[2] * l)) / box[2];
+            const double kk = sqrt((kx * kx + ky * ky) + kz * kz);
+            if (!(kk <= kMax)) continue;
+            int b = (int)floor(kk / dk);
+            if (b > nBins - 1) b = nBins - 1;
+            const double* r = rhoKx2 + 2 * (((size_t)h * W + (k + M)) * W + (l + M));
+            const double weight = h > 0 ? 2.0 : 1.0;
+            sMean[b] += weight * ((r[0] * r[0] + r[1] * r[1]) / nAtoms);
+            count[b] += weight;
+         }
+   for (int b = 0; b < nBins; ++b) sMean[b] = count[b] > 0.0 ? sMean[b] / count[b] : NAN;
+   return 0;
+}
+
+int comdBraggOrder(SimFlat* s, double* out)
+{
+   double rho[2 * 2 * 3 * 3];
+   const int rc = comdStructureFactor(s, 1, s->cells, rho);
+   if (rc != 0) return -1;
+   const double nAtoms = rho[2 * (1 * 3 + 1)];
+   double sum = 0.0;
+   for (int k = 0; k < 3; k += 2)
+      for (int l = 0; l < 3; l += 2) { const double* r = rho + 2 * ((3 + k) * 3 + l); sum += (r[0] * r[0] + r[1] * r[1]) / nAtoms; }      /* h = 1 */
+   *out = (sum / 4.0) / nAtoms;
    return 0;
 }

@@ -32,7 +32,10 @@
  * step whose shear strain is at least X as extended XYZ),
  * --heatflux, --hfStart S, --hfWindow M, --hfFile PATH, --hfAcfFile PATH (heat flux J V = sum_i (e_kin,i + e_i) v_i + 1/2 sum_i sum_j r_ij (f_ij . v_i), reduced on the
  * device at every printed step from global step S on; a Jx(eV/A^2/fs) column, PATH gets the samples, the ACF file the autocorrelation over M lags and the running
- * Green-Kubo thermal conductivity in W/(m K); the reference has no transport output). */
+ * Green-Kubo thermal conductivity in W/(m K); the reference has no transport output),
+ * --sk M, --skStride s|sx,sy,sz, --skBins N, --skStart S, --skFile PATH (static structure factor S(k) = |sum_j exp(-i k . r_j)|^2 / N on the half grid of wave vectors
+ *   2 pi (sx h / Lx, sy k / Ly, sz l / Lz), h in [0, M], k, l in [-M, M], and the Bragg order S(111) / N of the conventional cell, summed on the device at every
+ *   printed step from global step S on; an S111/N column, PATH gets the powder average over N |k| bins; the reference has no reciprocal-space analysis). */
 #include "comd_host.h"
 #include <getopt.h>
 #include <math.h>
@@ -82,6 +85,8 @@ Command parseCommandLine(int argc, char** argv)
    strcpy(cmd.profFile, "profile.dat");
    cmd.mpEvery = 100; cmd.mpSwaps = 1;
    strcpy(cmd.mpFile, "mp.dat");
+   strcpy(cmd.skStride, "1"); cmd.skBins = 50;
+   strcpy(cmd.skFile, "sk.dat");
    int help = 0;
 
    const ArgDef defs[] = {
@@ -174,6 +179,11 @@ Command parseCommandLine(int argc, char** argv)
       { "mpSwaps",       0,  1, 'i', &cmd.mpSwaps,        0, "pairs of atoms an exchange swaps at most, 1..64 (default 1)" },
       { "mpStart",       0,  1, 'i', &cmd.mpStart,        0, "global step exchanging begins at (default 0)" },
       { "mpFile",        0,  1, 's', cmd.mpFile, sizeof cmd.mpFile, "file the exchanges are written to (default mp.dat)" },
+      { "sk",            0,  1, 'i', &cmd.sk,             0, "static structure factor S(k) on the wave vectors 2 pi (sx h / Lx, sy k / Ly, sz l / Lz), h in 0..M, k, l in -M..M, M = 1..64 (0 = off), and the Bragg order, sampled at every printed step (an S111/N column)" },
+      { "skStride",      0,  1, 's', cmd.skStride, sizeof cmd.skStride, "strides of the wave-vector grid, s or sx,sy,sz, each >= 1 with stride * M <= 65536 (default 1; -x,-y,-z gives the reciprocal lattice of the cubic cell)" },
+      { "skBins",        0,  1, 'i', &cmd.skBins,         0, "|k| bins of the powder average, 1..4096 (default 50)" },
+      { "skStart",       0,  1, 'i', &cmd.skStart,        0, "global step structure-factor sampling begins at (0..nSteps; default 0)" },
+      { "skFile",        0,  1, 's', cmd.skFile, sizeof cmd.skFile, "file the time-averaged powder average S(|k|) is written to (default sk.dat)" },
    };
    const int nDefs = (int)(sizeof defs / sizeof defs[0]);
 
@@ -267,6 +277,8 @@ void printCmdYaml(FILE* file, Command* cmd)
       fprintf(file, "  Profile axis: %s\n  Profile bins: %d\n  Profile from step: %d\n  Profile file: %s\n", cmd->profAxis, cmd->profBins, cmd->profStart, cmd->profFile);
    if (cmd->mp)
       fprintf(file, "  MullerPlathe every: %d steps\n  MullerPlathe swaps: %d\n  MullerPlathe from step: %d\n  MullerPlathe file: %s\n", cmd->mpEvery, cmd->mpSwaps, cmd->mpStart, cmd->mpFile);
+   if (cmd->sk) fprintf(file, "  Structure factor kMax index: %d\n  Structure factor stride: %s\n  Structure factor bins: %d\n  Structure factor from step: %d\n  Structure factor file: %s\n",
+                        cmd->sk, cmd->skStride, cmd->skBins, cmd->skStart, cmd->skFile);
    fprintf(file, "\n");
    fflush(file);
 }

@@ -102,6 +102,11 @@ typedef struct CommandSt {
    int mpSwaps;           /* extension: pairs of atoms an exchange swaps at most, 1..64 (default 1) */
    int mpStart;           /* extension: the global step exchanging begins at (default 0) */
    char mpFile[1024];     /* extension: where the print rank writes the exchanges (default mp.dat) */
+   int sk;                /* extension: the static structure factor on the half grid h in [0, M], k, l in [-M, M] and the Bragg order, sampled at the printed steps; M, 0 = off */
+   char skStride[64];     /* extension: the strides of the grid, s or sx,sy,sz (default 1) */
+   int skBins;            /* extension: |k| bins of the powder average, 1..4096 (default 50) */
+   int skStart;           /* extension: the global step sampling begins at (default 0) */
+   char skFile[1024];     /* extension: where the print rank writes the time-averaged powder average (default sk.dat) */
 } Command;
 
 #define COMD_LANGEVIN_SEED 0x436f4d44ull     /* "CoMD" */
@@ -441,6 +446,14 @@ typedef struct SimFlatSt {
    char mpFile[1024];
    RowTable mpRows;                 /* [6] doubles: step, time (fs), kept pairs, skipped pairs, dE (eV), cumulative E (eV) */
    double* mpTable;                 /* comdMullerPlatheSwap: the candidate table of all ranks and its staging, 2 x [2][nRanks * 64][6] */
+   /* structure factor (--sk): at every printed step from global step skStart on comdMain adds the powder average of comdStructureFactor up and samples comdBraggOrder */
+   int cells[3];                    /* the unit cells of -x -y -z: the strides of comdBraggOrder */
+   int sk, skStride[3], skBins, skStart;      /* sk: the largest index M, 0 = off */
+   char skFile[1024];
+   double* skSum;                   /* [2][skBins]: per |k| bin the sum of S over the vectors and samples, and the number of vectors summed (h > 0 twice) */
+   int skSamples;
+   double skBoxSum[3];              /* the extents summed over the samples */
+   double skBraggNow, skBraggFirst, skBraggSum;      /* comdBraggOrder of the last sample, of the first, summed over the samples */
 } SimFlat;
 
 SimFlat* initSimulation(Command cmd);
@@ -618,13 +631,35 @@ int  comdMullerPlatheSwap(SimFlat* s, int axis, int nBins, int k, int* pairsGid,
 int  comdSetMullerPlathe(SimFlat* s, int on, int axis, int nBins, int every, int swaps, int start);
 int  comdGetMullerPlathe(SimFlat* s, double out8[8]);
 int  comdFourierKappa(const double* T, int nBins, double width, double area, double energy, double time, double* gradient, double* kappa);
+/* not in the reference: the static structure factor (hip/sk_kernels.h).  comdStructureFactor and comdBraggOrder are collective: every rank makes each call.
+ * comdStructureFactorRefusal: why a grid is refused: 0 fine, 1 M outside 1..COMD_SK_MAX_M, 2 a stride < 1, 3 a stride * M above COMD_SK_MAX_HM.
+ * comdStructureFactor: the density amplitudes rho(h, k, l) = sum_j exp(-i K . r_j) over the atoms of all ranks, K = 2 pi (stride[0] h / Lx, stride[1] k / Ly,
+ *    stride[2] l / Lz) on the current global extents, h in [0, M], k, l in [-M, M]: outKx2[((h W + k + M) W + l + M) 2 + {0, 1}], W = 2M + 1, real and imaginary
+ *    part.  computeStructureFactor (comd_hip.h) for this rank's atoms, summed over the ranks with addDoubleParallelLong: the same on every rank.  rho(0, 0, 0) is N
+ *    exactly.  One configuration gives the same bits at every call; methods, cell numberings and rank counts order the atoms differently and differ in the
+ *    rounding.  Returns what comdStructureFactorRefusal does, nothing launched; -1 without device state.
+ * comdStructureFactorRadial: plain C, no device: the powder average of such amplitudes on a box of extents box[3].  S = |rho|^2 / N with N = Re rho(0, 0, 0).
+ *    nBins uniform |k| bins up to kMax = min_a 2 pi stride[a] M / box[a], the largest sphere inside the grid: a vector with 0 < |k| <= kMax is in bin
+ *    min(floor(|k| / (kMax / nBins)), nBins - 1), K_a = (2 pi (stride[a] index)) / box[a], |k| = sqrt((Kx^2 + Ky^2) + Kz^2).  A vector with h > 0 counts twice (it
+ *    stands for -K too), one with h = 0 once (the plane holds both); K = 0 is left out.  kCentre[b] = (b + 0.5) kMax / nBins, count[b] the weights, sMean[b] the
+ *    weighted mean of S, NaN where count is 0.  Returns what comdStructureFactorRefusal does, 4 for nBins outside 1..COMD_SK_MAX_BINS, 5 for a box extent or an N
+ *    that is not positive.
+ * comdBraggOrder: the mean over the four reflections (1, +-1, +-1) of S / N at the strides (nx, ny, nz) of -x -y -z, the {111} family of the conventional cubic
+ *    cell: 1 on the perfect lattice, the Debye-Waller factor of a warm crystal, ~1/N in the melt.  One comdStructureFactor call with M = 1.  -1 without device state. */
+#define COMD_SK_MAX_M 64
+#define COMD_SK_MAX_HM 65536
+#define COMD_SK_MAX_BINS 4096
+int  comdStructureFactorRefusal(int M, const int stride[3]);
+int  comdStructureFactor(SimFlat* s, int M, const int stride[3], double* outKx2);
+int  comdStructureFactorRadial(const double* rhoKx2, int M, const int stride[3], const double box[3], int nBins, double* kCentre, double* sMean, double* count);
+int  comdBraggOrder(SimFlat* s, double* out);
 void deformListBudget(SimFlat* s);      /* *_nl: the skin left to the displacement test by the compression since the build; after a box change and after a list build */
 void redistributeAtoms(SimFlat* sim);
 void ensureInteriorForceLaunched(SimFlat* sim);
 
 /* ---- performanceTimers.h ---- */
 enum TimerHandle { totalTimer, loopTimer, timestepTimer, positionTimer, velocityTimer, redistributeTimer, atomHaloTimer,
-                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, cspTimer, cnaTimer, deformTimer, stressTimer, strainTimer, heatfluxTimer, baroTimer, profileTimer, mpTimer, numberOfTimers };
+                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, cspTimer, cnaTimer, deformTimer, stressTimer, strainTimer, heatfluxTimer, baroTimer, profileTimer, mpTimer, skTimer, numberOfTimers };
 void profileStart(enum TimerHandle handle);
 void profileStop(enum TimerHandle handle);
 double getElapsedTime(enum TimerHandle handle);

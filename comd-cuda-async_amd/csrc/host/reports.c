@@ -596,6 +596,58 @@ static void writeHeatFlux(FILE* yaml, SimFlat* s, int iStep)
    fprintf(yaml, "  kappaUnits: W/m/K\n\n");
 }
 
+/* --sk: the amplitudes of this printed step go through the powder average into the sums; the Bragg order is a call of its own (M = 1 at the strides of the cells) */
+static void sampleSk(SimFlat* s, int iStep)
+{
+   const int M = s->sk, W = 2 * M + 1, n = s->skBins;
+   double* rho = (double*)malloc((size_t)2 * (M + 1) * W * W * sizeof(double));
+   double* now = (double*)malloc(3 * (size_t)n * sizeof(double));
+   const double box[3] = { (double)s->domain->globalExtent[0], (double)s->domain->globalExtent[1], (double)s->domain->globalExtent[2] };
+   if (comdStructureFactor(s, M, s->skStride, rho) != 0 || comdBraggOrder(s, &s->skBraggNow) != 0) { printf("Error: --sk needs the device state.\n"); exit(-1); }
+   if (comdStructureFactorRadial(rho, M, s->skStride, box, n, now, now + n, now + 2 * n) != 0) { printf("Error: --sk: the powder average was refused.\n"); exit(-1); }
+   for (int b = 0; b < n; ++b) if (now[2 * n + b] > 0.0) { s->skSum[b] += now[n + b] * now[2 * n + b]; s->skSum[n + b] += now[2 * n + b]; }
+   free(rho); free(now);
+   if (s->skSamples == 0) s->skBraggFirst = s->skBraggNow;
+   s->skBraggSum += s->skBraggNow;
+   for (int a = 0; a < 3; ++a) s->skBoxSum[a] += box[a];
+   s->skSamples++;
+   (void)iStep;
+}
+
+/* --sk: the file and the YAML block.  skFile: a header with N, M, the strides, the bins, the samples and the mean box, then per bin the |k| centre (1/A) on the mean
+ * box, S averaged over the samples and the vectors of the bin, and the vectors per sample (h > 0 twice); an empty bin prints nan */
+static void writeSk(FILE* yaml, SimFlat* s, int iStep)
+{
+   if (!printRank()) return;
+   const int M = s->sk, n = s->skBins, samples = s->skSamples;
+   double box[3], kMax = INFINITY;
+   for (int a = 0; a < 3; ++a) {
+      box[a] = samples ? s->skBoxSum[a] / samples : (double)s->domain->globalExtent[a];
+      const double k = (6.283185307179586 * (double)(s->skStride[a] * M)) / box[a];
+      if (k < kMax) kMax = k;
+   }
+   const double dk = kMax / n;
+   FILE* f = openReport(s->skFile);
+   fprintf(f, "# StructureFactor: N %d M %d stride %d %d %d bins %d samples %d startStep %d meanL %.17g %.17g %.17g A | columns: |k| centre (1/A), S averaged over "
+              "samples and vectors, vectors per sample\n", s->atoms->nGlobal, M, s->skStride[0], s->skStride[1], s->skStride[2], n, samples, s->skStart, box[0], box[1], box[2]);
+   int best = -1;
+   for (int b = 0; b < n; ++b) {
+      const double count = s->skSum[n + b];
+      if (count > 0.0) {
+         const double mean = s->skSum[b] / count;
+         if (best < 0 || mean > s->skSum[best] / s->skSum[n + best]) best = b;
+         fprintf(f, "%.17g %.17g %.17g\n", (b + 0.5) * dk, mean, count / samples);
+      } else fprintf(f, "%.17g nan %.17g\n", (b + 0.5) * dk, 0.0);
+   }
+   fclose(f);
+   if (!yaml) return;
+   fprintf(yaml, "StructureFactor:\n  kMaxIndex: %d\n  stride: [ %d, %d, %d ]\n  bins: %d\n  samples: %d\n  file: %s\n", M, s->skStride[0], s->skStride[1], s->skStride[2], n, samples, s->skFile);
+   if (best >= 0) fprintf(yaml, "  kOfHighestS: %.12e\n", (best + 0.5) * dk); else fprintf(yaml, "  kOfHighestS: n/a\n");
+   if (samples) fprintf(yaml, "  braggFirst: %.12e\n  braggFinal: %.12e\n  braggMean: %.12e\n\n", s->skBraggFirst, s->skBraggNow, s->skBraggSum / samples);
+   else fprintf(yaml, "  braggFirst: n/a\n  braggFinal: n/a\n  braggMean: n/a\n\n");
+   (void)iStep;
+}
+
 /* ---- the table: one row per report, in the order of the columns of printThings and of the YAML blocks ---------------------------------------------------------
  * on      the row applies to this run;
  * from    the first global step it samples at (NULL: 0), start what is done when the run reaches that step: at a printed step under the report's timer, just
@@ -632,11 +684,13 @@ static int strainOn(const SimFlat* s)      { return s->strain; }
 static int heatfluxOn(const SimFlat* s)    { return s->heatflux; }
 static int profileOn(const SimFlat* s)     { return s->profile; }
 static int mpOn(const SimFlat* s)          { return s->mpReport; }
+static int skOn(const SimFlat* s)          { return s->sk; }
 
 static int msdFrom(const SimFlat* s)       { return s->msdStart; }
 static int strainFrom(const SimFlat* s)    { return s->strainRef; }
 static int heatfluxFrom(const SimFlat* s)  { return s->hfStart; }
 static int profileFrom(const SimFlat* s)   { return s->profStart; }
+static int skFrom(const SimFlat* s)        { return s->skStart; }
 
 static double volumeRatio(const SimFlat* s) { return (double)s->V / (s->box0[0] * s->box0[1] * s->box0[2]); }
 static void pressureColumn(const SimFlat* s) { fprintf(screenOut, " %16.10f", pressureOf(s) * eVperA3inGPa); }
@@ -649,6 +703,7 @@ static void stressColumn(const SimFlat* s)   { fprintf(screenOut, " %16.10f", s-
 static void strainColumn(const SimFlat* s)   { fprintf(screenOut, " %16.10f", s->strainMaxShearNow); }
 static void heatfluxColumn(const SimFlat* s) { fprintf(screenOut, " %19.10e", s->hfJxNow); }
 static void mpColumn(const SimFlat* s)       { fprintf(screenOut, " %19.10e", s->mpExchanged); }
+static void skColumn(const SimFlat* s)       { fprintf(screenOut, " %16.10f", s->skBraggNow); }
 
 static const Report reports[] = {
    { .on = virialOn,        .sample = samplePressure, .timer = pressureTimer },      /* first: the samplers below read W, K, V */
@@ -668,6 +723,7 @@ static const Report reports[] = {
      .write = writeHeatFlux, .writeTimed = 1 },
    { .on = profileOn,       .from = profileFrom, .sample = sampleProfile, .timer = profileTimer, .write = writeProfile, .writeTimed = 1 },      /* and the files and the block of --mp */
    { .on = mpOn,            .header = "              dE(eV)", .column = mpColumn },      /* its rows: mpExchange, inside timestep() */
+   { .on = skOn,            .from = skFrom, .sample = sampleSk, .timer = skTimer, .header = "           S111/N", .column = skColumn, .write = writeSk },
 };
 #define FOR_REPORTS(r, s) for (const Report* r = reports; r < reports + sizeof reports / sizeof reports[0]; ++r) if (r->on(s))
 
@@ -715,5 +771,5 @@ void reportsFree(SimFlat* s)
 {
    RowTable* tables[] = { &s->msdRows, &s->cspRows, &s->cnaRows, &s->deformRows, &s->baroRows, &s->mpRows, &s->stressRows, &s->strainRows, &s->hfRows };
    for (size_t i = 0; i < sizeof tables / sizeof tables[0]; ++i) free(tables[i]->rows);
-   free(s->rdfSum); free(s->cspLast); free(s->cnaLast); free(s->profSum);
+   free(s->rdfSum); free(s->cspLast); free(s->cnaLast); free(s->profSum); free(s->skSum);
 }

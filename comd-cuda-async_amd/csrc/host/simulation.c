@@ -251,6 +251,27 @@ SimFlat* initSimulationHost(Command cmd)
          strcpy(sim->mpFile, cmd.mpFile);
       }
    }
+   /* --sk (not in the reference): the settings are checked here, before any step */
+   sim->cells[0] = cmd.nx; sim->cells[1] = cmd.ny; sim->cells[2] = cmd.nz;
+   if (cmd.sk) {
+      int st[3] = { 0, 0, 0 }, used = 0;
+      const int got = sscanf(cmd.skStride, "%d,%d,%d%n", &st[0], &st[1], &st[2], &used);
+      if (got == 3 && cmd.skStride[used] == '\0') ;
+      else if (got >= 1 && sscanf(cmd.skStride, "%d%n", &st[0], &used) == 1 && cmd.skStride[used] == '\0') st[1] = st[2] = st[0];
+      else { printf("Error: --skStride must be s or sx,sy,sz (got '%s').\n", cmd.skStride); exit(-1); }
+      switch (comdStructureFactorRefusal(cmd.sk, st)) {
+         case 0: break;
+         case 1: printf("Error: --sk must lie in 1..%d (got %d).\n", COMD_SK_MAX_M, cmd.sk); exit(-1);
+         case 2: printf("Error: --skStride needs strides >= 1 (got '%s').\n", cmd.skStride); exit(-1);
+         default: printf("Error: --skStride times --sk must not exceed %d (got '%s' and %d).\n", COMD_SK_MAX_HM, cmd.skStride, cmd.sk); exit(-1);
+      }
+      if (cmd.skBins < 1 || cmd.skBins > COMD_SK_MAX_BINS) { printf("Error: --skBins must lie in 1..%d (got %d).\n", COMD_SK_MAX_BINS, cmd.skBins); exit(-1); }
+      if (cmd.skStart < 0 || cmd.skStart > cmd.nSteps) { printf("Error: --skStart must lie in 0..nSteps = 0..%d (got %d).\n", cmd.nSteps, cmd.skStart); exit(-1); }
+      sim->sk = cmd.sk; sim->skBins = cmd.skBins; sim->skStart = cmd.skStart;
+      for (int a = 0; a < 3; ++a) sim->skStride[a] = st[a];
+      strcpy(sim->skFile, cmd.skFile);
+      sim->skSum = (double*)calloc(2 * (size_t)cmd.skBins, sizeof(double));
+   }
    sanityChecks(cmd, sim->pot->cutoff, latticeConstant, sim->pot->latticeType);
    sim->species = initSpecies(sim->pot);
 

@@ -266,6 +266,8 @@ typedef struct SimGpuSt {
    int          profileCap;
    double*      mpBuf;                 /* device: the workgroups' candidate records of computeMullerPlatheCandidates and the merged lists, allocated by its first call */
    void*        mpRows;                /* device: the (slot, momentum) rows of comdMullerPlatheApplyGpu, allocated by its first call */
+   double*      skBuf;                 /* device [chunks + 1][K][2]: the chunks' amplitudes of computeStructureFactor and their sum, allocated by its first call and when they grow */
+   uint64_t     skCap;                 /* doubles in skBuf */
 } SimGpu;
 
 /* Everything AllocateGpu needs to know about the rank's geometry and potential.
@@ -494,6 +496,13 @@ void comdSetFacePairsGpu(SimGpu* sim, const int* rows5, int nRows);
  * Same stream and ordering as computeVirial; e[] is current after a force evaluation that carried energies (comdSetEnergyNeeded).  Reads r, p, e and the cell
  * tables, writes only its own buffer.  Blocks until the result is on the host.  Exits on a bad axis or bin count. */
 void computeSlabProfile(SimGpu* sim, int axis, int nBins, double extent, int64_t* out6xN);
+/* Not in the reference: the density amplitudes of the static structure factor (hip/sk_kernels.h) of THIS rank's local atoms on the half grid of wave vectors
+ * K = 2 pi (stride3[0] h / extent3[0], stride3[1] k / extent3[1], stride3[2] l / extent3[2]), h in [0, M], k, l in [-M, M]: outKx2[((h W + k + M) W + l + M) 2 + {0, 1}],
+ * W = 2M + 1, the real and imaginary part of sum_j exp(-i K . r_j) as doubles.  1 <= M <= 64, every stride >= 1 with stride M <= 65536.  The phases come from the
+ * fractional coordinates in double, so positions outside the box need no wrap.  The chunks' sums are added in a fixed order: one configuration gives the same
+ * bits at every call; another method, cell numbering, chunk count (COMD_SK_CHUNKS) or rank count orders the atoms differently and rounds differently.  Same stream
+ * and ordering as computeVirial.  Reads r and the cell tables, writes only its own buffer.  Blocks until the result is on the host.  Exits on bad arguments. */
+void computeStructureFactor(SimGpu* sim, int M, const int* stride3, const double* extent3, double* outKx2);
 /* Not in the reference: the candidates of a Mueller-Plathe momentum exchange (hip/mp_kernels.h) among THIS rank's local atoms, with the bins of computeSlabProfile
  * (nBins even): out[0][j], j < k, the atom of the j-th largest kinetic energy in slab 0, out[1][j] the atom of the j-th smallest in slab nBins / 2, 1 <= k <= 64.
  * Order: by (KE, gid), among equal KE the lower gid first in both lists, so the lists are fully determined.  A record is 6 doubles {KE, gid, p_x, p_y, p_z, slot}
