@@ -250,20 +250,22 @@ typedef struct HaloSpecSt {
    int   lastCount[4];                    /* ... and the counts those sizes were derived from (both ends of a message hold the same two numbers) */
 } HaloSpec;
 
+enum HaloKind { HALO_ATOMS, HALO_FORCE, HALO_POSITIONS };      /* whole atoms; dF/drho, 1 real per atom; positions + face shift, 3 reals per atom */
+
 typedef struct HaloExchangeSt {
    int nbrRank[6];
    int bufCapacity;                       /* bytes per message buffer */
-   int (*loadBuffer)(void* parms, void* data, int face, char* buf);       /* returns bytes, or -1: "ask msgBytes when you need it" */
-   int (*msgBytes)(void* parms, void* data, int face, char* buf);         /* optional: size of a packed device message (blocks) */
-   /* optional: both messages of an axis phase behind one synchronisation */
-   void (*msgBytes2)(void* parms, void* data, int faceM, char* bufM, int faceP, char* bufP, int out[2]);
+   /* the device exchanges: both faces of an axis phase packed / unpacked by one device launch each.  nBytes -1: "ask msgBytes2 when you need it" */
+   void (*loadBuffer2)(struct HaloExchangeSt* hh, void* data, int faceM, char* bufM, int faceP, char* bufP, int nBytes[2]);
+   void (*unloadBuffer2)(struct HaloExchangeSt* hh, void* data, int faceA, int bufSizeA, char* bufA, int faceB, int bufSizeB, char* bufB);
+   /* sizes of the two packed device messages of an axis phase, behind one synchronisation at the most */
+   void (*msgBytes2)(struct HaloExchangeSt* hh, void* data, int faceM, char* bufM, int faceP, char* bufP, int out[2]);
+   /* the reference's one-face plugin shape, used where loadBuffer2 / unloadBuffer2 are NULL: comdHaloExchangeHost fills them with its caller's host callbacks */
+   int (*loadBuffer)(void* parms, void* data, int face, char* buf);       /* returns bytes */
    void (*unloadBuffer)(void* parms, void* data, int face, int bufSize, char* buf);
-   /* optional: both faces of an axis phase packed / unpacked by one device launch each (same results as two loadBuffer / unloadBuffer calls) */
-   void (*loadBuffer2)(void* parms, void* data, int faceM, char* bufM, int faceP, char* bufP, int nBytes[2]);
-   void (*unloadBuffer2)(void* parms, void* data, int faceA, int bufSizeA, char* bufA, int faceB, int bufSizeB, char* bufB);
    void (*destroy)(void* parms);
    void* parms;
-   int type;                              /* 0 atoms, 1 force, 2 positions */
+   enum HaloKind kind;
    int deviceBuffers;                     /* 1: the four buffers are device memory */
    char *sendBufM, *sendBufP, *recvBufM, *recvBufP;
    /* size agreement without a handshake (device buffers, messages that leave the rank) */
@@ -296,15 +298,13 @@ typedef struct ForceExchangeParmsSt {
    int *sendCells[6], *recvCells[6];
    int *sendCellsGpu[6], *recvCellsGpu[6];
    int *sendOffsetsGpu[6], *recvOffsetsGpu[6];   /* device, nCells + 1 each: filled by one batched scan per step */
-   int* d_cellOffsets;
    int capacityAtoms;
-   int positions;                         /* 0: dF/drho (1 real per atom); 1: positions + face shift (3 reals per atom) */
    /* mirror map of the self-neighbour tail firstAxis..2 (built on first use): halo cell mirrorDst[k] is the image of mirrorSrc[k] displaced by mirrorShift[3k..] */
    int mirrorFirst, mirrorPairs;
    int *mirrorDstGpu, *mirrorSrcGpu; real_t* mirrorShiftGpu;
    int mirrorStale;                       /* haloSetBox: shift[][] has changed since mirrorShiftGpu was filled */
    real_t shift[6][3];
-   int msgBytesCached[6];                 /* positions: message sizes are fixed between list builds; -1 = unknown */
+   int msgBytesCached[6];                 /* message sizes of the last blocking read; positions: fixed between list builds, so kept; -1 = unknown */
    int sendBound[6];                      /* agreed message sizes in atoms, 0 = none */
 } ForceExchangeParms;
 

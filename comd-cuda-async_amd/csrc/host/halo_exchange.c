@@ -3,11 +3,12 @@
  * Same protocol as the reference (haloExchange.c:8-29, exchangeData :1493-1522): per axis pack the minus and plus
  * faces, exchange both, then unpack minus and plus -- the order that keeps migrating atoms from being duplicated.
  * Same cell lists (mkAtomCellList :1543-1567, mkForceSend/RecvCellList :1712-1801), same periodic shifts (:316-323),
- * same HaloExchange {loadBuffer, unloadBuffer, destroy} plugin shape (haloExchange.h:84-104).
+ * same HaloExchange {loadBuffer, unloadBuffer, destroy} plugin shape (haloExchange.h:84-104), with both faces of an axis
+ * phase behind one call (loadBuffer2, unloadBuffer2); the one-face slots serve comdHaloExchangeHost's host callbacks only.
  *
- * What differs: messages never leave the device.  loadBuffer runs the pack kernels into a device buffer, the
+ * What differs: messages never leave the device.  loadBuffer2 runs the pack kernels into device buffers, the
  * transport moves device memory (RCCL send/recv over xGMI between ranks; nothing at all when a rank is its own
- * periodic neighbour), unloadBuffer runs the unpack kernels.  The reference stages every message through pinned
+ * periodic neighbour), unloadBuffer2 runs the unpack kernels.  The reference stages every message through pinned
  * host memory and blocks on six count read-backs per exchange (haloExchange.c:1632-1633, gpu_kernels.cu:534-535).
  * The whole GPUDirect-Async / libmp machinery of haloExchange.c:498-1366 has no counterpart by design.
  *
@@ -100,29 +101,11 @@ static int* uploadInts(const int* h, int n)
 }
 
 /* ---- atom exchange plugin ---------------------------------------------------------------------------- */
-static int loadAtomsBuffer(void* vparms, void* data, int face, char* buf)
-{
-   AtomExchangeParms* parms = (AtomExchangeParms*)vparms;
-   SimFlat* sim = (SimFlat*)data;
-   const int bound = parms->sendBound[face] > 0 && parms->sendBound[face] < parms->capacityAtoms ? parms->sendBound[face] : parms->capacityAtoms;
-   compactCellsGpu(buf, parms->nCells[face], parms->cellListGpu[face], &sim->gpu, parms->d_cellOffsets,
-                   parms->shift[face], bound, sim->gpu.boundary_stream);
-   return -1;            /* the count stays on the device (message header); exchangeData asks msgBytes only if a peer needs it */
-}
-
 /* blocking: the reference reads this count back after every pack (gpu_kernels.cu:534-535); here only when the message leaves the rank,
  * and after BOTH faces of the axis have been packed, so one stream drain serves the two reads */
-static int atomsMsgBytes(void* vparms, void* data, int face, char* buf)
+static void atomsMsgBytes2(HaloExchange* hh, void* data, int faceM, char* bufM, int faceP, char* bufP, int out[2])
 {
-   (void)vparms; (void)face;
-   SimFlat* sim = (SimFlat*)data;
-   int n = atomMsgCountGpu(&sim->gpu, buf, sim->gpu.boundary_stream);
-   return COMD_ATOM_MSG_HEADER + n * COMD_ATOM_MSG_BYTES_PER_ATOM;
-}
-
-static void atomsMsgBytes2(void* vparms, void* data, int faceM, char* bufM, int faceP, char* bufP, int out[2])
-{
-   (void)vparms; (void)faceM; (void)faceP;
+   (void)hh; (void)faceM; (void)faceP;
    SimFlat* sim = (SimFlat*)data;
    int n[2];
    comdReadDeviceInt2((const int*)bufM, (const int*)bufP, n, sim->gpu.boundary_stream);      /* the counts sit in the message headers */
@@ -130,18 +113,9 @@ static void atomsMsgBytes2(void* vparms, void* data, int faceM, char* bufM, int 
    out[1] = COMD_ATOM_MSG_HEADER + n[1] * COMD_ATOM_MSG_BYTES_PER_ATOM;
 }
 
-static void unloadAtomsBuffer(void* vparms, void* data, int face, int bufSize, char* buf)
+static void loadAtomsBuffer2(HaloExchange* hh, void* data, int faceM, char* bufM, int faceP, char* bufP, int nBytes[2])
 {
-   AtomExchangeParms* parms = (AtomExchangeParms*)vparms;
-   SimFlat* sim = (SimFlat*)data;
-   int nBuf = bufSize < 0 ? -1 : (bufSize - COMD_ATOM_MSG_HEADER) / COMD_ATOM_MSG_BYTES_PER_ATOM;
-   const int bound = nBuf < 0 && parms->recvBound[face] > 0 && parms->recvBound[face] < parms->capacityAtoms ? parms->recvBound[face] : parms->capacityAtoms;
-   unloadAtomsBufferToGpu(buf, nBuf, bound, &sim->gpu, sim->gpu.boundary_stream);
-}
-
-static void loadAtomsBuffer2(void* vparms, void* data, int faceM, char* bufM, int faceP, char* bufP, int nBytes[2])
-{
-   AtomExchangeParms* parms = (AtomExchangeParms*)vparms;
+   AtomExchangeParms* parms = (AtomExchangeParms*)hh->parms;
    SimFlat* sim = (SimFlat*)data;
    const int f[2] = { faceM, faceP };
    int nCells[2], caps[2]; int* lists[2]; int* offs[2] = { parms->d_cellOffsets, parms->d_cellOffsets2 };
@@ -150,12 +124,12 @@ static void loadAtomsBuffer2(void* vparms, void* data, int faceM, char* bufM, in
       caps[k] = parms->sendBound[f[k]] > 0 && parms->sendBound[f[k]] < parms->capacityAtoms ? parms->sendBound[f[k]] : parms->capacityAtoms;
    }
    compactCellsGpu2(bufM, bufP, nCells, lists, &sim->gpu, offs, parms->shift[faceM], parms->shift[faceP], caps, sim->gpu.boundary_stream);
-   nBytes[0] = nBytes[1] = -1;              /* counts stay on the device (message headers) */
+   nBytes[0] = nBytes[1] = -1;              /* counts stay on the device (message headers); exchangeData asks msgBytes2 only if a peer needs them */
 }
 
-static void unloadAtomsBuffer2(void* vparms, void* data, int faceA, int bufSizeA, char* bufA, int faceB, int bufSizeB, char* bufB)
+static void unloadAtomsBuffer2(HaloExchange* hh, void* data, int faceA, int bufSizeA, char* bufA, int faceB, int bufSizeB, char* bufB)
 {
-   AtomExchangeParms* parms = (AtomExchangeParms*)vparms;
+   AtomExchangeParms* parms = (AtomExchangeParms*)hh->parms;
    SimFlat* sim = (SimFlat*)data;
    const int f[2] = { faceA, faceB }, size[2] = { bufSizeA, bufSizeB };
    int nBuf[2], bound[2];
@@ -206,17 +180,13 @@ HaloExchange* initAtomHaloExchange(Domain* domain, LinkCell* boxes, int allocDev
    AtomExchangeParms* parms = (AtomExchangeParms*)calloc(1, sizeof(AtomExchangeParms));
    parms->capacityAtoms = maxSize * 2 * boxes->maxAtoms;
    hh->bufCapacity = COMD_ATOM_MSG_HEADER + parms->capacityAtoms * COMD_ATOM_MSG_BYTES_PER_ATOM;
-   hh->loadBuffer = loadAtomsBuffer;
-   hh->msgBytes = atomsMsgBytes;
-   hh->msgBytes2 = atomsMsgBytes2;
-   hh->unloadBuffer = unloadAtomsBuffer;
    hh->destroy = destroyAtomsExchange;
    parms->nCells[HALO_X_MINUS] = parms->nCells[HALO_X_PLUS] = 2 * size0;
    parms->nCells[HALO_Y_MINUS] = parms->nCells[HALO_Y_PLUS] = 2 * size1;
    parms->nCells[HALO_Z_MINUS] = parms->nCells[HALO_Z_PLUS] = 2 * size2;
    for (int f = 0; f < 6; ++f) parms->cellList[f] = mkAtomCellList(boxes, (enum HaloFaceOrder)f, parms->nCells[f]);
    faceShifts(domain, parms->shift);
-   hh->type = 0;
+   hh->kind = HALO_ATOMS;
    hh->parms = parms;
    hh->deviceBuffers = allocDevice;
    hh->nTotalBoxes = boxes->nTotalBoxes; if (allocDevice) hh->mirror = atomsMirror;
@@ -226,50 +196,43 @@ HaloExchange* initAtomHaloExchange(Domain* domain, LinkCell* boxes, int allocDev
       for (int f = 0; f < 6; ++f) parms->cellListGpu[f] = uploadInts(parms->cellList[f], parms->nCells[f]);
       parms->d_cellOffsets = (int*)comdDeviceMalloc((long)(2 * maxSize + 1) * sizeof(int));
       parms->d_cellOffsets2 = (int*)comdDeviceMalloc((long)(2 * maxSize + 1) * sizeof(int));
-      hh->loadBuffer2 = loadAtomsBuffer2; hh->unloadBuffer2 = unloadAtomsBuffer2;
+      hh->loadBuffer2 = loadAtomsBuffer2; hh->unloadBuffer2 = unloadAtomsBuffer2; hh->msgBytes2 = atomsMsgBytes2;
       hh->sendBufM = (char*)comdDeviceMalloc(hh->bufCapacity); hh->sendBufP = (char*)comdDeviceMalloc(hh->bufCapacity);
       hh->recvBufM = (char*)comdDeviceMalloc(hh->bufCapacity); hh->recvBufP = (char*)comdDeviceMalloc(hh->bufCapacity);
    }
    return hh;
 }
 
-/* ---- force (dfEmbed) exchange plugin --------------------------------------------------------------------- */
-static int loadForceBuffer(void* vparms, void* vdata, int face, char* buf)
+/* ---- the slot-addressed exchanges: force (dfEmbed) and position refresh (Verlet-list mode) -------------------------
+ * Between list builds nothing is re-binned, so the halo cells of a rank hold the same atoms, in the same slots, as the send
+ * cells of its neighbour did at the build: the position exchange is positional, exactly like dF/drho, with three reals per atom
+ * and the periodic shift of the face added on the way out.  Cell lists, growing x -> y -> z footprint and buffers are those of
+ * the force exchange.  (The reference re-sends whole atoms and looks their slots up in a gid hash table,
+ * haloExchange.c:1622-1700.) */
+static void loadSlotBuffer2(HaloExchange* hh, void* vdata, int faceM, char* bufM, int faceP, char* bufP, int nBytes[2])
 {
-   ForceExchangeParms* parms = (ForceExchangeParms*)vparms;
-   SimFlat* s = (SimFlat*)vdata;
-   s->gpu.msgBoundAtoms = parms->sendBound[face];
-   loadForceBufferFromGpu((real_t*)buf, parms->nCells[face], parms->sendCellsGpu[face], parms->sendOffsetsGpu[face], &s->gpu, s->gpu.boundary_stream);
-   s->gpu.msgBoundAtoms = 0;
-   return -1;
-}
-
-static void loadSlotBuffer2(void* vparms, void* vdata, int faceM, char* bufM, int faceP, char* bufP, int nBytes[2])
-{
-   ForceExchangeParms* parms = (ForceExchangeParms*)vparms;
+   ForceExchangeParms* parms = (ForceExchangeParms*)hh->parms;
    SimFlat* s = (SimFlat*)vdata;
    const int f[2] = { faceM, faceP };
    int nCells[2], bounds[2]; int* lists[2]; int* offs[2];
    for (int k = 0; k < 2; ++k) { nCells[k] = parms->nCells[f[k]]; lists[k] = parms->sendCellsGpu[f[k]]; offs[k] = parms->sendOffsetsGpu[f[k]]; bounds[k] = parms->sendBound[f[k]]; }
-   if (parms->positions) {
+   if (hh->kind == HALO_POSITIONS)
       loadPositionBufferFromGpu2((real_t*)bufM, (real_t*)bufP, nCells, lists, offs, bounds, parms->shift[faceM], parms->shift[faceP], &s->gpu, s->gpu.boundary_stream);
-      nBytes[0] = parms->msgBytesCached[faceM]; nBytes[1] = parms->msgBytesCached[faceP];
-   } else {
+   else
       loadForceBufferFromGpu2((real_t*)bufM, (real_t*)bufP, nCells, lists, offs, bounds, &s->gpu, s->gpu.boundary_stream);
-      nBytes[0] = nBytes[1] = -1;
-   }
+   nBytes[0] = nBytes[1] = -1;              /* the counts are the totals of the scan, on the device */
 }
 
-static void unloadSlotBuffer2(void* vparms, void* vdata, int faceA, int bufSizeA, char* bufA, int faceB, int bufSizeB, char* bufB)
+static void unloadSlotBuffer2(HaloExchange* hh, void* vdata, int faceA, int bufSizeA, char* bufA, int faceB, int bufSizeB, char* bufB)
 {
-   ForceExchangeParms* parms = (ForceExchangeParms*)vparms;
+   ForceExchangeParms* parms = (ForceExchangeParms*)hh->parms;
    SimFlat* s = (SimFlat*)vdata;
-   (void)bufSizeA; (void)bufSizeB;         /* positional */
+   (void)bufSizeA; (void)bufSizeB;         /* positional: the receive cells hold the same atoms, in gid order, as the sender's send cells */
    const int f[2] = { faceA, faceB };
    int nCells[2]; int* lists[2]; int* offs[2];
    for (int k = 0; k < 2; ++k) { nCells[k] = parms->nCells[f[k]]; lists[k] = parms->recvCellsGpu[f[k]]; offs[k] = parms->recvOffsetsGpu[f[k]]; }
-   if (parms->positions) unloadPositionBufferToGpu2((const real_t*)bufA, (const real_t*)bufB, nCells, lists, offs, &s->gpu, s->gpu.boundary_stream);
-   else                  unloadForceBufferToGpu2((const real_t*)bufA, (const real_t*)bufB, nCells, lists, offs, &s->gpu, s->gpu.boundary_stream);
+   if (hh->kind == HALO_POSITIONS) unloadPositionBufferToGpu2((const real_t*)bufA, (const real_t*)bufB, nCells, lists, offs, &s->gpu, s->gpu.boundary_stream);
+   else                            unloadForceBufferToGpu2((const real_t*)bufA, (const real_t*)bufB, nCells, lists, offs, &s->gpu, s->gpu.boundary_stream);
 }
 
 /* force and position messages: the counts are the totals of the batched scan (send lists: what leaves; receive lists: what must arrive) */
@@ -287,31 +250,19 @@ static void forceSetBounds(void* vparms, int face, int sendBoundAtoms, int recvB
    ((ForceExchangeParms*)vparms)->sendBound[face] = sendBoundAtoms;
 }
 
-static int forceMsgBytes(void* vparms, void* vdata, int face, char* buf)
-{
-   (void)buf;
-   ForceExchangeParms* parms = (ForceExchangeParms*)vparms;
-   SimFlat* s = (SimFlat*)vdata;
-   int n = comdReadDeviceInt(parms->sendOffsetsGpu[face] + parms->nCells[face], s->gpu.boundary_stream);
-   return n * (int)sizeof(real_t);
-}
-
-static void forceMsgBytes2(void* vparms, void* vdata, int faceM, char* bufM, int faceP, char* bufP, int out[2])
+/* one blocking read for both faces.  Positions: message sizes cannot change between list builds -- read once, then cached */
+static void slotMsgBytes2(HaloExchange* hh, void* vdata, int faceM, char* bufM, int faceP, char* bufP, int out[2])
 {
    (void)bufM; (void)bufP;
-   ForceExchangeParms* parms = (ForceExchangeParms*)vparms;
+   ForceExchangeParms* parms = (ForceExchangeParms*)hh->parms;
    SimFlat* s = (SimFlat*)vdata;
-   int n[2];
-   comdReadDeviceInt2(parms->sendOffsetsGpu[faceM] + parms->nCells[faceM], parms->sendOffsetsGpu[faceP] + parms->nCells[faceP], n, s->gpu.boundary_stream);
-   out[0] = n[0] * (int)sizeof(real_t); out[1] = n[1] * (int)sizeof(real_t);
-}
-
-static void unloadForceBuffer(void* vparms, void* vdata, int face, int bufSize, char* buf)
-{
-   ForceExchangeParms* parms = (ForceExchangeParms*)vparms;
-   SimFlat* s = (SimFlat*)vdata;
-   (void)bufSize;       /* positional: the receive cells hold the same atoms, in gid order, as the sender's send cells */
-   unloadForceBufferToGpu((const real_t*)buf, parms->nCells[face], parms->recvCellsGpu[face], parms->recvOffsetsGpu[face], &s->gpu, s->gpu.boundary_stream);
+   const int cached = hh->kind == HALO_POSITIONS;
+   if (!cached || parms->msgBytesCached[faceM] < 0 || parms->msgBytesCached[faceP] < 0) {
+      int n[2];
+      comdReadDeviceInt2(parms->sendOffsetsGpu[faceM] + parms->nCells[faceM], parms->sendOffsetsGpu[faceP] + parms->nCells[faceP], n, s->gpu.boundary_stream);
+      parms->msgBytesCached[faceM] = n[0] * hh->msgBytesPerAtom; parms->msgBytesCached[faceP] = n[1] * hh->msgBytesPerAtom;
+   }
+   out[0] = parms->msgBytesCached[faceM]; out[1] = parms->msgBytesCached[faceP];
 }
 
 static void destroyForceExchange(void* vparms)
@@ -322,7 +273,6 @@ static void destroyForceExchange(void* vparms)
       comdDeviceFree(parms->sendCellsGpu[f]); comdDeviceFree(parms->recvCellsGpu[f]);
       comdDeviceFree(parms->sendOffsetsGpu[f]); comdDeviceFree(parms->recvOffsetsGpu[f]);
    }
-   comdDeviceFree(parms->d_cellOffsets);
 }
 
 /* [round 4] Self-neighbour axes at the END of the x -> y -> z sequence (all three on one rank; y and z on a 2 x 1 x 1 grid; z on 2 x 2 x 1): every halo
@@ -377,10 +327,11 @@ static void slotMirror(HaloExchange* hh, void* vdata, int firstAxis)
       parms->mirrorFirst = firstAxis; parms->mirrorPairs = n; parms->mirrorStale = 0;
       free(dst); free(src); free(sh); free(rootOf); free(shiftOf);
    }
-   mirrorSlotCellsGpu(parms->positions ? 1 : 0, parms->mirrorPairs, parms->mirrorDstGpu, parms->mirrorSrcGpu, parms->mirrorShiftGpu, &s->gpu, s->gpu.boundary_stream);
+   mirrorSlotCellsGpu(hh->kind == HALO_POSITIONS ? 1 : 0, parms->mirrorPairs, parms->mirrorDstGpu, parms->mirrorSrcGpu, parms->mirrorShiftGpu, &s->gpu, s->gpu.boundary_stream);
 }
 
-HaloExchange* initForceHaloExchange(Domain* domain, LinkCell* boxes, int allocDevice)
+/* force and positions: same cell lists, offsets and buffers; positions carry 3x the payload and the periodic shift of the face */
+static HaloExchange* initSlotHaloExchange(Domain* domain, LinkCell* boxes, int allocDevice, enum HaloKind kind)
 {
    HaloExchange* hh = initHaloExchangeBase(domain);
    const int* g = boxes->gridSize;
@@ -388,91 +339,8 @@ HaloExchange* initForceHaloExchange(Domain* domain, LinkCell* boxes, int allocDe
    const int maxSize = MAXI(size0, MAXI(size1, size2));
    ForceExchangeParms* parms = (ForceExchangeParms*)calloc(1, sizeof(ForceExchangeParms));
    parms->capacityAtoms = maxSize * boxes->maxAtoms;
-   hh->bufCapacity = parms->capacityAtoms * (int)sizeof(real_t);
-   hh->loadBuffer = loadForceBuffer;
-   hh->msgBytes = forceMsgBytes;
-   hh->msgBytes2 = forceMsgBytes2;
-   hh->unloadBuffer = unloadForceBuffer;
-   hh->destroy = destroyForceExchange;
-   parms->nCells[HALO_X_MINUS] = parms->nCells[HALO_X_PLUS] = size0;
-   parms->nCells[HALO_Y_MINUS] = parms->nCells[HALO_Y_PLUS] = size1;
-   parms->nCells[HALO_Z_MINUS] = parms->nCells[HALO_Z_PLUS] = size2;
-   for (int f = 0; f < 6; ++f) {
-      parms->sendCells[f] = mkForceSendCellList(boxes, f, parms->nCells[f]);
-      parms->recvCells[f] = mkForceRecvCellList(boxes, f, parms->nCells[f]);
-   }
-   hh->type = 1;
-   hh->parms = parms;
-   hh->deviceBuffers = allocDevice;
-   hh->nTotalBoxes = boxes->nTotalBoxes; if (allocDevice) hh->mirror = slotMirror;
-   hh->msgHeaderBytes = 0; hh->msgBytesPerAtom = (int)sizeof(real_t); hh->capacityAtoms = parms->capacityAtoms;
-   hh->countPtrs = forceCountPtrs; hh->setBounds = forceSetBounds;
-   if (allocDevice) { hh->loadBuffer2 = loadSlotBuffer2; hh->unloadBuffer2 = unloadSlotBuffer2; }
-   if (allocDevice) {
-      for (int f = 0; f < 6; ++f) {
-         parms->sendCellsGpu[f] = uploadInts(parms->sendCells[f], parms->nCells[f]);
-         parms->recvCellsGpu[f] = uploadInts(parms->recvCells[f], parms->nCells[f]);
-         parms->sendOffsetsGpu[f] = (int*)comdDeviceMalloc((long)(parms->nCells[f] + 1) * sizeof(int));
-         parms->recvOffsetsGpu[f] = (int*)comdDeviceMalloc((long)(parms->nCells[f] + 1) * sizeof(int));
-      }
-      parms->d_cellOffsets = (int*)comdDeviceMalloc((long)(maxSize + 1) * sizeof(int));
-      hh->sendBufM = (char*)comdDeviceMalloc(hh->bufCapacity); hh->sendBufP = (char*)comdDeviceMalloc(hh->bufCapacity);
-      hh->recvBufM = (char*)comdDeviceMalloc(hh->bufCapacity); hh->recvBufP = (char*)comdDeviceMalloc(hh->bufCapacity);
-   }
-   return hh;
-}
-
-/* ---- position refresh plugin (Verlet-list mode) ----------------------------------------------------------------
- * Between list builds nothing is re-binned, so the halo cells of a rank hold the same atoms, in the same slots, as the send
- * cells of its neighbour did at the build: the exchange is positional, exactly like dF/drho, with three reals per atom and
- * the periodic shift of the face added on the way out.  Cell lists, growing x -> y -> z footprint and buffers are those of
- * initForceHaloExchange.  (The reference re-sends whole atoms and looks their slots up in a gid hash table,
- * haloExchange.c:1622-1700.)  Message sizes cannot change between builds: read once, then cached. */
-static int loadPositionBuffer(void* vparms, void* vdata, int face, char* buf)
-{
-   ForceExchangeParms* parms = (ForceExchangeParms*)vparms;
-   SimFlat* s = (SimFlat*)vdata;
-   s->gpu.msgBoundAtoms = parms->sendBound[face];
-   loadPositionBufferFromGpu((real_t*)buf, parms->nCells[face], parms->sendCellsGpu[face], parms->sendOffsetsGpu[face], parms->shift[face],
-                             &s->gpu, s->gpu.boundary_stream);
-   s->gpu.msgBoundAtoms = 0;
-   return parms->msgBytesCached[face];
-}
-
-static int positionMsgBytes(void* vparms, void* vdata, int face, char* buf)
-{
-   (void)buf;
-   ForceExchangeParms* parms = (ForceExchangeParms*)vparms;
-   SimFlat* s = (SimFlat*)vdata;
-   if (parms->msgBytesCached[face] < 0) {
-      int n = comdReadDeviceInt(parms->sendOffsetsGpu[face] + parms->nCells[face], s->gpu.boundary_stream);
-      parms->msgBytesCached[face] = 3 * n * (int)sizeof(real_t);
-   }
-   return parms->msgBytesCached[face];
-}
-
-static void unloadPositionBuffer(void* vparms, void* vdata, int face, int bufSize, char* buf)
-{
-   ForceExchangeParms* parms = (ForceExchangeParms*)vparms;
-   SimFlat* s = (SimFlat*)vdata;
-   (void)bufSize;
-   unloadPositionBufferToGpu((const real_t*)buf, parms->nCells[face], parms->recvCellsGpu[face], parms->recvOffsetsGpu[face], &s->gpu, s->gpu.boundary_stream);
-}
-
-HaloExchange* initPositionHaloExchange(Domain* domain, LinkCell* boxes, int allocDevice)
-{
-   /* same cell lists and offsets as the force exchange; 3x the payload */
-   HaloExchange* hh = initHaloExchangeBase(domain);
-   const int* g = boxes->gridSize;
-   const int size0 = g[1] * g[2], size1 = (g[0] + 2) * g[2], size2 = (g[0] + 2) * (g[1] + 2);
-   const int maxSize = MAXI(size0, MAXI(size1, size2));
-   ForceExchangeParms* parms = (ForceExchangeParms*)calloc(1, sizeof(ForceExchangeParms));
-   parms->positions = 1;
-   parms->capacityAtoms = maxSize * boxes->maxAtoms;
-   hh->bufCapacity = 3 * parms->capacityAtoms * (int)sizeof(real_t);
-   hh->loadBuffer = loadPositionBuffer;
-   hh->msgBytes = positionMsgBytes;
-   hh->unloadBuffer = unloadPositionBuffer;
+   hh->msgHeaderBytes = 0; hh->msgBytesPerAtom = (kind == HALO_POSITIONS ? 3 : 1) * (int)sizeof(real_t); hh->capacityAtoms = parms->capacityAtoms;
+   hh->bufCapacity = parms->capacityAtoms * hh->msgBytesPerAtom;
    hh->destroy = destroyForceExchange;
    parms->nCells[HALO_X_MINUS] = parms->nCells[HALO_X_PLUS] = size0;
    parms->nCells[HALO_Y_MINUS] = parms->nCells[HALO_Y_PLUS] = size1;
@@ -482,36 +350,45 @@ HaloExchange* initPositionHaloExchange(Domain* domain, LinkCell* boxes, int allo
       parms->recvCells[f] = mkForceRecvCellList(boxes, f, parms->nCells[f]);
       parms->msgBytesCached[f] = -1;
    }
-   faceShifts(domain, parms->shift);
-   hh->type = 2;
+   if (kind == HALO_POSITIONS) faceShifts(domain, parms->shift);
+   hh->kind = kind;
    hh->parms = parms;
    hh->deviceBuffers = allocDevice;
-   hh->nTotalBoxes = boxes->nTotalBoxes; if (allocDevice) hh->mirror = slotMirror;
-   hh->msgHeaderBytes = 0; hh->msgBytesPerAtom = 3 * (int)sizeof(real_t); hh->capacityAtoms = parms->capacityAtoms;
+   hh->nTotalBoxes = boxes->nTotalBoxes;
    hh->countPtrs = forceCountPtrs; hh->setBounds = forceSetBounds;
-   if (allocDevice) { hh->loadBuffer2 = loadSlotBuffer2; hh->unloadBuffer2 = unloadSlotBuffer2; }
-   hh->exactCounts = 1;                      /* slots are frozen between list builds: the counts of the first exchange hold until the next build */
+   hh->exactCounts = kind == HALO_POSITIONS;      /* slots are frozen between list builds: the counts of the first exchange hold until the next build */
    if (allocDevice) {
+      hh->mirror = slotMirror;
+      hh->loadBuffer2 = loadSlotBuffer2; hh->unloadBuffer2 = unloadSlotBuffer2; hh->msgBytes2 = slotMsgBytes2;
       for (int f = 0; f < 6; ++f) {
          parms->sendCellsGpu[f] = uploadInts(parms->sendCells[f], parms->nCells[f]);
          parms->recvCellsGpu[f] = uploadInts(parms->recvCells[f], parms->nCells[f]);
          parms->sendOffsetsGpu[f] = (int*)comdDeviceMalloc((long)(parms->nCells[f] + 1) * sizeof(int));
          parms->recvOffsetsGpu[f] = (int*)comdDeviceMalloc((long)(parms->nCells[f] + 1) * sizeof(int));
       }
-      parms->d_cellOffsets = (int*)comdDeviceMalloc((long)(maxSize + 1) * sizeof(int));
       hh->sendBufM = (char*)comdDeviceMalloc(hh->bufCapacity); hh->sendBufP = (char*)comdDeviceMalloc(hh->bufCapacity);
       hh->recvBufM = (char*)comdDeviceMalloc(hh->bufCapacity); hh->recvBufP = (char*)comdDeviceMalloc(hh->bufCapacity);
    }
    return hh;
 }
 
+HaloExchange* initForceHaloExchange(Domain* domain, LinkCell* boxes, int allocDevice)
+{
+   return initSlotHaloExchange(domain, boxes, allocDevice, HALO_FORCE);
+}
+
+HaloExchange* initPositionHaloExchange(Domain* domain, LinkCell* boxes, int allocDevice)
+{
+   return initSlotHaloExchange(domain, boxes, allocDevice, HALO_POSITIONS);
+}
+
 /* comdSetBox: the global box has changed -- the periodic shifts of an exchange that carries some (atoms, positions; dF/drho has none) are taken from the
  * domain again, and the folded shift table of the mirror path is dropped: slotMirror makes it again on its next call */
 void haloSetBox(HaloExchange* hh, const Domain* domain)
 {
-   if (hh->type == 0) { faceShifts(domain, ((AtomExchangeParms*)hh->parms)->shift); return; }
+   if (hh->kind == HALO_ATOMS) { faceShifts(domain, ((AtomExchangeParms*)hh->parms)->shift); return; }
+   if (hh->kind != HALO_POSITIONS) return;
    ForceExchangeParms* parms = (ForceExchangeParms*)hh->parms;
-   if (!parms->positions) return;
    faceShifts(domain, parms->shift);
    parms->mirrorStale = 1;
 }
@@ -595,6 +472,22 @@ static int boundGrowing(int now, int before, int lastBound, int capacityAtoms)
    return wide > capacityAtoms ? capacityAtoms : (int)wide;
 }
 
+/* pack / unpack both faces of an axis phase: the two-face entry of a device exchange (one scan launch, one pack launch; one unpack launch),
+ * else the two host callbacks of comdHaloExchangeHost.  nBytes / bufSize -1: the count is on the device */
+static void loadBothFaces(HaloExchange* hh, void* data, int faceM, int faceP, int nBytes[2])
+{
+   if (hh->loadBuffer2) { hh->loadBuffer2(hh, data, faceM, hh->sendBufM, faceP, hh->sendBufP, nBytes); return; }
+   nBytes[0] = hh->loadBuffer(hh->parms, data, faceM, hh->sendBufM);
+   nBytes[1] = hh->loadBuffer(hh->parms, data, faceP, hh->sendBufP);
+}
+
+static void unloadBothFaces(HaloExchange* hh, void* data, int faceM, int bufSizeM, char* bufM, int faceP, int bufSizeP, char* bufP)
+{
+   if (hh->unloadBuffer2) { hh->unloadBuffer2(hh, data, faceM, bufSizeM, bufM, faceP, bufSizeP, bufP); return; }
+   hh->unloadBuffer(hh->parms, data, faceM, bufSizeM, bufM);
+   hh->unloadBuffer(hh->parms, data, faceP, bufSizeP, bufP);
+}
+
 void exchangeData(HaloExchange* hh, void* data, int iAxis)
 {
    const int faceM = 2 * iAxis, faceP = faceM + 1;
@@ -611,7 +504,7 @@ void exchangeData(HaloExchange* hh, void* data, int iAxis)
       for (int i = 0; sp->haveBound && i < 4; ++i)
          if (sp->mirror[i] > sp->lastBound[i]) {
             fprintf(stderr, "Rank %d: a halo message overflowed its buffer, or grew by more than 12.5 %% + 64 atoms in one step (%d atoms against an agreed %d; "
-                            "exchange %d, axis %d).  COMD_HALO_HANDSHAKE=1 exchanges exact sizes.\n", getMyRank(), sp->mirror[i], sp->lastBound[i], hh->type, iAxis);
+                            "exchange %d, axis %d).  COMD_HALO_HANDSHAKE=1 exchanges exact sizes.\n", getMyRank(), sp->mirror[i], sp->lastBound[i], (int)hh->kind, iAxis);
             exit(-1);
          }
       for (int i = 0; i < 4; ++i)
@@ -621,24 +514,13 @@ void exchangeData(HaloExchange* hh, void* data, int iAxis)
       sp->haveBound = 1;
       if (hh->setBounds) { hh->setBounds(hh->parms, faceM, bound[0], bound[3]); hh->setBounds(hh->parms, faceP, bound[1], bound[2]); }
    }
-   int nSendM, nSendP;
-   if (hh->loadBuffer2) {                                  /* both faces: one scan launch, one pack launch */
-      int n[2];
-      hh->loadBuffer2(hh->parms, data, faceM, hh->sendBufM, faceP, hh->sendBufP, n);
-      nSendM = n[0]; nSendP = n[1];
-   } else {
-      nSendM = hh->loadBuffer(hh->parms, data, faceM, hh->sendBufM);
-      nSendP = hh->loadBuffer(hh->parms, data, faceP, hh->sendBufP);
-   }
+   int nSend[2];                                           /* bytes through the minus face, through the plus face */
+   loadBothFaces(hh, data, faceM, faceP, nSend);
 
    if (selfOnly) {
       /* this rank is its own neighbour along the axis: what it sends through the minus face arrives through its plus
        * face.  Unpack straight from the send buffers (the reference's comm path has the same shortcut, haloExchange.c:788-853). */
-      if (hh->unloadBuffer2) hh->unloadBuffer2(hh->parms, data, faceM, nSendP, hh->sendBufP, faceP, nSendM, hh->sendBufM);
-      else {
-         hh->unloadBuffer(hh->parms, data, faceM, nSendP, hh->sendBufP);
-         hh->unloadBuffer(hh->parms, data, faceP, nSendM, hh->sendBufM);
-      }
+      unloadBothFaces(hh, data, faceM, nSend[1], hh->sendBufP, faceP, nSend[0], hh->sendBufM);
       return;
    }
    if (useSized) {
@@ -647,36 +529,22 @@ void exchangeData(HaloExchange* hh, void* data, int iAxis)
       const int h = hh->msgHeaderBytes, b = hh->msgBytesPerAtom;
       sendReceiveDevice2Sized(hh->sendBufM, h + bound[0] * b, nbrM, hh->recvBufP, h + bound[2] * b,
                               hh->sendBufP, h + bound[1] * b, nbrP, hh->recvBufM, h + bound[3] * b, sim->gpu.boundary_stream);
-      if (hh->unloadBuffer2) hh->unloadBuffer2(hh->parms, data, faceM, -1, hh->recvBufM, faceP, -1, hh->recvBufP);
-      else {
-         hh->unloadBuffer(hh->parms, data, faceM, -1, hh->recvBufM);
-         hh->unloadBuffer(hh->parms, data, faceP, -1, hh->recvBufP);
-      }
+      unloadBothFaces(hh, data, faceM, -1, hh->recvBufM, faceP, -1, hh->recvBufP);
       if (hh->setBounds) { hh->setBounds(hh->parms, faceM, 0, 0); hh->setBounds(hh->parms, faceP, 0, 0); }
    } else {
-      if (nSendM < 0 && nSendP < 0 && hh->msgBytes2) {
-         int n[2];
-         hh->msgBytes2(hh->parms, data, faceM, hh->sendBufM, faceP, hh->sendBufP, n);
-         nSendM = n[0]; nSendP = n[1];
-      }
-      if (nSendM < 0 && hh->msgBytes) nSendM = hh->msgBytes(hh->parms, data, faceM, hh->sendBufM);
-      if (nSendP < 0 && hh->msgBytes) nSendP = hh->msgBytes(hh->parms, data, faceP, hh->sendBufP);
+      if ((nSend[0] < 0 || nSend[1] < 0) && hh->msgBytes2) hh->msgBytes2(hh, data, faceM, hh->sendBufM, faceP, hh->sendBufP, nSend);
       int nRecvP, nRecvM;
       if (hh->deviceBuffers) {
          SimFlat* sim = (SimFlat*)data;
          int nRecv[2];
-         sendReceiveDevice2(hh->sendBufM, nSendM, nbrM, hh->recvBufP, hh->sendBufP, nSendP, nbrP, hh->recvBufM, hh->bufCapacity,
+         sendReceiveDevice2(hh->sendBufM, nSend[0], nbrM, hh->recvBufP, hh->sendBufP, nSend[1], nbrP, hh->recvBufM, hh->bufCapacity,
                             sim->gpu.boundary_stream, nRecv);
          nRecvP = nRecv[0]; nRecvM = nRecv[1];
       } else {
-         nRecvP = sendReceiveParallel(hh->sendBufM, nSendM, nbrM, hh->recvBufP, hh->bufCapacity, nbrP);
-         nRecvM = sendReceiveParallel(hh->sendBufP, nSendP, nbrP, hh->recvBufM, hh->bufCapacity, nbrM);
+         nRecvP = sendReceiveParallel(hh->sendBufM, nSend[0], nbrM, hh->recvBufP, hh->bufCapacity, nbrP);
+         nRecvM = sendReceiveParallel(hh->sendBufP, nSend[1], nbrP, hh->recvBufM, hh->bufCapacity, nbrM);
       }
-      if (hh->unloadBuffer2) hh->unloadBuffer2(hh->parms, data, faceM, nRecvM, hh->recvBufM, faceP, nRecvP, hh->recvBufP);
-      else {
-         hh->unloadBuffer(hh->parms, data, faceM, nRecvM, hh->recvBufM);
-         hh->unloadBuffer(hh->parms, data, faceP, nRecvP, hh->recvBufP);
-      }
+      unloadBothFaces(hh, data, faceM, nRecvM, hh->recvBufM, faceP, nRecvP, hh->recvBufP);
    }
    if (sized && !(hh->exactCounts && useSized)) {
       /* leave the four counts of this phase where the next exchange of the axis finds them without asking the device */

@@ -215,9 +215,6 @@ typedef struct SimGpuSt {
    int          reduceBlocks;
    /* per-simulation switches of the launch wrappers (library globals in round 1) */
    int          needEnergy;            /* comdSetEnergyNeeded: 0 = the coming force evaluations feed no energy read */
-   int          forceScansReady;       /* comdForceScansReady: load/unloadForceBuffer*Gpu use the offsets of scanCellListsGpu as they are */
-   int          msgBoundAtoms;         /* > 0: load{Force,Position}BufferFromGpu flag status[2] when the listed cells hold more atoms than this
-                                        * (the size both ends of a halo message agreed on beforehand, see CommTransport.sendrecv2sized) */
    void*        timing;                /* comdForceTiming*: event pool of this simulation, NULL = off */
    void*        tuning;                /* private to the device library: the COMD_* environment variables as AllocateGpu found them (hip/comd_device.hip ComdTuning) */
    real_t       latticeConstant;       /* GpuConfig.latticeConstant (0: 3.615): density estimate behind the LDS sizing of the cell kernels */
@@ -649,20 +646,21 @@ int  atomMsgCountGpu(SimGpu* sim, const char* msg_d, comdStream_t stream);
  * nBuf < 0: take the count from the message header on the device; maxAtomsInMsg bounds the launch. */
 void unloadAtomsBufferToGpu(const char* msg_d, int nBuf, int maxAtomsInMsg, SimGpu* sim, comdStream_t stream);
 /* loadForceBufferFromGpu(buf, &nbuf, nCells, cellList, natoms_buf, partial_sums, SimFlat*, gpu_buf, stream), :619-640:
- * gather dfEmbed of the listed cells, in list order, into gpu_buf (real_t[]); d_cellOffsets needs nCells+1 ints.
- * Does not block; the count ends up in d_cellOffsets[nCells]. */
+ * gather dfEmbed of the listed cells, in list order, into gpu_buf (real_t[]); d_cellOffsets needs nCells+1 ints: the call scans
+ * the occupancies of its list into them first.  Does not block; the count ends up in d_cellOffsets[nCells]. */
 void loadForceBufferFromGpu(real_t* gpu_buf, int nCells, int* d_cellList, int* d_cellOffsets, SimGpu* sim, comdStream_t stream);
 /* unloadForceBufferToGpu(buf, nBuf, nCells, cellList, natoms_buf, partial_sums, SimFlat*, gpu_buf, stream), :642-660 */
 void unloadForceBufferToGpu(const real_t* gpu_buf, int nCells, int* d_cellList, int* d_cellOffsets, SimGpu* sim, comdStream_t stream);
+/* The two-face entries never scan: d_cellOffsets hold what scanCellListsGpu left there.  boundAtoms[f] > 0: status[2] is raised when the
+ * listed cells hold more atoms than that (the size both ends of a halo message agreed on beforehand, see CommTransport.sendrecv2sized). */
 void loadForceBufferFromGpu2(real_t* bufM, real_t* bufP, const int nCells[2], int* const d_cellList[2], int* const d_cellOffsets[2],
                              const int boundAtoms[2], SimGpu* sim, comdStream_t stream);
 void unloadForceBufferToGpu2(const real_t* bufA, const real_t* bufB, const int nCells[2], int* const d_cellList[2], int* const d_cellOffsets[2],
                              SimGpu* sim, comdStream_t stream);
 /* The force exchange scans twelve cell lists per step (natoms_buf/partial_sums of haloExchange.c:438-465).  Occupancies are final
  * once the atom exchange has been sorted, so all of them can be scanned in ONE launch: scanCellListsGpu fills d_cellOffsets[i]
- * (nCells[i] + 1 ints) for up to 12 lists; comdForceScansReady(1) then tells load/unloadForceBuffer*Gpu to use those offsets as they are. */
+ * (nCells[i] + 1 ints) for up to 12 lists, and load/unloadForceBufferFromGpu2 use those offsets as they are. */
 void scanCellListsGpu(SimGpu* sim, int nLists, int** d_cellLists, const int* nCells, int** d_cellOffsets, comdStream_t stream);
-void comdForceScansReady(SimGpu* sim, int on);
 /* blocking read of one device int (message counts for the multi-rank transport) */
 int  comdReadDeviceInt(const int* d_ptr, comdStream_t stream);
 /* two device ints behind ONE stream synchronisation (the two message counts of an axis phase) */
@@ -758,9 +756,8 @@ void comm_finalize(void);
  * (no prototypes: their reference signatures carry MPI and libmp types; tests/test_boundary_shim.py walks the list) */
 /* Between list builds the halo copies keep their slots and only their positions are refreshed: gather r (+ the periodic shift of
  * the face) of the listed cells, in list order, into gpu_buf (3 real_t per atom); scatter them into the receive cells.  The
- * reference re-sends whole atoms and finds their slots through a gid hash table (haloExchange.c:1622-1700, hashTable.c). */
-void loadPositionBufferFromGpu(real_t* gpu_buf, int nCells, int* d_cellList, int* d_cellOffsets, const real_t shift[3], SimGpu* sim, comdStream_t stream);
-void unloadPositionBufferToGpu(const real_t* gpu_buf, int nCells, int* d_cellList, int* d_cellOffsets, SimGpu* sim, comdStream_t stream);
+ * reference re-sends whole atoms and finds their slots through a gid hash table (haloExchange.c:1622-1700, hashTable.c).
+ * Both faces of an axis phase, like load/unloadForceBufferFromGpu2; the offsets are those scanCellListsGpu left after the last list build. */
 void loadPositionBufferFromGpu2(real_t* bufM, real_t* bufP, const int nCells[2], int* const d_cellList[2], int* const d_cellOffsets[2],
                                 const int boundAtoms[2], const real_t shiftM[3], const real_t shiftP[3], SimGpu* sim, comdStream_t stream);
 void unloadPositionBufferToGpu2(const real_t* bufA, const real_t* bufB, const int nCells[2], int* const d_cellList[2], int* const d_cellOffsets[2],

@@ -69,7 +69,6 @@ int shim_world_run(SimGpu* gpu, ShimWorld* w, int nSteps, double dt, double eOut
    pot.cutoff = (real_t)w->cutoff;
    flat.boxes = &lc; flat.pot = &pot;
    flat.gpu = *gpu;                                     /* the reference embeds SimGpu in SimFlat by value (CoMDTypes.h:122) */
-   flat.gpu.msgBoundAtoms = 0; flat.gpu.forceScansReady = 0;
    flat.method = w->method; flat.gpuAsync = w->gpuAsync;
    flat.n_boundary_cells = gpu->n_boundary_cells;
    flat.boundary_cells = gpu->boundary_cells; flat.interior_cells = gpu->interior_cells;
