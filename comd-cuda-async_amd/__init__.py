@@ -164,6 +164,10 @@ def lib_host():
         lib.comdAtomStrain.restype = ctypes.c_int
         lib.comdStrainSummary.argtypes = [vp, ctypes.c_double, ctypes.c_double, c_double_p]
         lib.comdStrainSummary.restype = ctypes.c_int
+        lib.comdSteinhardt.argtypes = [vp, c_double_p]
+        lib.comdSteinhardt.restype = ctypes.c_int
+        lib.comdSteinhardtSummary.argtypes = [vp, ctypes.c_double, c_double_p]
+        lib.comdSteinhardtSummary.restype = ctypes.c_int
         lib.comdStrainReferenceBox.argtypes = [vp, c_double_p]
         lib.comdStrainReferenceBox.restype = ctypes.c_int
         lib.comdDefaultCoordRadius.argtypes = [vp]
@@ -946,6 +950,54 @@ class Simulation:
             raise RuntimeError("strain_summary: comdStrainSummary failed")
         return {"n": int(out[0]), "invalid": int(out[1]), "mean_shear": out[2], "max_shear": out[3], "max_shear_gid": int(out[4]),
                 "mean_volumetric": out[5], "mean_d2min": out[6], "max_d2min": out[7], "above_threshold": int(out[8])}
+
+    # --- bond-orientational order (not in the reference: comd-hip --steinhardt, --stSolid, --stFile, --stDump, --stDumpMax) ---
+    STEINHARDT_SOLID = 0.45
+
+    def _steinhardt_threshold(self, what, threshold):
+        """the q6 threshold handed to the host, after the refusals that come before any launch"""
+        if self.host_only:
+            raise RuntimeError(f"{what}: a host-only simulation has no device state")
+        if threshold is not None and not (0.0 < float(threshold) < 1.0):
+            raise ValueError(f"{what}: need 0 < threshold < 1 (got {threshold})")
+        return self.STEINHARDT_SOLID if threshold is None else float(threshold)
+
+    def steinhardt(self):
+        """float64 (n_global, 4) keyed by gid, columns q4 q6 w4 w6: Steinhardt's bond-orientational order (Steinhardt, Nelson, Ronchetti 1983) of every atom
+        of the current state on its 12 nearest neighbours inside the force cutoff, the set centro_symmetry() takes.  With the unit vectors u_ij to them,
+        q_lm = (1/12) sum_j Y_lm(u_ij), q_l = sqrt(4 pi / (2l + 1) sum_m |q_lm|^2) and w_l = sum_{m1+m2+m3=0} (l l l; m1 m2 m3) q_lm1 q_lm2 q_lm3 /
+        (sum_m |q_lm|^2)^(3/2): q6 is 0.575 on an FCC site, 0.485 on an HCP one, 0.663 in an icosahedron and falls continuously in a melt; w4 is negative
+        for FCC and positive for HCP; w6 = -0.170 singles out the icosahedron.  w_l is 0 where q_l^2 < 1e-6.  An atom with fewer than 12 neighbours inside
+        the cutoff is a NaN row.  Computed on the device by computeSteinhardt, summed over the ranks (every rank gets the global array); valid whenever
+        centro_symmetry() is.  RuntimeError on a host-only simulation."""
+        np = self._np
+        self._steinhardt_threshold("steinhardt", None)
+        n = self.n_global
+        out = np.zeros((max(n, 1), 4), dtype=np.float64)
+        if self.lib.comdSteinhardt(self.ptr, out.ctypes.data_as(c_double_p)) != 0:
+            raise RuntimeError("steinhardt: comdSteinhardt failed")
+        return out[:n]
+
+    def steinhardt_summary(self, threshold=None):
+        """{"n", "invalid", "mean_q4", "mean_q6", "min_q6", "min_q6_gid", "max_q6", "mean_w4", "mean_w6", "solid"}: the figures of steinhardt(), reduced on
+        the device (computeSteinhardtSummary: the per-atom planes never leave it) and over the ranks.  n counts the valid atoms; the invalid ones are counted
+        and left out of means and extremes; the gid is the lowest one that holds the minimum; solid counts the atoms with q6 >= threshold (None: 0.45).  With
+        no valid atom at all invalid is the number of atoms, the means and extremes are 0 and min_q6_gid is -1.  ValueError, before anything is launched, for
+        a threshold outside (0, 1); RuntimeError on a host-only simulation."""
+        t = self._steinhardt_threshold("steinhardt_summary", threshold)
+        out = (ctypes.c_double * 10)()
+        if self.lib.comdSteinhardtSummary(self.ptr, t, out) != 0:
+            raise RuntimeError("steinhardt_summary: comdSteinhardtSummary failed")
+        return {"n": int(out[0]), "invalid": int(out[1]), "mean_q4": out[2], "mean_q6": out[3], "min_q6": out[4], "min_q6_gid": int(out[5]),
+                "max_q6": out[6], "mean_w4": out[7], "mean_w6": out[8], "solid": int(out[9])}
+
+    def solid_like(self, threshold=None):
+        """Ascending int64 gids of the atoms with q6 >= threshold (None: 0.45); atoms with fewer than 12 neighbours (NaN) do not count.  ValueError, before
+        anything is launched, for a threshold outside (0, 1)."""
+        np = self._np
+        t = self._steinhardt_threshold("solid_like", threshold)
+        with np.errstate(invalid="ignore"):
+            return np.nonzero(self.steinhardt()[:, 1] >= t)[0].astype(np.int64)
 
     # --- box deformation (not in the reference: comd-hip --erateX, --erateY, --erateZ, --deformStart, --deformFile) ---
     def _box6(self):

@@ -348,6 +348,35 @@ extern "C" void computeAtomStrainSummary(SimGpu* sim, double threshold, double* 
    launchSummary(sim, AtomStrain_Summary, AtomStrain_SummaryFinal, sim->strainBuf, threshold, sim->strainSumBuf, ATOMSTRAIN_SUM_BLOCKS, ATOMSTRAIN_SUM_N, out);
 }
 
+// Not in the reference: Steinhardt's bond-orientational order q4, q6, w4, w6 of every local atom (steinhardt_kernels.h).  One instance for every potential
+// and method, as computeCentroSymmetry, whose walk it shares.  The four planes and the rows of the summary are allocated by the first call.
+extern "C" void computeSteinhardt(SimGpu* sim, real_t* outBySlot4)
+{
+   hipStream_t st = analysisStream(sim);
+   const real_t cutoff = pairCutoff(sim);
+   refuseSlotsBeyondInt(sim, "computeSteinhardt");
+   const size_t nSlots = localSlots(sim);
+   if (!sim->steinhardtBuf) {
+      sim->steinhardtBuf = dalloc<real_t>(STEINHARDT_PLANES * nSlots);
+      sim->steinhardtSumBuf = dalloc<double>((size_t)(STEINHARDT_SUM_BLOCKS + 1) * STEINHARDT_SUM_N, false);
+   }
+   SteinhardtArgs v;
+   fillStencilArgs(v, sim);
+   v.rc2 = cutoff * cutoff;
+   v.plane = nSlots;
+   hipLaunchKernelGGL(Steinhardt_thread_atom, dim3(STEINHARDT_BLOCKS), dim3(256), 0, st, v, sim->steinhardtBuf);
+   LAUNCH_CHECK();
+   if (outBySlot4) HIP_CHECK(hipMemcpyAsync(outBySlot4, sim->steinhardtBuf, STEINHARDT_PLANES * nSlots * sizeof(real_t), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// Not in the reference: the printed-step figures of the planes computeSteinhardt has left on the device (steinhardt_kernels.h): 10 doubles
+extern "C" void computeSteinhardtSummary(SimGpu* sim, double threshold, double* out)
+{
+   if (!sim->steinhardtBuf) { fprintf(stderr, "computeSteinhardtSummary: no computeSteinhardt call before it\n"); exit(-1); }
+   launchSummary(sim, Steinhardt_Summary, Steinhardt_SummaryFinal, sim->steinhardtBuf, threshold, sim->steinhardtSumBuf, STEINHARDT_SUM_BLOCKS, STEINHARDT_SUM_N, out);
+}
+
 // Not in the reference: displacement tracking for the mean-squared displacement (msd_kernels.h).  on: one zeroed 32-byte record per global atom id,
 // which the drift kernels of this simulation add into from now on (already on: zeroed again, the origin becomes "now"); off: the memory is
 // freed.  1 and nothing tracked when the device cannot give the memory.

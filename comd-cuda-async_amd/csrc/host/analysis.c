@@ -1,5 +1,5 @@
 /* analysis.c -- the host entries of the analyses (not in the reference; comd_host.h): pressure, g(r), centro-symmetry, common neighbour analysis, per-atom
- * stress and strain, heat flux and its autocorrelation, displacements, slab profiles, the Mueller-Plathe exchange and the structure factor.  Each is a call into include/comd_hip.h for this rank's share and a sum over the ranks. */
+ * stress and strain, Steinhardt order, heat flux and its autocorrelation, displacements, slab profiles, the Mueller-Plathe exchange and the structure factor.  Each is a call into include/comd_hip.h for this rank's share and a sum over the ranks. */
 #include "comd_host.h"
 #include "slot_gather.h"
 #include <math.h>
@@ -57,7 +57,7 @@ double comdDefaultCoordRadius(SimFlat* s)
    return r < cutoff ? r : cutoff;
 }
 
-/* ---- the by-gid gather of comdCentroSymmetry, comdCommonNeighbors, comdAtomStress, comdAtomStrain and comdAtomHeatFlux ----
+/* ---- the by-gid gather of comdCentroSymmetry, comdCommonNeighbors, comdAtomStress, comdAtomStrain, comdSteinhardt and comdAtomHeatFlux ----
  * An output is out[nGlobal][width], filled from `width` consecutive by-slot planes of one kind (slot_gather.h); the real_t outputs come first.  `run` launches the
  * kernel and copies its planes into plane[k], one pointer per output. */
 typedef struct { void* out; int kind, width; } GidOutput;
@@ -305,6 +305,54 @@ int comdStrainSummary(SimFlat* s, double rCut, double threshold, double* out9)
    out9[0] = N + local[7]; out9[1] = local[7];
    out9[2] = N > 0.0 ? local[0] / N : 0.0; out9[3] = N > 0.0 ? local[1] : 0.0; out9[4] = local[2];
    out9[5] = N > 0.0 ? local[3] / N : 0.0; out9[6] = N > 0.0 ? local[4] / N : 0.0; out9[7] = N > 0.0 ? local[5] : 0.0; out9[8] = local[8];
+   return 0;
+}
+
+/* ---- Steinhardt's bond-orientational order (not in the reference; comd_host.h) ---- */
+static void runSteinhardt(SimFlat* s, void* const* plane, const void* none) { computeSteinhardt(&s->gpu, (real_t*)plane[0]); }
+
+int comdSteinhardt(SimFlat* s, double* outByGid4)
+{
+   if (!s->gpu.boxes.nAtoms) return -1;
+   const GidOutput out = { outByGid4, SLOT_REAL, 4 };
+   gatherByGid(s, runSteinhardt, NULL, &out, 1);
+   return 0;
+}
+
+int comdSteinhardtSummary(SimFlat* s, double threshold, double* out10)
+{
+   if (!s->gpu.boxes.nAtoms || !(threshold > 0.0 && threshold < 1.0)) return -1;
+   double local[10];         /* valid, invalid, sum q4, sum q6, sum w4, sum w6, min q6, gid, max q6, above (computeSteinhardtSummary) */
+   computeSteinhardt(&s->gpu, NULL);
+   computeSteinhardtSummary(&s->gpu, threshold, local);
+   const int nRanks = getNRanks(), me = getMyRank();
+   if (nRanks > 1) {
+      /* the sums add; the extremes and the gid go through one slot per rank of a summed vector (no MIN/MAX of doubles in the transport), taken in rank order */
+      double* mine = (double*)calloc(2 * (size_t)(7 + 3 * nRanks), sizeof(double));
+      double* all = mine + 7 + 3 * (size_t)nRanks;
+      for (int c = 0; c < 6; ++c) mine[c] = local[c];
+      mine[6] = local[9];
+      if (local[0] > 0.0) { double* slot = mine + 7 + 3 * (size_t)me; slot[0] = local[6]; slot[1] = local[7] + 1.0; slot[2] = local[8]; }
+      startTimer(commReduceTimer);
+      addDoubleParallel(mine, all, 7 + 3 * nRanks);
+      stopTimer(commReduceTimer);
+      for (int c = 0; c < 6; ++c) local[c] = all[c];
+      local[9] = all[6];
+      local[6] = INFINITY; local[7] = -1.0; local[8] = -INFINITY;
+      for (int r = 0; r < nRanks; ++r) {
+         const double* slot = all + 7 + 3 * (size_t)r;
+         if (slot[1] == 0.0) continue;          /* a rank without valid atoms */
+         const double g = slot[1] - 1.0;
+         if (local[7] < 0.0 || slot[0] < local[6] || (slot[0] == local[6] && g < local[7])) { local[6] = slot[0]; local[7] = g; }
+         if (slot[2] > local[8]) local[8] = slot[2];
+      }
+      free(mine);
+   }
+   const double N = local[0];
+   out10[0] = N; out10[1] = local[1];
+   out10[2] = N > 0.0 ? local[2] / N : 0.0; out10[3] = N > 0.0 ? local[3] / N : 0.0;
+   out10[4] = N > 0.0 ? local[6] : 0.0; out10[5] = N > 0.0 ? local[7] : -1.0; out10[6] = N > 0.0 ? local[8] : 0.0;
+   out10[7] = N > 0.0 ? local[4] / N : 0.0; out10[8] = N > 0.0 ? local[5] / N : 0.0; out10[9] = local[9];
    return 0;
 }
 

@@ -35,7 +35,10 @@
  * Green-Kubo thermal conductivity in W/(m K); the reference has no transport output),
  * --sk M, --skStride s|sx,sy,sz, --skBins N, --skStart S, --skFile PATH (static structure factor S(k) = |sum_j exp(-i k . r_j)|^2 / N on the half grid of wave vectors
  *   2 pi (sx h / Lx, sy k / Ly, sz l / Lz), h in [0, M], k, l in [-M, M], and the Bragg order S(111) / N of the conventional cell, summed on the device at every
- *   printed step from global step S on; an S111/N column, PATH gets the powder average over N |k| bins; the reference has no reciprocal-space analysis). */
+ *   printed step from global step S on; an S111/N column, PATH gets the powder average over N |k| bins; the reference has no reciprocal-space analysis),
+ * --steinhardt, --stSolid X, --stFile PATH, --stDump PATH, --stDumpMax X (Steinhardt's bond-orientational order q4, q6, w4, w6 of every atom on its 12 nearest
+ *   neighbours, reduced on the device at every printed step; a MeanQ6 column, atoms with q6 >= X count as solid-like, PATH gets a line per sample and the dump the
+ *   values of the atoms of the last step whose q6 is at most --stDumpMax, the invalid ones always, as extended XYZ). */
 #include "comd_host.h"
 #include <getopt.h>
 #include <math.h>
@@ -87,6 +90,8 @@ Command parseCommandLine(int argc, char** argv)
    strcpy(cmd.mpFile, "mp.dat");
    strcpy(cmd.skStride, "1"); cmd.skBins = 50;
    strcpy(cmd.skFile, "sk.dat");
+   strcpy(cmd.stFile, "steinhardt.dat");
+   cmd.stSolid = 0.45; cmd.stDumpMax = INFINITY;
    int help = 0;
 
    const ArgDef defs[] = {
@@ -184,6 +189,11 @@ Command parseCommandLine(int argc, char** argv)
       { "skBins",        0,  1, 'i', &cmd.skBins,         0, "|k| bins of the powder average, 1..4096 (default 50)" },
       { "skStart",       0,  1, 'i', &cmd.skStart,        0, "global step structure-factor sampling begins at (0..nSteps; default 0)" },
       { "skFile",        0,  1, 's', cmd.skFile, sizeof cmd.skFile, "file the time-averaged powder average S(|k|) is written to (default sk.dat)" },
+      { "steinhardt",    0,  0, 'i', &cmd.steinhardt,     0, "Steinhardt bond-orientational order q4, q6, w4, w6 of every atom on its 12 nearest neighbours, sampled at every printed step (a MeanQ6 column)" },
+      { "stSolid",       0,  1, 'd', &cmd.stSolid,        0, "atoms with q6 of at least this count as solid-like, 0 < x < 1 (default 0.45)" },
+      { "stFile",        0,  1, 's', cmd.stFile, sizeof cmd.stFile, "file the samples are written to (default steinhardt.dat)" },
+      { "stDump",        0,  1, 's', cmd.stDump, sizeof cmd.stDump, "extended-XYZ file of q4, q6, w4, w6 of the atoms of the last step (default: none)" },
+      { "stDumpMax",     0,  1, 'd', &cmd.stDumpMax,      0, "only atoms with q6 of at most this are dumped, and the atoms with fewer than 12 neighbours (default inf: all atoms)" },
    };
    const int nDefs = (int)(sizeof defs / sizeof defs[0]);
 
@@ -279,6 +289,7 @@ void printCmdYaml(FILE* file, Command* cmd)
       fprintf(file, "  MullerPlathe every: %d steps\n  MullerPlathe swaps: %d\n  MullerPlathe from step: %d\n  MullerPlathe file: %s\n", cmd->mpEvery, cmd->mpSwaps, cmd->mpStart, cmd->mpFile);
    if (cmd->sk) fprintf(file, "  Structure factor kMax index: %d\n  Structure factor stride: %s\n  Structure factor bins: %d\n  Structure factor from step: %d\n  Structure factor file: %s\n",
                         cmd->sk, cmd->skStride, cmd->skBins, cmd->skStart, cmd->skFile);
+   if (cmd->steinhardt) fprintf(file, "  Steinhardt solid threshold: %g\n  Steinhardt file: %s\n", cmd->stSolid, cmd->stFile);
    fprintf(file, "\n");
    fflush(file);
 }

@@ -107,6 +107,11 @@ typedef struct CommandSt {
    int skBins;            /* extension: |k| bins of the powder average, 1..4096 (default 50) */
    int skStart;           /* extension: the global step sampling begins at (default 0) */
    char skFile[1024];     /* extension: where the print rank writes the time-averaged powder average (default sk.dat) */
+   int steinhardt;        /* extension: Steinhardt's bond-orientational order q4, q6, w4, w6 of every atom, reduced on the device at every printed step */
+   double stSolid;        /* extension: atoms with q6 of at least this are counted as solid-like, 0 < x < 1 (default 0.45) */
+   char stFile[1024];     /* extension: where the print rank writes the samples (default steinhardt.dat) */
+   char stDump[1024];     /* extension: extended-XYZ file of the per-atom values of the last step; empty = none */
+   double stDumpMax;      /* extension: only atoms with q6 of at most this are dumped, the invalid ones always; +inf = all */
 } Command;
 
 #define COMD_LANGEVIN_SEED 0x436f4d44ull     /* "CoMD" */
@@ -454,6 +459,12 @@ typedef struct SimFlatSt {
    int skSamples;
    double skBoxSum[3];              /* the extents summed over the samples */
    double skBraggNow, skBraggFirst, skBraggSum;      /* comdBraggOrder of the last sample, of the first, summed over the samples */
+   /* Steinhardt order (--steinhardt): comdMain samples comdSteinhardtSummary at every printed step */
+   int steinhardt;
+   double stSolid, stDumpMax;       /* the q6 threshold of the solid-like count; the dump keeps q6 <= stDumpMax and the invalid atoms */
+   char stFile[1024], stDump[1024];
+   RowTable stRows;                 /* [11] doubles: step, the ten values of comdSteinhardtSummary */
+   double stMeanQ6Now;              /* the MeanQ6 column of printThings: the last sample */
 } SimFlat;
 
 SimFlat* initSimulation(Command cmd);
@@ -553,6 +564,16 @@ int comdAtomStrain(SimFlat* s, double rCut, double* strainByGid7, int* countByGi
  * means and extremes over the valid atoms (0 without any).  Reduced on the device and then over the ranks.  The same on every rank.  Collective.  -1 as
  * comdAtomStrain, or for a threshold that is not > 0. */
 int comdStrainSummary(SimFlat* s, double rCut, double threshold, double* out9);
+/* not in the reference: Steinhardt's bond-orientational order of every atom of the current state on its 12 nearest neighbours inside the force cutoff
+ * (computeSteinhardt, comd_hip.h, has the definitions), keyed by gid: outByGid4[4 g + c], c = 0 q4, 1 q6, 2 w4, 3 w6; NaN in all four for an invalid atom
+ * (fewer than 12 neighbours inside the cutoff).  Valid whenever comdCentroSymmetry is.  Each rank fills the entries of its local atoms, the others stay 0, and
+ * the array is summed over the ranks (NaN + 0 stays NaN): the same on every rank.  Collective.  -1 and nothing launched without device state. */
+int comdSteinhardt(SimFlat* s, double* outByGid4);
+/* not in the reference: out10 = {valid atoms, invalid atoms, mean q4, mean q6, min q6, the gid that holds it (the lowest of equals, -1 without a valid atom),
+ * max q6, mean w4, mean w6, atoms with q6 >= threshold} of the current state (computeSteinhardtSummary, comd_hip.h); means and extremes over the valid atoms
+ * (0 without any).  Reduced on the device and then over the ranks.  The same on every rank.  Collective.  -1 without device state or for a threshold outside
+ * (0, 1). */
+int comdSteinhardtSummary(SimFlat* s, double threshold, double* out10);
 /* not in the reference (its box is nx lat for the whole run): box deformation, LAMMPS's `fix deform ... remap x`.
  * comdSetBox: the global box becomes L[3] Angstroms (the origin stays at 0) and the positions of the local atoms are scaled with it, L_new / L_old per axis, by
  *    comdRemapBoxGpu.  Every copy of the geometry follows: Domain (the expressions of initDecomposition, so neighbouring ranks agree bit for bit on their shared
@@ -659,7 +680,7 @@ void ensureInteriorForceLaunched(SimFlat* sim);
 
 /* ---- performanceTimers.h ---- */
 enum TimerHandle { totalTimer, loopTimer, timestepTimer, positionTimer, velocityTimer, redistributeTimer, atomHaloTimer,
-                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, cspTimer, cnaTimer, deformTimer, stressTimer, strainTimer, heatfluxTimer, baroTimer, profileTimer, mpTimer, skTimer, numberOfTimers };
+                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, cspTimer, cnaTimer, deformTimer, stressTimer, strainTimer, heatfluxTimer, baroTimer, profileTimer, mpTimer, skTimer, steinhardtTimer, numberOfTimers };
 void profileStart(enum TimerHandle handle);
 void profileStop(enum TimerHandle handle);
 double getElapsedTime(enum TimerHandle handle);

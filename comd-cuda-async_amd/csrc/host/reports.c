@@ -89,7 +89,7 @@ static double* positionsByGid(SimFlat* s)
    return pos;
 }
 
-/* an extended-XYZ dump (--cspDump, --cnaDump, --stressDump, --strainDump) of the atoms `row` keeps: their number, the Lattice= line of the current box with the
+/* an extended-XYZ dump (--cspDump, --cnaDump, --stressDump, --strainDump, --stDump) of the atoms `row` keeps: their number, the Lattice= line of the current box with the
  * caller's properties and settings behind species and pos, then per kept atom "Cu x y z" and what row(f, g, ctx) prints behind it; row(NULL, g, ctx) only
  * says whether atom g is kept.  On the print rank, with the positions of positionsByGid */
 typedef int (*XyzRow)(FILE* f, size_t g, const void* ctx);
@@ -648,6 +648,62 @@ static void writeSk(FILE* yaml, SimFlat* s, int iStep)
    (void)iStep;
 }
 
+/* --steinhardt: one more row {step, valid atoms, invalid atoms, mean q4, mean q6, min q6, the gid of the min, max q6, mean w4, mean w6, atoms at or above the
+ * threshold} from the device reduction */
+static void sampleSteinhardt(SimFlat* s, int iStep)
+{
+   double* row = (double*)nextRow(&s->stRows, 11 * sizeof(double));
+   row[0] = (double)iStep;
+   if (comdSteinhardtSummary(s, s->stSolid, row + 1) != 0) { printf("Error: --steinhardt needs the device state.\n"); exit(-1); }
+   s->stMeanQ6Now = row[4];
+}
+
+/* --steinhardt: the file: a header line, then the rows of sampleSteinhardt.  --stDump: the values of the last step as extended XYZ, Cu x y z q4 q6 w4 w6 gid, the
+ * atoms whose q6 is at most --stDumpMax (+inf: all atoms) and the invalid ones with their NaNs; the positions gathered by gid over the ranks as the values
+ * are.  The YAML block names the file and gives the last sample's mean q6 and the fraction of the atoms at or above the threshold. */
+typedef struct { const double* q; double max; } SteinhardtDump;
+static int steinhardtXyzRow(FILE* f, size_t g, const void* ctx)
+{
+   const SteinhardtDump* d = (const SteinhardtDump*)ctx;
+   const double* t = d->q + 4 * g;
+   if (f) fprintf(f, " %.17g %.17g %.17g %.17g %zu\n", t[0], t[1], t[2], t[3], g);
+   return !(t[1] > d->max);          /* a NaN stays in */
+}
+
+static void writeSteinhardt(FILE* yaml, SimFlat* s, int iStep)
+{
+   const size_t n = (size_t)s->atoms->nGlobal;
+   double *pos = NULL, *q = NULL;
+   if (s->stDump[0]) {          /* collective: before the other ranks leave */
+      pos = positionsByGid(s);
+      q = (double*)malloc((n ? 4 * n : 1) * sizeof(double));
+      if (comdSteinhardt(s, q) != 0) { printf("Error: --stDump needs the device state.\n"); exit(-1); }
+   }
+   if (!printRank()) { free(pos); free(q); return; }
+   const int samples = s->stRows.n;
+   const double* rows = (const double*)s->stRows.rows;
+   FILE* f = openReport(s->stFile);
+   fprintf(f, "# Steinhardt: N %d threshold %.17g samples %d | columns: step, valid atoms, invalid atoms (fewer than 12 neighbours), mean q4, mean q6, min q6, "
+              "gid of the min, max q6, mean w4, mean w6, atoms with q6 >= threshold\n", s->atoms->nGlobal, s->stSolid, samples);
+   const double* last = NULL;
+   for (int k = 0; k < samples; ++k) {
+      last = rows + 11 * (size_t)k;
+      fprintf(f, "%.0f %.0f %.0f %.17g %.17g %.17g %.0f %.17g %.17g %.17g %.0f\n", last[0], last[1], last[2], last[3], last[4], last[5], last[6], last[7], last[8], last[9], last[10]);
+   }
+   fclose(f);
+   if (pos && q) {
+      const SteinhardtDump dump = { q, s->stDumpMax };
+      char tail[256];
+      snprintf(tail, sizeof tail, "q4:R:1:q6:R:1:w4:R:1:w6:R:1:gid:I:1 step=%d maxQ6=%.17g", iStep, s->stDumpMax);
+      writeXyz(s->stDump, s, pos, tail, steinhardtXyzRow, &dump);
+   }
+   free(pos); free(q);
+   if (!yaml) return;
+   const double atoms = last ? last[1] + last[2] : 0.0;
+   fprintf(yaml, "Steinhardt:\n  threshold: %.12e\n  samples: %d\n  file: %s\n  finalMeanQ6: %.12e\n  finalSolidFraction: %.12e\n\n", s->stSolid, samples, s->stFile,
+           last ? last[4] : 0.0, atoms > 0.0 ? last[10] / atoms : 0.0);
+}
+
 /* ---- the table: one row per report, in the order of the columns of printThings and of the YAML blocks ---------------------------------------------------------
  * on      the row applies to this run;
  * from    the first global step it samples at (NULL: 0), start what is done when the run reaches that step: at a printed step under the report's timer, just
@@ -685,6 +741,7 @@ static int heatfluxOn(const SimFlat* s)    { return s->heatflux; }
 static int profileOn(const SimFlat* s)     { return s->profile; }
 static int mpOn(const SimFlat* s)          { return s->mpReport; }
 static int skOn(const SimFlat* s)          { return s->sk; }
+static int steinhardtOn(const SimFlat* s)  { return s->steinhardt; }
 
 static int msdFrom(const SimFlat* s)       { return s->msdStart; }
 static int strainFrom(const SimFlat* s)    { return s->strainRef; }
@@ -704,6 +761,7 @@ static void strainColumn(const SimFlat* s)   { fprintf(screenOut, " %16.10f", s-
 static void heatfluxColumn(const SimFlat* s) { fprintf(screenOut, " %19.10e", s->hfJxNow); }
 static void mpColumn(const SimFlat* s)       { fprintf(screenOut, " %19.10e", s->mpExchanged); }
 static void skColumn(const SimFlat* s)       { fprintf(screenOut, " %16.10f", s->skBraggNow); }
+static void steinhardtColumn(const SimFlat* s) { fprintf(screenOut, " %16.10f", s->stMeanQ6Now); }
 
 static const Report reports[] = {
    { .on = virialOn,        .sample = samplePressure, .timer = pressureTimer },      /* first: the samplers below read W, K, V */
@@ -724,6 +782,7 @@ static const Report reports[] = {
    { .on = profileOn,       .from = profileFrom, .sample = sampleProfile, .timer = profileTimer, .write = writeProfile, .writeTimed = 1 },      /* and the files and the block of --mp */
    { .on = mpOn,            .header = "              dE(eV)", .column = mpColumn },      /* its rows: mpExchange, inside timestep() */
    { .on = skOn,            .from = skFrom, .sample = sampleSk, .timer = skTimer, .header = "           S111/N", .column = skColumn, .write = writeSk },
+   { .on = steinhardtOn,    .sample = sampleSteinhardt, .timer = steinhardtTimer, .header = "           MeanQ6", .column = steinhardtColumn, .write = writeSteinhardt },
 };
 #define FOR_REPORTS(r, s) for (const Report* r = reports; r < reports + sizeof reports / sizeof reports[0]; ++r) if (r->on(s))
 
@@ -769,7 +828,7 @@ void reportsWrite(FILE* yaml, SimFlat* s, int iStep)
 
 void reportsFree(SimFlat* s)
 {
-   RowTable* tables[] = { &s->msdRows, &s->cspRows, &s->cnaRows, &s->deformRows, &s->baroRows, &s->mpRows, &s->stressRows, &s->strainRows, &s->hfRows };
+   RowTable* tables[] = { &s->msdRows, &s->cspRows, &s->cnaRows, &s->deformRows, &s->baroRows, &s->mpRows, &s->stressRows, &s->strainRows, &s->hfRows, &s->stRows };
    for (size_t i = 0; i < sizeof tables / sizeof tables[0]; ++i) free(tables[i]->rows);
    free(s->rdfSum); free(s->cspLast); free(s->cnaLast); free(s->profSum); free(s->skSum);
 }

@@ -272,6 +272,11 @@ SimFlat* initSimulationHost(Command cmd)
       strcpy(sim->skFile, cmd.skFile);
       sim->skSum = (double*)calloc(2 * (size_t)cmd.skBins, sizeof(double));
    }
+   /* --steinhardt (not in the reference): the threshold is a q6, which lies in [0, 1]; so is the bound of the dump, +inf = all atoms */
+   if (!(cmd.stSolid > 0.0 && cmd.stSolid < 1.0)) { printf("Error: --stSolid must lie in (0, 1) (got %g).\n", cmd.stSolid); exit(-1); }
+   if (!(cmd.stDumpMax > 0.0)) { printf("Error: --stDumpMax must be > 0 (got %g).\n", cmd.stDumpMax); exit(-1); }
+   sim->steinhardt = cmd.steinhardt; sim->stSolid = cmd.stSolid; sim->stDumpMax = cmd.stDumpMax;
+   strcpy(sim->stFile, cmd.stFile); strcpy(sim->stDump, cmd.stDump);
    sanityChecks(cmd, sim->pot->cutoff, latticeConstant, sim->pot->latticeType);
    sim->species = initSpecies(sim->pot);
 

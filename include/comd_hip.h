@@ -265,6 +265,8 @@ typedef struct SimGpuSt {
    void*        mpRows;                /* device: the (slot, momentum) rows of comdMullerPlatheApplyGpu, allocated by its first call */
    double*      skBuf;                 /* device [chunks + 1][K][2]: the chunks' amplitudes of computeStructureFactor and their sum, allocated by its first call and when they grow */
    uint64_t     skCap;                 /* doubles in skBuf */
+   real_t*      steinhardtBuf;         /* device [4][nLocalBoxes*maxAtoms]: the planes q4 q6 w4 w6 of computeSteinhardt, allocated by its first call */
+   double*      steinhardtSumBuf;      /* device: the workgroups' rows for computeSteinhardtSummary, allocated with steinhardtBuf */
 } SimGpu;
 
 /* Everything AllocateGpu needs to know about the rank's geometry and potential.
@@ -591,6 +593,26 @@ void computeAtomStrain(SimGpu* sim, real_t rCut, real_t* outBySlot7, int* outCou
  * -- over THIS rank's atoms; without valid atoms the extremes are -inf.  Nine doubles are copied, never the planes.  Deterministic two-stage reduction.
  * A call without a computeAtomStrain before it ends the run.  Blocks until the result is on the host. */
 void computeAtomStrainSummary(SimGpu* sim, double threshold, double* out);
+/* Not in the reference (CoMD has no structural analysis): Steinhardt's bond-orientational order (Steinhardt, Nelson, Ronchetti 1983) of every one of THIS
+ * rank's local atoms (hip/steinhardt_kernels.h).  For the atom i in local slot o = cell * maxAtoms + index, take its 12 nearest neighbours j != i (local or
+ * halo image) inside the force cutoff: exactly the set, the tie rule and the walk of computeCentroSymmetry.  With the unit vectors
+ * u_ij = (r_j - r_i) / |r_j - r_i|:
+ *   q_lm(i) = (1/12) sum_j Y_lm(u_ij), for l = 4 and 6, added in ascending order of the distance;
+ *   q_l     = sqrt(4 pi / (2l + 1) sum_m |q_lm|^2);
+ *   w_l     = sum_{m1 + m2 + m3 = 0} (l l l; m1 m2 m3) q_lm1 q_lm2 q_lm3 / (sum_m |q_lm|^2)^(3/2), with the Wigner 3j symbols;
+ *   w_l is reported as 0 where q_l^2 < 1e-6 (the icosahedron's w4 is 0/0).
+ * An atom with fewer than 12 neighbours inside the cutoff is invalid: all four values are NaN.  The arithmetic is in real_t.
+ * outBySlot4[c * nLocalBoxes * maxAtoms + o]: c = 0 q4, 1 q6, 2 w4, 3 w6, four planes in host memory; entries of empty slots mean nothing.  outBySlot4 == NULL:
+ * the planes stay on the device for computeSteinhardtSummary, nothing is copied.  Valid when computeCentroSymmetry is (halo images current, any method, cells
+ * sized for cutoff + skin and not re-binned included); same stream, no atomics, bit-reproducible; reads r and the cell tables, writes only its own planes
+ * (4 sizeof(real_t) bytes per local slot, allocated by the first call, freed by DestroyGpu).  Blocks until the kernel is done (and the copy, when asked for). */
+void computeSteinhardt(SimGpu* sim, real_t* outBySlot4);
+/* Not in the reference: the printed-step figures of the planes the last computeSteinhardt call left on the device, formed in double:
+ *   out[0] valid atoms, out[1] invalid atoms (left out of the sums and extremes), out[2] sum of q4, out[3] sum of q6, out[4] sum of w4, out[5] sum of w6,
+ *   out[6] min q6, out[7] the gid that holds it (the lowest one of equals; -1 without a valid atom), out[8] max q6, out[9] atoms with q6 >= threshold
+ * -- over THIS rank's atoms; without valid atoms the extremes are +inf and -inf.  Ten doubles are copied, never the planes.  Deterministic two-stage
+ * reduction.  A call without a computeSteinhardt before it ends the run.  Blocks until the result is on the host. */
+void computeSteinhardtSummary(SimGpu* sim, double threshold, double* out);
 /* Not in the reference: unwrapped displacements since an origin, for the mean-squared displacement (hip/msd_kernels.h).  on != 0: allocate and zero
  * one 32-byte record {dx, dy, dz, spare} per global atom id, signed 64-bit fixed point in units of 2^-32 Angstroms; from then on the drift kernels
  * of this simulation (advancePositionGpu and the fused forms, plain and Langevin) add dt p/m of every local atom into the record of its gid.  Already
