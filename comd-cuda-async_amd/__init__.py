@@ -168,6 +168,10 @@ def lib_host():
         lib.comdSteinhardt.restype = ctypes.c_int
         lib.comdSteinhardtSummary.argtypes = [vp, ctypes.c_double, c_double_p]
         lib.comdSteinhardtSummary.restype = ctypes.c_int
+        lib.comdBornMatrix.argtypes = [vp, c_double_p]
+        lib.comdBornMatrix.restype = ctypes.c_int
+        lib.comdElasticConstants.argtypes = [c_double_p, c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_double_p, c_double_p, c_double_p]
+        lib.comdElasticConstants.restype = ctypes.c_int
         lib.comdStrainReferenceBox.argtypes = [vp, c_double_p]
         lib.comdStrainReferenceBox.restype = ctypes.c_int
         lib.comdDefaultCoordRadius.argtypes = [vp]
@@ -999,6 +1003,27 @@ class Simulation:
         with np.errstate(invalid="ignore"):
             return np.nonzero(self.steinhardt()[:, 1] >= t)[0].astype(np.int64)
 
+    # --- Born matrix and elastic constants (not in the reference: comd-hip --elastic, --elStart, --elFile) ---
+    def born_matrix(self):
+        """float64 (6, 6), symmetric, in eV: the Born matrix B_IJ = d^2 U / d eta_I d eta_J of the current state, eta the Lagrangian strain, Voigt order
+        xx yy zz yz xz xy (extensive: divide by volume for a modulus).  B_abcd = sum_i [sum_j (1/2 (phi'' - phi'/r) + F'_i (rho'' - rho'/r)) r_a r_b r_c r_d / r^2
+        + F''(rhobar_i) g^i_ab g^i_cd], g^i_ab = sum_j rho'(r) r_a r_b / r, over the neighbours inside the force cutoff, with the derivatives of the force
+        the kernels apply.  Computed on the device by computeBornMatrix, summed over the ranks (the same on every rank); valid whenever virial() is."""
+        if self.host_only:
+            raise RuntimeError("born_matrix: a host-only simulation has no device state")
+        np = self._np
+        tri = np.zeros(21, dtype=np.float64)
+        if self.lib.comdBornMatrix(self.ptr, tri.ctypes.data_as(c_double_p)) != 0:
+            raise RuntimeError("born_matrix: comdBornMatrix failed")
+        out = np.zeros((6, 6), dtype=np.float64)
+        out[np.triu_indices(6)] = tri
+        return out + np.triu(out, 1).T
+
+    def born_constants(self):
+        """{"C11", "C12", "C44"}: the cubic averages of born_matrix() / volume in eV/A^3 (x GPA_PER_EV_A3 = GPa): the elastic constants of a
+        stress-free lattice at T = 0, and the Born part of elastic_constants() otherwise."""
+        return _cubic_averages(self.born_matrix() / self.volume)
+
     # --- box deformation (not in the reference: comd-hip --erateX, --erateY, --erateZ, --deformStart, --deformFile) ---
     def _box6(self):
         out = (ctypes.c_double * 6)()
@@ -1178,6 +1203,38 @@ def heat_flux_acf(j, window):
     out = np.zeros((int(window), 3), dtype=np.float64)
     if lib_host().comdHeatFluxAcf(j.ctypes.data_as(c_double_p), j.shape[0], int(window), out.ctypes.data_as(c_double_p)) != 0:
         raise ValueError("heat_flux_acf: comdHeatFluxAcf refused the series")
+    return out
+
+
+def _cubic_averages(c):
+    return {"C11": float((c[0, 0] + c[1, 1] + c[2, 2]) / 3.0), "C12": float((c[0, 1] + c[0, 2] + c[1, 2]) / 3.0), "C44": float((c[3, 3] + c[4, 4] + c[5, 5]) / 3.0)}
+
+
+def elastic_constants(born, stress, volume, temperature, n_atoms):
+    """The stress-fluctuation elastic constants (Squire, Holt, Hoover 1969) of S samples of a fixed box (comdElasticConstants of the host library; no device):
+        C_IJ = <B_IJ> / V - (V / kB T) (<s_I s_J> - <s_I> <s_J>) + (N kB T / V) kappa_IJ,  kappa = diag(2, 2, 2, 1, 1, 1)
+    born (S, 6, 6) in eV (Simulation.born_matrix()), stress (S, 6) the pair stress -W / V in eV/A^3, volume in A^3, temperature in K.  With temperature = 0 or
+    S = 1 only the Born part is there.  Returns {"C", "born", "fluctuation", "kinetic"} (6 x 6 each, eV/A^3; C is their sum), the cubic averages "C11", "C12",
+    "C44" and "K" = (C11 + 2 C12) / 3, "G_V" = (C11 - C12 + 3 C44) / 5, "A" = 2 C44 / (C11 - C12), "cauchy_pressure" = C12 - C44.  These are derivatives with
+    respect to the Lagrangian strain: under stress they differ from stress-strain coefficients by terms in the stress.  ValueError for mismatched shapes."""
+    import numpy as np
+    born = np.ascontiguousarray(born, dtype=np.float64)
+    stress = np.ascontiguousarray(stress, dtype=np.float64)
+    if born.ndim != 3 or born.shape[1:] != (6, 6) or stress.ndim != 2 or stress.shape[1] != 6 or born.shape[0] != stress.shape[0] or born.shape[0] < 1:
+        raise ValueError(f"elastic_constants: need born (S, 6, 6) and stress (S, 6) with S >= 1 (got {born.shape}, {stress.shape})")
+    if not (volume > 0.0 and temperature >= 0.0 and n_atoms >= 0):
+        raise ValueError(f"elastic_constants: need volume > 0, temperature >= 0, n_atoms >= 0 (got {volume}, {temperature}, {n_atoms})")
+    iu = np.triu_indices(6)
+    tri = np.ascontiguousarray(born[:, iu[0], iu[1]] / float(volume))
+    parts = [np.zeros((6, 6), dtype=np.float64) for _ in range(3)]
+    if lib_host().comdElasticConstants(tri.ctypes.data_as(c_double_p), stress.ctypes.data_as(c_double_p), born.shape[0], float(volume), float(temperature),
+                                       float(n_atoms), *[q.ctypes.data_as(c_double_p) for q in parts]) != 0:
+        raise ValueError("elastic_constants: comdElasticConstants refused the samples")
+    c = (parts[0] + parts[1]) + parts[2]
+    out = {"C": c, "born": parts[0], "fluctuation": parts[1], "kinetic": parts[2]}
+    out.update(_cubic_averages(c))
+    c11, c12, c44 = out["C11"], out["C12"], out["C44"]
+    out.update(K=(c11 + 2.0 * c12) / 3.0, G_V=(c11 - c12 + 3.0 * c44) / 5.0, A=2.0 * c44 / (c11 - c12) if c11 != c12 else float("nan"), cauchy_pressure=c12 - c44)
     return out
 
 

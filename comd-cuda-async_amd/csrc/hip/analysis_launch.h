@@ -377,6 +377,38 @@ extern "C" void computeSteinhardtSummary(SimGpu* sim, double threshold, double* 
    launchSummary(sim, Steinhardt_Summary, Steinhardt_SummaryFinal, sim->steinhardtBuf, threshold, sim->steinhardtSumBuf, STEINHARDT_SUM_BLOCKS, STEINHARDT_SUM_N, out);
 }
 
+// the second-derivative sibling (born_kernels.h) of a pair functor of withPairFunction
+static BornLj bornPairOf(const SimGpu*, const VirialLj& p) { BornLj b; b.s6x14 = R(7.0) * p.a.s6x2; b.fs = p.scale(); return b; }
+static BornLjTable bornPairOf(const SimGpu*, const VirialLjTable& p) { BornLjTable b; b.t = p.t; return b; }
+template <bool SPLINE>
+static BornEam<SPLINE> bornPairOf(const SimGpu* sim, const VirialEam<SPLINE>& p)
+{
+   BornEam<SPLINE> b;
+   b.phi = p.phi; b.rho = p.rho; b.f = sim->eam_pot.f; b.phiS = p.phiS; b.rhoS = p.rhoS;
+   b.dfEmbed = p.dfEmbed; b.rhobar = sim->eam_pot.rhobar; b.dfi = R(0.0); b.d2fi = R(0.0);
+   return b;
+}
+
+// Not in the reference: the Born matrix (born_kernels.h), one kernel instance per pair function of the force paths, as computeVirial.  The rows are
+// allocated by the first call.
+extern "C" void computeBornMatrix(SimGpu* sim, double* out21)
+{
+   hipStream_t st = analysisStream(sim);
+   if (!sim->bornBuf) sim->bornBuf = dalloc<double>((size_t)(BORN_BLOCKS + 1) * BORN_N, false);
+   BornArgs v;
+   fillStencilArgs(v, sim);
+   double* out = sim->bornBuf + (size_t)BORN_BLOCKS * BORN_N;
+   withPairFunction(sim, [&](auto p, real_t rc2) {
+      v.rc2 = rc2;
+      auto b = bornPairOf(sim, p);
+      hipLaunchKernelGGL(BornMatrix_thread_atom<decltype(b)>, dim3(BORN_BLOCKS), dim3(256), 0, st, v, b, sim->bornBuf);
+   });
+   hipLaunchKernelGGL(BornMatrix_Final, dim3(1), dim3(256), 0, st, (const double*)sim->bornBuf, BORN_BLOCKS, out);
+   LAUNCH_CHECK();
+   HIP_CHECK(hipMemcpyAsync(out21, out, BORN_N * sizeof(double), hipMemcpyDeviceToHost, st));
+   HIP_CHECK(hipStreamSynchronize(st));
+}
+
 // Not in the reference: displacement tracking for the mean-squared displacement (msd_kernels.h).  on: one zeroed 32-byte record per global atom id,
 // which the drift kernels of this simulation add into from now on (already on: zeroed again, the origin becomes "now"); off: the memory is
 // freed.  1 and nothing tracked when the device cannot give the memory.

@@ -31,6 +31,7 @@
 #include "stress_kernels.h"
 #include "strain_kernels.h"
 #include "steinhardt_kernels.h"
+#include "born_kernels.h"
 #include "heatflux_kernels.h"
 #include "langevin_kernels.h"
 #include "msd_kernels.h"
@@ -617,7 +618,7 @@ extern "C" void DestroyGpu(SimGpu* sim)
                     sim->eam_pot.pairRows, sim->eam_pot.pairRowCount, sim->eam_pot.cellSel, sim->eam_pot.brickGroup, sim->eam_pot.brickList, sim->eam_pot.brickSel, sim->eam_pot.brickStats, sim->eam_pot.atomRows, sim->eam_pot.atomRowCount, sim->eam_pot.atomBrickSel,
                     sim->atoms.neighborList.brickRows, sim->atoms.neighborList.brickRowCount, sim->adapterScan, sim->lj_pot.waveCand, sim->lj_pot.waveCandCount, sim->lj_pot.packedR[0], sim->lj_pot.packedR[1], sim->lj_pot.packedF[0], sim->lj_pot.packedF[1],
                     sim->lj_pot.lj_interpolation.values, sim->virialBuf, sim->pairHistBuf, sim->dispBuf, sim->dispSumBuf, sim->cspBuf, sim->cspCoordBuf, sim->cnaBuf, sim->stressBuf, sim->stressSumBuf,
-                    sim->strainRefBuf, sim->strainBuf, sim->strainCountBuf, sim->strainSumBuf, sim->heatFluxBuf, sim->heatFluxSumBuf, sim->fdotrBuf, sim->fdotrRows, sim->profileBuf, sim->mpBuf, sim->mpRows, sim->skBuf, sim->steinhardtBuf, sim->steinhardtSumBuf };
+                    sim->strainRefBuf, sim->strainBuf, sim->strainCountBuf, sim->strainSumBuf, sim->heatFluxBuf, sim->heatFluxSumBuf, sim->fdotrBuf, sim->fdotrRows, sim->profileBuf, sim->mpBuf, sim->mpRows, sim->skBuf, sim->steinhardtBuf, sim->steinhardtSumBuf, sim->bornBuf };
    for (void* p : ptrs) if (p) HIP_CHECK(hipFree(p));
    if (sim->statusEvent) (void)hipEventDestroy((hipEvent_t)sim->statusEvent);
    if (sim->pinned) HIP_CHECK(hipHostFree(sim->pinned));

@@ -1,5 +1,5 @@
 /* analysis.c -- the host entries of the analyses (not in the reference; comd_host.h): pressure, g(r), centro-symmetry, common neighbour analysis, per-atom
- * stress and strain, Steinhardt order, heat flux and its autocorrelation, displacements, slab profiles, the Mueller-Plathe exchange and the structure factor.  Each is a call into include/comd_hip.h for this rank's share and a sum over the ranks. */
+ * stress and strain, Steinhardt order, the Born matrix and the elastic constants, heat flux and its autocorrelation, displacements, slab profiles, the Mueller-Plathe exchange and the structure factor.  Each is a call into include/comd_hip.h for this rank's share and a sum over the ranks. */
 #include "comd_host.h"
 #include "slot_gather.h"
 #include <math.h>
@@ -353,6 +353,40 @@ int comdSteinhardtSummary(SimFlat* s, double threshold, double* out10)
    out10[2] = N > 0.0 ? local[2] / N : 0.0; out10[3] = N > 0.0 ? local[3] / N : 0.0;
    out10[4] = N > 0.0 ? local[6] : 0.0; out10[5] = N > 0.0 ? local[7] : -1.0; out10[6] = N > 0.0 ? local[8] : 0.0;
    out10[7] = N > 0.0 ? local[4] / N : 0.0; out10[8] = N > 0.0 ? local[5] / N : 0.0; out10[9] = local[9];
+   return 0;
+}
+
+/* ---- the Born matrix and the stress-fluctuation elastic constants (not in the reference; comd_host.h) ---- */
+int comdBornMatrix(SimFlat* s, double* born21)
+{
+   if (!s->gpu.boxes.nAtoms) return -1;
+   double local[21];
+   computeBornMatrix(&s->gpu, local);
+   startTimer(commReduceTimer);
+   addDoubleParallel(local, born21, 21);
+   stopTimer(commReduceTimer);
+   return 0;
+}
+
+int comdElasticConstants(const double* bornOverV, const double* stress, int nSamples, double volume, double temperature, double nAtoms, double* outBorn, double* outFluct, double* outKinetic)
+{
+   if (nSamples < 1 || !(volume >= 0.0) || !(temperature >= 0.0)) return -1;
+   double meanS[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+   for (int k = 0; k < nSamples; ++k) for (int i = 0; i < 6; ++i) meanS[i] += stress[6 * (size_t)k + i] / nSamples;
+   const int fluctuating = temperature > 0.0 && nSamples >= 2;
+   for (int i = 0, c = 0; i < 6; ++i)
+      for (int j = i; j < 6; ++j, ++c) {
+         double born = 0.0, cov = 0.0;
+         for (int k = 0; k < nSamples; ++k) {
+            born += bornOverV[21 * (size_t)k + c] / nSamples;
+            cov += (stress[6 * (size_t)k + i] - meanS[i]) * (stress[6 * (size_t)k + j] - meanS[j]) / nSamples;          /* <s_I s_J> - <s_I> <s_J>, without its cancellation */
+         }
+         const double fluct = fluctuating ? -volume / (kB_eV * temperature) * cov : 0.0;
+         const double kin = fluctuating && i == j ? (i < 3 ? 2.0 : 1.0) * nAtoms * kB_eV * temperature / volume : 0.0;
+         outBorn[6 * i + j] = outBorn[6 * j + i] = born;
+         outFluct[6 * i + j] = outFluct[6 * j + i] = fluct;
+         outKinetic[6 * i + j] = outKinetic[6 * j + i] = kin;
+      }
    return 0;
 }
 

@@ -38,7 +38,10 @@
  *   printed step from global step S on; an S111/N column, PATH gets the powder average over N |k| bins; the reference has no reciprocal-space analysis),
  * --steinhardt, --stSolid X, --stFile PATH, --stDump PATH, --stDumpMax X (Steinhardt's bond-orientational order q4, q6, w4, w6 of every atom on its 12 nearest
  *   neighbours, reduced on the device at every printed step; a MeanQ6 column, atoms with q6 >= X count as solid-like, PATH gets a line per sample and the dump the
- *   values of the atoms of the last step whose q6 is at most --stDumpMax, the invalid ones always, as extended XYZ). */
+ *   values of the atoms of the last step whose q6 is at most --stDumpMax, the invalid ones always, as extended XYZ),
+ * --elastic, --elStart S, --elFile PATH (the Born matrix d^2 U / d eta d eta, summed on the device at every printed step from global step S on, and the
+ *   stress-fluctuation elastic constants C = <B>/V - V/(kB T) cov(sigma) + N kB T/V kappa of the samples at the end of the run; a C11B(GPa) column, PATH gets a
+ *   line per sample and the 6 x 6 C; a fixed box only: refused beside --erateX/Y/Z and --baro). */
 #include "comd_host.h"
 #include <getopt.h>
 #include <math.h>
@@ -92,6 +95,7 @@ Command parseCommandLine(int argc, char** argv)
    strcpy(cmd.skFile, "sk.dat");
    strcpy(cmd.stFile, "steinhardt.dat");
    cmd.stSolid = 0.45; cmd.stDumpMax = INFINITY;
+   strcpy(cmd.elFile, "elastic.dat");
    int help = 0;
 
    const ArgDef defs[] = {
@@ -194,6 +198,9 @@ Command parseCommandLine(int argc, char** argv)
       { "stFile",        0,  1, 's', cmd.stFile, sizeof cmd.stFile, "file the samples are written to (default steinhardt.dat)" },
       { "stDump",        0,  1, 's', cmd.stDump, sizeof cmd.stDump, "extended-XYZ file of q4, q6, w4, w6 of the atoms of the last step (default: none)" },
       { "stDumpMax",     0,  1, 'd', &cmd.stDumpMax,      0, "only atoms with q6 of at most this are dumped, and the atoms with fewer than 12 neighbours (default inf: all atoms)" },
+      { "elastic",       0,  0, 'i', &cmd.elastic,        0, "Born matrix at every printed step and the stress-fluctuation elastic constants C11, C12, C44, K, G at the end of the run (a C11B(GPa) column; a fixed box: not with --erateX/Y/Z or --baro)" },
+      { "elStart",       0,  1, 'i', &cmd.elStart,        0, "global step elastic sampling begins at (0..nSteps; default 0)" },
+      { "elFile",        0,  1, 's', cmd.elFile, sizeof cmd.elFile, "file the samples and the elastic constants are written to (default elastic.dat)" },
    };
    const int nDefs = (int)(sizeof defs / sizeof defs[0]);
 
@@ -290,6 +297,7 @@ void printCmdYaml(FILE* file, Command* cmd)
    if (cmd->sk) fprintf(file, "  Structure factor kMax index: %d\n  Structure factor stride: %s\n  Structure factor bins: %d\n  Structure factor from step: %d\n  Structure factor file: %s\n",
                         cmd->sk, cmd->skStride, cmd->skBins, cmd->skStart, cmd->skFile);
    if (cmd->steinhardt) fprintf(file, "  Steinhardt solid threshold: %g\n  Steinhardt file: %s\n", cmd->stSolid, cmd->stFile);
+   if (cmd->elastic) fprintf(file, "  Elastic from step: %d\n  Elastic file: %s\n", cmd->elStart, cmd->elFile);
    fprintf(file, "\n");
    fflush(file);
 }

@@ -112,6 +112,9 @@ typedef struct CommandSt {
    char stFile[1024];     /* extension: where the print rank writes the samples (default steinhardt.dat) */
    char stDump[1024];     /* extension: extended-XYZ file of the per-atom values of the last step; empty = none */
    double stDumpMax;      /* extension: only atoms with q6 of at most this are dumped, the invalid ones always; +inf = all */
+   int elastic;           /* extension: the Born matrix at every printed step, and the stress-fluctuation elastic constants at the end of the run */
+   int elStart;           /* extension: the global step sampling begins at (0..nSteps; default 0) */
+   char elFile[1024];     /* extension: where the print rank writes the samples and the constants (default elastic.dat) */
 } Command;
 
 #define COMD_LANGEVIN_SEED 0x436f4d44ull     /* "CoMD" */
@@ -465,6 +468,11 @@ typedef struct SimFlatSt {
    char stFile[1024], stDump[1024];
    RowTable stRows;                 /* [11] doubles: step, the ten values of comdSteinhardtSummary */
    double stMeanQ6Now;              /* the MeanQ6 column of printThings: the last sample */
+   /* elastic constants (--elastic): comdMain samples comdBornMatrix and the pair stress at every printed step from elStart on */
+   int elastic, elStart;
+   char elFile[1024];
+   RowTable elRows;                 /* [30] doubles: step, T (K), V (A^3), the six pair stresses -W / V and the 21 B / V (eV/A^3) */
+   double elC11BornNow;             /* the C11B(GPa) column of printThings: (B11 + B22 + B33) / 3V of the last sample */
 } SimFlat;
 
 SimFlat* initSimulation(Command cmd);
@@ -574,6 +582,16 @@ int comdSteinhardt(SimFlat* s, double* outByGid4);
  * (0 without any).  Reduced on the device and then over the ranks.  The same on every rank.  Collective.  -1 without device state or for a threshold outside
  * (0, 1). */
 int comdSteinhardtSummary(SimFlat* s, double threshold, double* out10);
+/* not in the reference: born21 = the Born matrix of the current state (computeBornMatrix, comd_hip.h, has the definition), the second derivative of the potential
+ * energy with respect to the Lagrangian strain, in eV: the upper triangle of the 6 x 6 matrix in Voigt order xx yy zz yz xz xy, row-major, summed over the
+ * ranks.  Valid whenever computePressure is: after a complete force evaluation.  The same on every rank.  Collective.  -1 and nothing launched without device state. */
+int comdBornMatrix(SimFlat* s, double* born21);
+/* not in the reference: the stress-fluctuation elastic constants (Squire, Holt, Hoover 1969) of nSamples samples of a fixed box, in the units of the input:
+ *   C_IJ = <B_IJ> / V - (V / kB T) (<s_I s_J> - <s_I> <s_J>) + (N kB T / V) kappa_IJ,  kappa = diag(2, 2, 2, 1, 1, 1)
+ * bornOverV[nSamples][21] the upper triangles of B / V, stress[nSamples][6] the pair stresses -W / V (both eV/A^3), volume in A^3, temperature in K.  With
+ * temperature = 0 or fewer than two samples the fluctuation and kinetic parts are 0.  outBorn, outFluct, outKinetic: the three parts, 6 x 6 each, row-major; their
+ * sum is C.  Pure arithmetic; -1 for nSamples < 1 or a volume or temperature that is not >= 0. */
+int comdElasticConstants(const double* bornOverV, const double* stress, int nSamples, double volume, double temperature, double nAtoms, double* outBorn, double* outFluct, double* outKinetic);
 /* not in the reference (its box is nx lat for the whole run): box deformation, LAMMPS's `fix deform ... remap x`.
  * comdSetBox: the global box becomes L[3] Angstroms (the origin stays at 0) and the positions of the local atoms are scaled with it, L_new / L_old per axis, by
  *    comdRemapBoxGpu.  Every copy of the geometry follows: Domain (the expressions of initDecomposition, so neighbouring ranks agree bit for bit on their shared
@@ -680,7 +698,7 @@ void ensureInteriorForceLaunched(SimFlat* sim);
 
 /* ---- performanceTimers.h ---- */
 enum TimerHandle { totalTimer, loopTimer, timestepTimer, positionTimer, velocityTimer, redistributeTimer, atomHaloTimer,
-                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, cspTimer, cnaTimer, deformTimer, stressTimer, strainTimer, heatfluxTimer, baroTimer, profileTimer, mpTimer, skTimer, steinhardtTimer, numberOfTimers };
+                   computeForceTimer, eamHaloTimer, commHaloTimer, commReduceTimer, neighborListBuildTimer, pressureTimer, rdfTimer, msdTimer, cspTimer, cnaTimer, deformTimer, stressTimer, strainTimer, heatfluxTimer, baroTimer, profileTimer, mpTimer, skTimer, steinhardtTimer, elasticTimer, numberOfTimers };
 void profileStart(enum TimerHandle handle);
 void profileStop(enum TimerHandle handle);
 double getElapsedTime(enum TimerHandle handle);

@@ -3,6 +3,7 @@
 #include "comd_host.h"
 #include <math.h>
 #include <stdlib.h>
+#include <string.h>
 
 /* the next row of a table of samples that grows by doubling */
 void* nextRow(RowTable* t, size_t rowBytes)
@@ -704,6 +705,83 @@ static void writeSteinhardt(FILE* yaml, SimFlat* s, int iStep)
            last ? last[4] : 0.0, atoms > 0.0 ? last[10] / atoms : 0.0);
 }
 
+/* --elastic: one more row {step, T (K), V (A^3), the pair stress sigma_I = -W_I / V (6) and the upper triangle of B / V (21), eV/A^3} from the tensors computePressure
+ * has just left in W, V and the device's Born matrix */
+#define ELASTIC_ROW 30
+#define ELASTIC_T_REST 1e-9            /* K: below this mean temperature the lattice is at rest (a -T 0 run picks up 1e-28 K from forces that are rounding errors, and
+                                        * V / kB T times the rounding noise of the stress is no fluctuation term): T counts as 0 */
+static void sampleElastic(SimFlat* s, int iStep)
+{
+   double* row = (double*)nextRow(&s->elRows, ELASTIC_ROW * sizeof(double));
+   double born[21];
+   if (comdBornMatrix(s, born) != 0) { printf("Error: --elastic needs the device state.\n"); exit(-1); }
+   row[0] = (double)iStep;
+   row[1] = (s->eKinetic / s->atoms->nGlobal) / (kB_eV * 1.5);
+   row[2] = (double)s->V;
+   for (int c = 0; c < 6; ++c) row[3 + c] = -(double)s->W[c] / s->V;
+   for (int c = 0; c < 21; ++c) row[9 + c] = born[c] / s->V;
+   s->elC11BornNow = (row[9] + row[15] + row[20]) / 3.0;
+}
+
+/* the cubic averages of a 6 x 6 matrix: (11 + 22 + 33) / 3, (12 + 13 + 23) / 3, (44 + 55 + 66) / 3 */
+static void cubicAverages(const double* m, double out[3])
+{
+   out[0] = (m[0] + m[7] + m[14]) / 3.0; out[1] = (m[1] + m[2] + m[8]) / 3.0; out[2] = (m[21] + m[28] + m[35]) / 3.0;
+}
+
+/* --elastic: the file: a header line, per sample the step, T, V, the six pair stresses and the 21 B_IJ / V in GPa, then the 6 x 6 C in GPa behind '#'.  The
+ * YAML block gives C11, C12, C44 (cubic averages) with their Born, fluctuation and kinetic parts, K = (C11 + 2 C12) / 3, G_V = (C11 - C12 + 3 C44) / 5,
+ * A = 2 C44 / (C11 - C12) and the Cauchy pressure C12 - C44; T and V are the means over the samples, a T below ELASTIC_T_REST counting as 0.  Derivatives with respect to the Lagrangian strain:
+ * under stress they differ from stress-strain coefficients by terms in the stress. */
+static void writeElastic(FILE* yaml, SimFlat* s, int iStep)
+{
+   if (!printRank()) return;
+   const int samples = s->elRows.n;
+   const double* rows = (const double*)s->elRows.rows;
+   double T = 0.0, V = 0.0;
+   for (int k = 0; k < samples; ++k) { T += rows[ELASTIC_ROW * (size_t)k + 1] / samples; V += rows[ELASTIC_ROW * (size_t)k + 2] / samples; }
+   if (T < ELASTIC_T_REST) T = 0.0;
+   const size_t nRows = samples > 0 ? (size_t)samples : 1;
+   double *born = (double*)malloc(nRows * 21 * sizeof(double)), *stress = (double*)malloc(nRows * 6 * sizeof(double));
+   for (int k = 0; k < samples; ++k) {
+      for (int c = 0; c < 6; ++c) stress[6 * (size_t)k + c] = rows[ELASTIC_ROW * (size_t)k + 3 + c];
+      for (int c = 0; c < 21; ++c) born[21 * (size_t)k + c] = rows[ELASTIC_ROW * (size_t)k + 9 + c];
+   }
+   double part[3][36], C[36];
+   memset(part, 0, sizeof part);
+   if (samples > 0) comdElasticConstants(born, stress, samples, V, T, (double)s->atoms->nGlobal, part[0], part[1], part[2]);
+   for (int c = 0; c < 36; ++c) C[c] = (part[0][c] + part[1][c]) + part[2][c];
+   free(born); free(stress);
+   FILE* f = openReport(s->elFile);
+   fprintf(f, "# Elastic: N %d samples %d T %.17g V %.17g | columns: step, T (K), V (A^3), pair stress xx yy zz yz xz xy (GPa, tension positive), "
+              "B/V 11 12 13 14 15 16 22 23 24 25 26 33 34 35 36 44 45 46 55 56 66 (GPa)\n", s->atoms->nGlobal, samples, T, V);
+   for (int k = 0; k < samples; ++k) {
+      const double* r = rows + ELASTIC_ROW * (size_t)k;
+      fprintf(f, "%.0f %.17g %.17g", r[0], r[1], r[2]);
+      for (int c = 3; c < ELASTIC_ROW; ++c) fprintf(f, " %.17g", r[c] * eVperA3inGPa);
+      fprintf(f, "\n");
+   }
+   fprintf(f, "# C (GPa) = <B>/V - V/(kB T) (<s s> - <s><s>) + N kB T/V kappa, Voigt order xx yy zz yz xz xy:\n");
+   for (int i = 0; i < 6; ++i) {
+      fprintf(f, "#");
+      for (int j = 0; j < 6; ++j) fprintf(f, " %.17g", C[6 * i + j] * eVperA3inGPa);
+      fprintf(f, "\n");
+   }
+   fclose(f);
+   if (!yaml) return;
+   static const char* name[3] = { "C11", "C12", "C44" };
+   double c[3], b[3], fl[3], kin[3];
+   cubicAverages(C, c); cubicAverages(part[0], b); cubicAverages(part[1], fl); cubicAverages(part[2], kin);
+   fprintf(yaml, "Elastic:\n  samples: %d\n  fromStep: %d\n  temperature: %.12e\n  volume: %.12e\n  file: %s\n  Units: GPa\n", samples, s->elStart, T, V, s->elFile);
+   for (int m = 0; m < 3; ++m)
+      fprintf(yaml, "  %s: %.12e\n  %sBorn: %.12e\n  %sFluctuation: %.12e\n  %sKinetic: %.12e\n", name[m], c[m] * eVperA3inGPa, name[m], b[m] * eVperA3inGPa,
+              name[m], fl[m] * eVperA3inGPa, name[m], kin[m] * eVperA3inGPa);
+   fprintf(yaml, "  bulkModulus: %.12e\n  shearModulusVoigt: %.12e\n  cauchyPressure: %.12e\n", (c[0] + 2.0 * c[1]) / 3.0 * eVperA3inGPa,
+           (c[0] - c[1] + 3.0 * c[2]) / 5.0 * eVperA3inGPa, (c[1] - c[2]) * eVperA3inGPa);
+   if (c[0] != c[1]) fprintf(yaml, "  anisotropy: %.12e\n\n", 2.0 * c[2] / (c[0] - c[1])); else fprintf(yaml, "  anisotropy: n/a\n\n");
+   (void)iStep;
+}
+
 /* ---- the table: one row per report, in the order of the columns of printThings and of the YAML blocks ---------------------------------------------------------
  * on      the row applies to this run;
  * from    the first global step it samples at (NULL: 0), start what is done when the run reaches that step: at a printed step under the report's timer, just
@@ -725,7 +803,7 @@ typedef struct ReportSt {
    int  writeTimed;
 } Report;
 
-static int virialOn(const SimFlat* s)      { return s->pressure || s->deformReport || s->baroReport; }
+static int virialOn(const SimFlat* s)      { return s->pressure || s->deformReport || s->baroReport || s->elastic; }
 static int pressureShown(const SimFlat* s) { return s->pressure || s->baroReport; }
 static int pressureOn(const SimFlat* s)    { return s->pressure; }
 static int rdfOn(const SimFlat* s)         { return s->rdfBins; }
@@ -742,12 +820,14 @@ static int profileOn(const SimFlat* s)     { return s->profile; }
 static int mpOn(const SimFlat* s)          { return s->mpReport; }
 static int skOn(const SimFlat* s)          { return s->sk; }
 static int steinhardtOn(const SimFlat* s)  { return s->steinhardt; }
+static int elasticOn(const SimFlat* s)     { return s->elastic; }
 
 static int msdFrom(const SimFlat* s)       { return s->msdStart; }
 static int strainFrom(const SimFlat* s)    { return s->strainRef; }
 static int heatfluxFrom(const SimFlat* s)  { return s->hfStart; }
 static int profileFrom(const SimFlat* s)   { return s->profStart; }
 static int skFrom(const SimFlat* s)        { return s->skStart; }
+static int elasticFrom(const SimFlat* s)   { return s->elStart; }
 
 static double volumeRatio(const SimFlat* s) { return (double)s->V / (s->box0[0] * s->box0[1] * s->box0[2]); }
 static void pressureColumn(const SimFlat* s) { fprintf(screenOut, " %16.10f", pressureOf(s) * eVperA3inGPa); }
@@ -762,6 +842,7 @@ static void heatfluxColumn(const SimFlat* s) { fprintf(screenOut, " %19.10e", s-
 static void mpColumn(const SimFlat* s)       { fprintf(screenOut, " %19.10e", s->mpExchanged); }
 static void skColumn(const SimFlat* s)       { fprintf(screenOut, " %16.10f", s->skBraggNow); }
 static void steinhardtColumn(const SimFlat* s) { fprintf(screenOut, " %16.10f", s->stMeanQ6Now); }
+static void elasticColumn(const SimFlat* s)  { fprintf(screenOut, " %16.10f", s->elC11BornNow * eVperA3inGPa); }
 
 static const Report reports[] = {
    { .on = virialOn,        .sample = samplePressure, .timer = pressureTimer },      /* first: the samplers below read W, K, V */
@@ -783,6 +864,7 @@ static const Report reports[] = {
    { .on = mpOn,            .header = "              dE(eV)", .column = mpColumn },      /* its rows: mpExchange, inside timestep() */
    { .on = skOn,            .from = skFrom, .sample = sampleSk, .timer = skTimer, .header = "           S111/N", .column = skColumn, .write = writeSk },
    { .on = steinhardtOn,    .sample = sampleSteinhardt, .timer = steinhardtTimer, .header = "           MeanQ6", .column = steinhardtColumn, .write = writeSteinhardt },
+   { .on = elasticOn,       .from = elasticFrom, .sample = sampleElastic, .timer = elasticTimer, .header = "        C11B(GPa)", .column = elasticColumn, .write = writeElastic },
 };
 #define FOR_REPORTS(r, s) for (const Report* r = reports; r < reports + sizeof reports / sizeof reports[0]; ++r) if (r->on(s))
 
@@ -828,7 +910,7 @@ void reportsWrite(FILE* yaml, SimFlat* s, int iStep)
 
 void reportsFree(SimFlat* s)
 {
-   RowTable* tables[] = { &s->msdRows, &s->cspRows, &s->cnaRows, &s->deformRows, &s->baroRows, &s->mpRows, &s->stressRows, &s->strainRows, &s->hfRows, &s->stRows };
+   RowTable* tables[] = { &s->msdRows, &s->cspRows, &s->cnaRows, &s->deformRows, &s->baroRows, &s->mpRows, &s->stressRows, &s->strainRows, &s->hfRows, &s->stRows, &s->elRows };
    for (size_t i = 0; i < sizeof tables / sizeof tables[0]; ++i) free(tables[i]->rows);
    free(s->rdfSum); free(s->cspLast); free(s->cnaLast); free(s->profSum); free(s->skSum);
 }

@@ -277,6 +277,13 @@ SimFlat* initSimulationHost(Command cmd)
    if (!(cmd.stDumpMax > 0.0)) { printf("Error: --stDumpMax must be > 0 (got %g).\n", cmd.stDumpMax); exit(-1); }
    sim->steinhardt = cmd.steinhardt; sim->stSolid = cmd.stSolid; sim->stDumpMax = cmd.stDumpMax;
    strcpy(sim->stFile, cmd.stFile); strcpy(sim->stDump, cmd.stDump);
+   /* --elastic (not in the reference): the fluctuation formula is for a fixed box */
+   if (cmd.elastic) {
+      if (cmd.erate[0] != 0.0 || cmd.erate[1] != 0.0 || cmd.erate[2] != 0.0 || cmd.baro) { printf("Error: --elastic needs a fixed box: it cannot run with --erateX/Y/Z or --baro.\n"); exit(-1); }
+      if (cmd.elStart < 0 || cmd.elStart > cmd.nSteps) { printf("Error: --elStart must lie in 0..nSteps (got %d).\n", cmd.elStart); exit(-1); }
+   }
+   sim->elastic = cmd.elastic; sim->elStart = cmd.elStart;
+   strcpy(sim->elFile, cmd.elFile);
    sanityChecks(cmd, sim->pot->cutoff, latticeConstant, sim->pot->latticeType);
    sim->species = initSpecies(sim->pot);
 

@@ -1,4 +1,4 @@
-/* timers.c -- the reference's twelve wall-clock timers (+ pressure, rdf, msd, csp, cna, deform, stress, strain, heatflux, barostat, profile, mp, sk and steinhardt, shown only when used) and its end-of-run report
+/* timers.c -- the reference's twelve wall-clock timers (+ pressure, rdf, msd, csp, cna, deform, stress, strain, heatflux, barostat, profile, mp, sk, steinhardt and elastic, shown only when used) and its end-of-run report
  * (performanceTimers.c:55-340: names, per-rank table, cross-rank statistics, three rate figures,
  * YAML block).  Like the reference's, these are host timers: GPU work lands in whichever timer
  * hits the next blocking call (performanceTimers.h:29-44).  With --deviceTimers (timersUseDevice) every
@@ -14,7 +14,7 @@
 
 static const char* timerName[numberOfTimers] = {
    "total", "loop", "timestep", "  position", "  velocity", "  redistribute", "    atomHalo",
-   "  force", "    eamHalo", "commHalo", "commReduce", "  neighborList", "pressure", "rdf", "msd", "csp", "cna", "  deform", "stress", "strain", "heatflux", "  barostat", "profile", "  mp", "sk", "steinhardt"
+   "  force", "    eamHalo", "commHalo", "commReduce", "  neighborList", "pressure", "rdf", "msd", "csp", "cna", "  deform", "stress", "strain", "heatflux", "  barostat", "profile", "  mp", "sk", "steinhardt", "elastic"
 };
 
 typedef struct { uint64_t start, total, count, elapsed; int minRank, maxRank; double minValue, maxValue, average, stdev; } Timers;

@@ -267,6 +267,7 @@ typedef struct SimGpuSt {
    uint64_t     skCap;                 /* doubles in skBuf */
    real_t*      steinhardtBuf;         /* device [4][nLocalBoxes*maxAtoms]: the planes q4 q6 w4 w6 of computeSteinhardt, allocated by its first call */
    double*      steinhardtSumBuf;      /* device: the workgroups' rows for computeSteinhardtSummary, allocated with steinhardtBuf */
+   double*      bornBuf;               /* device: the workgroups' rows of 21 for computeBornMatrix and their sum, allocated by its first call */
 } SimGpu;
 
 /* Everything AllocateGpu needs to know about the rank's geometry and potential.
@@ -613,6 +614,18 @@ void computeSteinhardt(SimGpu* sim, real_t* outBySlot4);
  * -- over THIS rank's atoms; without valid atoms the extremes are +inf and -inf.  Ten doubles are copied, never the planes.  Deterministic two-stage
  * reduction.  A call without a computeSteinhardt before it ends the run.  Blocks until the result is on the host. */
 void computeSteinhardtSummary(SimGpu* sim, double threshold, double* out);
+/* Not in the reference (CoMD computes no elastic property): the Born matrix of THIS rank's local atoms (hip/born_kernels.h), the second derivative of the
+ * potential energy with respect to the Lagrangian strain eta at the current configuration, in eV (extensive):
+ *   B_abcd = sum_i [ sum_j ( 1/2 (phi'' - phi'/r) + F'_i (rho'' - rho'/r) ) r_a r_b r_c r_d / r^2  +  F''(rhobar_i) g^i_ab g^i_cd ],  g^i_ab = sum_j rho'(r) r_a r_b / r
+ * j over the neighbours (local or halo image) with 0 < r^2 <= rc^2, the acceptance test and the pair convention of computeVirial: every pair is seen from both
+ * sides, so the sum over the ranks is the matrix of the whole system.  LJ has no F terms.  The derivatives are those of the force the kernels apply: exact for
+ * analytic LJ; for the quadratic tables (EAM funcfl / setfl, -I, and F(rhobar) in every mode) the derivative of interpolate's df, constant on the segment
+ * interpolate lands on; for the -P splines those of the cubic in r^2.  F'_i and F''_i come from dfEmbed and rhobar of the last force evaluation.
+ * out21: the upper triangle of the symmetric 6 x 6 matrix in Voigt order xx yy zz yz xz xy, row-major (11 12 13 14 15 16 22 23 ... 66), doubles in both builds.
+ * Valid when computeVirial is: after a complete force evaluation (timestep, computeForce), any method.  Same stream and ordering as computeVirial; no atomics,
+ * a fixed grid, bit-reproducible; reads r, rhobar, dfEmbed and the cell tables, writes only its own rows (allocated by the first call, freed by DestroyGpu).
+ * Blocks until the result is on the host. */
+void computeBornMatrix(SimGpu* sim, double* out21);
 /* Not in the reference: unwrapped displacements since an origin, for the mean-squared displacement (hip/msd_kernels.h).  on != 0: allocate and zero
  * one 32-byte record {dx, dy, dz, spare} per global atom id, signed 64-bit fixed point in units of 2^-32 Angstroms; from then on the drift kernels
  * of this simulation (advancePositionGpu and the fused forms, plain and Langevin) add dt p/m of every local atom into the record of its gid.  Already
